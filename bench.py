@@ -19,6 +19,12 @@ The same line carries a ``secondary`` object (never the judged ``value``; timed 
 32 of 128x128 LR per GPU; with N ranks the data-parallel path with one RCCL all-reduce per gradient arena) and ``c5_tiled_4k`` =
 BASELINE configs[4], one 4K frame through the tile-sharded path — each with its own roofline of its dominant kernel.
 ``--no-secondary`` skips them; ``--mode train|tiled`` and ``--dtype bf16`` print those workloads as lines of their own (tuning).
+
+``--dump-outputs DIR`` writes what the last timed step of the chosen mode computed as DIR/<name>.npy (dump_outputs): ``output``
+(the super-resolved batch; --mode train: the generator's output, plus one ``loss_<name>`` per logged loss) or ``frame`` (--mode
+tiled, a fixed sample of the uint8 4K frame rank 0 assembles, as float32); with N ranks the other modes write ``<name>_rank<r>``
+per rank, within 64 MB together.  Inputs and weights are seeded, so the same arguments give the same inputs in every run and two
+builds can be compared file for file.
 """
 import argparse
 import ctypes as C
@@ -35,7 +41,7 @@ sys.path.insert(0, ROOT)
 CFG = dict(num_in_ch=3, num_out_ch=3, scale=4, num_feat=64, num_block=23, num_grow_ch=32)
 BATCH = 16
 TILE = 128
-PEAK_F32_TFLOPS = 157.3   # MI355X fp32 MFMA (v_mfma_f32_32x32x2_f32), /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_F32_TFLOPS = 157.3   # MI355X fp32 MFMA (v_mfma_f32_32x32x2_f32)
 PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA (v_mfma_f32_32x32x16_bf16); secondary --dtype bf16 run only
 PEAK_HBM_GBS = 8000.0
 FLOPS_PER_IMAGE = 5.8743e11
@@ -207,6 +213,34 @@ def roofline_of(ks, peak_tflops, suffix=''):
                  'mfma_frac': round(mfma_frac, 4)}, **common)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """``--dump-outputs``: writes each ``name -> tensor | array | number`` of ``arrays`` as ``directory/<name>.npy``, float64 data as
+    float64 and everything else (fp32, bf16, uint8 ...) as float32, so that two builds can be compared output for output.  When the
+    arrays together are larger than ``budget`` bytes, each one over its equal share is replaced by a fixed sample of its flattened
+    elements: indices drawn from a PCG64 stream seeded with DUMP_SAMPLE_SEED, deduplicated and sorted, so the same shape always gives
+    the same sample."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a)) for k, a in arrays.items()}
+    total = sum(t.numel() * (8 if t.dtype == torch.float64 else 4) for t in arrays.values())
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        itemsize = 8 if dtype == torch.float64 else 4
+        if total > budget and t.numel() * itemsize > share:
+            idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, t.numel(), share // itemsize))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, f'{name}.npy'), t.to(dtype).cpu().numpy())
+
+
+def _rank_name(name, world, rank):
+    return name if world == 1 else f'{name}_rank{rank}'
+
+
 def _sync(dist):
     if dist is not None:
         dist.barrier()
@@ -221,7 +255,7 @@ def _max_over_ranks(dt, dist, dev, backend):
     return float(t.item())
 
 
-def measure_train(world, rank, dev, dist, backend, *, yml, dtype, disc, disc_dtype, batch, lq, steps, warmup, profile):
+def measure_train(world, rank, dev, dist, backend, *, yml, dtype, disc, disc_dtype, batch, lq, steps, warmup, profile, dump=None):
     """Whole ESRGANModel.optimize_parameters steps (generator forward/backward, discriminator passes, losses, both fused Adam steps,
     EMA) on synthetic batches resident in HBM; with N ranks the model's own data-parallel path runs (replica alignment at
     construction, one RCCL all-reduce of each gradient arena per step) and per-GPU work is fixed (weak scaling)."""
@@ -264,6 +298,9 @@ def measure_train(world, rank, dev, dist, backend, *, yml, dtype, disc, disc_dty
     dt = _max_over_ranks(time.perf_counter() - t0, dist, dev, backend)
     log = model.get_current_log()
     assert all(v == v and abs(v) < 1e30 for v in log.values()), log
+    if dump:   # the last timed step's generator output and losses
+        dump_outputs(dump, dict({_rank_name('output', world, rank): model.output},
+                                **{_rank_name(f'loss_{k}', world, rank): float(v) for k, v in log.items()}), DUMP_BUDGET_BYTES // world)
     res = {
         'metric': 'images/sec (ESRGAN training step: 23-block RRDBNet + %s, L1 + relativistic GAN loss, Adam, EMA)' % opt['network_d']['type'],
         'value': round(world * batch * steps / dt, 3), 'unit': 'images/sec', 'n_gpus': world, 'steps': steps,
@@ -288,7 +325,7 @@ def measure_train(world, rank, dev, dist, backend, *, yml, dtype, disc, disc_dty
     return res
 
 
-def measure_tiled(net, world, rank, dev, dist, backend, *, dtype, steps, warmup, tile_batch, profile):
+def measure_tiled(net, world, rank, dev, dist, backend, *, dtype, steps, warmup, tile_batch, profile, dump=None):
     """BASELINE configs[4]: one 4K frame (3840x2160 LR) through the tiler — 512x512 cells + 16 px pad, the cells sharded over the
     ranks, HR crops gathered onto rank 0 by one RCCL gather (uint8 output convention).  One frame is split over all ranks, so this
     is strong scaling; a step = one whole frame assembled on rank 0."""
@@ -313,6 +350,8 @@ def measure_tiled(net, world, rank, dev, dist, backend, *, dtype, steps, warmup,
     dt = _max_over_ranks(time.perf_counter() - t0, dist, dev, backend)
     if rank == 0:
         assert out.shape == (1, 3, 4 * H, 4 * W) and out.dtype == torch.uint8
+        if dump:   # the frame assembled on rank 0 by the last timed step
+            dump_outputs(dump, {'frame': out})
     from image_restoration_amd import watchdog
     res = {
         'handoff_fallbacks': watchdog.fallback_count,  # tiled_forward repeats timed-out cells on the chain launch: 0 = the fused kernel ran
@@ -456,7 +495,12 @@ def main():
     ap.add_argument('--no-secondary', action='store_true', help='skip the C3 training step and the C5 tiled frame next to the headline')
     ap.add_argument('--secondary-timeout', type=float, default=300.0)
     ap.add_argument('--profile', action='store_true', help='--mode train|tiled: add the roofline of the dominant kernel')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB '
+                         'in all; a fixed seeded sample of a larger output)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(args.gpus)   # nothing above or in self_launch touches the GPU
@@ -520,7 +564,7 @@ def main():
     if args.mode == 'train':
         return finish(measure_train(world, rank, dev, dist, backend, yml='train_rrdbnet_esrgan_x4_mi355x.yml', dtype=args.dtype,
                                     disc=args.disc, disc_dtype=args.disc_dtype, batch=args.batch, lq=args.lq, steps=args.steps,
-                                    warmup=args.warmup, profile=args.profile))
+                                    warmup=args.warmup, profile=args.profile, dump=args.dump_outputs))
 
     import image_restoration_amd as ira
     from image_restoration_amd.utils import synth
@@ -528,7 +572,7 @@ def main():
     net.load_state_dict({k: torch.from_numpy(v) for k, v in synth.rrdbnet_state_dict(0, **CFG).items()}, strict=True)
     if args.mode == 'tiled':
         return finish(measure_tiled(net, world, rank, dev, dist, backend, dtype=args.dtype, steps=args.steps, warmup=args.warmup,
-                                    tile_batch=args.tile_batch, profile=args.profile))
+                                    tile_batch=args.tile_batch, profile=args.profile, dump=args.dump_outputs))
     net.set_compute_dtype(args.dtype)
     x = torch.from_numpy(synth.uniform_input(1234 + rank, (BATCH, 3, TILE, TILE))).to(dev)
 
@@ -546,6 +590,8 @@ def main():
     assert bool(torch.isfinite(y).all())
     from image_restoration_amd import watchdog
     watchdog.verify('bench.py headline', synchronize=False)   # a timed-out dense-block launch would have produced a fast, wrong number
+    if args.dump_outputs:   # the super-resolved batch of the last timed step
+        dump_outputs(args.dump_outputs, {_rank_name('output', world, rank): y}, DUMP_BUDGET_BYTES // world)
 
     value = world * BATCH * args.steps / dt
     line = {
