@@ -530,8 +530,9 @@ __global__ void psnr_finalize_kernel(const float* part, int nparts, float* out) 
 }
 
 // SSIM map sum (psnr_ssim.py:49-83): 11x11 Gaussian (sigma 1.5) statistics over the valid region of the border-cropped,
-// uint8-quantised channel; one thread per output pixel, 121 taps, float accumulation of integers <= 255^2 weighted by a
-// normalised window (relative error ~1e-6, the reference computes in float64).
+// uint8-quantised channel; one thread per output pixel, 121 taps, float accumulation.  The moments are taken about the window's
+// centre value (ca, cb) and the shift is added back to the means: variances and covariance are shift-invariant, and in a bright,
+// flat window the raw second moment (~6e4) would cancel against mean^2 in fp32 (SSIM errors ~5e-5 against the float64 reference).
 struct SsimWin {
   float w[11];
 };
@@ -547,13 +548,15 @@ __global__ __launch_bounds__(256) void ssim_sum_kernel(const float* __restrict__
     const int x = (int)(i % ww), y = (int)((i / ww) % hh), ch = (int)(i / ((long long)ww * hh));
     const float* pa = a + (((long long)n * c + ch) * h + (y + crop)) * w + (x + crop);
     const float* pb = b + (((long long)n * c + ch) * h + (y + crop)) * w + (x + crop);
-    float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
+    const float ca = rintf(fminf(fmaxf(pa[5 * w + 5], 0.f), 1.f) * 255.f);
+    const float cb = rintf(fminf(fmaxf(pb[5 * w + 5], 0.f), 1.f) * 255.f);
+    float m1 = 0.f, m2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;  // moments of (qa - ca), (qb - cb)
     for (int dy = 0; dy < 11; ++dy) {
       float r1 = 0.f, r2 = 0.f, r11 = 0.f, r22 = 0.f, r12 = 0.f;
 #pragma unroll
       for (int dx = 0; dx < 11; ++dx) {
-        const float qa = rintf(fminf(fmaxf(pa[dy * w + dx], 0.f), 1.f) * 255.f);
-        const float qb = rintf(fminf(fmaxf(pb[dy * w + dx], 0.f), 1.f) * 255.f);
+        const float qa = rintf(fminf(fmaxf(pa[dy * w + dx], 0.f), 1.f) * 255.f) - ca;
+        const float qb = rintf(fminf(fmaxf(pb[dy * w + dx], 0.f), 1.f) * 255.f) - cb;
         const float g = win.w[dx];
         r1 += g * qa;
         r2 += g * qb;
@@ -569,7 +572,8 @@ __global__ __launch_bounds__(256) void ssim_sum_kernel(const float* __restrict__
       s12 += g * r12;
     }
     const float v1 = s11 - m1 * m1, v2 = s22 - m2 * m2, cv = s12 - m1 * m2;
-    s += ((2.f * m1 * m2 + C1) * (2.f * cv + C2)) / ((m1 * m1 + m2 * m2 + C1) * (v1 + v2 + C2));
+    const float mu1 = ca + m1, mu2 = cb + m2;
+    s += ((2.f * mu1 * mu2 + C1) * (2.f * cv + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (v1 + v2 + C2));
   }
   s = block_sum(s, sh);
   if (threadIdx.x == 0) part[(long long)n * gridDim.x + blockIdx.x] = s;

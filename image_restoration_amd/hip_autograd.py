@@ -195,12 +195,14 @@ class LinearFn(torch.autograd.Function):
 
 
 class L1LossFn(torch.autograd.Function):
-    """loss_weight * mean|pred - target| (sr_l1_loss_fwd_f32 / sr_l1_loss_bwd_f32)."""
+    """loss_weight * mean|pred - target| (sr_l1_loss_fwd_f32 / sr_l1_loss_bwd_f32).  Inputs of any floating dtype are computed
+    in fp32; the gradient comes back in pred's dtype (as torch's losses do)."""
 
     @staticmethod
     def forward(ctx, pred, target, weight):
         lib = _lib.load()
-        pred, target = pred.contiguous(), target.contiguous()
+        ctx.dtype = pred.dtype
+        pred, target = pred.contiguous().float(), target.contiguous().float()
         dev = pred.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
         wsb = lib.sr_reduce_workspace_bytes(8)
@@ -222,7 +224,7 @@ class L1LossFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check(lib.sr_l1_loss_bwd_f32(pred.data_ptr(), target.data_ptr(), pred.numel(), ctx.weight, g.data_ptr(),
                                               dp.data_ptr(), _stream(dev)), 'sr_l1_loss_bwd_f32')
-        return dp, None, None
+        return dp.to(ctx.dtype), None, None
 
 
 class GramFn(torch.autograd.Function):
@@ -256,12 +258,13 @@ class GramFn(torch.autograd.Function):
 
 class PixelLossFn(torch.autograd.Function):
     """weight * mean(criterion(pred - target)), criterion kind 1 = squared error, 2 = Charbonnier(eps)
-    (sr_pixel_loss_fwd_f32 / sr_pixel_loss_bwd_f32)."""
+    (sr_pixel_loss_fwd_f32 / sr_pixel_loss_bwd_f32); fp32 arithmetic, the gradient in pred's dtype (as L1LossFn)."""
 
     @staticmethod
     def forward(ctx, pred, target, weight, kind, eps):
         lib = _lib.load()
-        pred, target = pred.contiguous(), target.contiguous()
+        ctx.dtype = pred.dtype
+        pred, target = pred.contiguous().float(), target.contiguous().float()
         dev = pred.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
         wsb = lib.sr_reduce_workspace_bytes(8)
@@ -284,7 +287,7 @@ class PixelLossFn(torch.autograd.Function):
             _lib.check(lib.sr_pixel_loss_bwd_f32(pred.data_ptr(), target.data_ptr(), pred.numel(), kind, eps, weight,
                                                  g.contiguous().float().data_ptr(), dp.data_ptr(), _stream(dev)),
                        'sr_pixel_loss_bwd_f32')
-        return dp, None, None, None, None
+        return dp.to(ctx.dtype), None, None, None, None
 
 
 class GanPointLossFn(torch.autograd.Function):
@@ -293,6 +296,7 @@ class GanPointLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kind, c, weight):
         lib = _lib.load()
+        ctx.dtype = x.dtype
         x = x.contiguous().float()
         dev = x.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
@@ -314,18 +318,20 @@ class GanPointLossFn(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _lib.check(lib.sr_gan_point_loss_bwd_f32(x.data_ptr(), x.numel(), kind, c, weight, g.contiguous().float().data_ptr(),
                                                      dx.data_ptr(), _stream(x.device)), 'sr_gan_point_loss_bwd_f32')
-        return dx, None, None, None
+        return dx.to(ctx.dtype), None, None, None
 
 
 class BCELogitsFn(torch.autograd.Function):
     """weight * BCEWithLogits(x - mean(other), target) with `other` optional (plain GAN loss when None).
 
-    The relativistic-average form of esrgan_model.py:40-41,67,71; gradients reach both x and other."""
+    The relativistic-average form of esrgan_model.py:40-41,67,71; gradients reach both x and other.  fp32 arithmetic; each
+    gradient comes back in its input's dtype."""
 
     @staticmethod
     def forward(ctx, x, other, target_is_real, weight):
         lib = _lib.load()
-        x = x.contiguous()
+        ctx.dtypes = (x.dtype, other.dtype if other is not None else None)
+        x = x.contiguous().float()
         dev = x.device
         wsb = lib.sr_reduce_workspace_bytes(8)
         ws = scratch(dev, wsb)
@@ -333,7 +339,7 @@ class BCELogitsFn(torch.autograd.Function):
         shift = dsum = None
         with torch.cuda.device(dev):
             if other is not None:
-                other = other.contiguous()
+                other = other.contiguous().float()
                 shift = torch.empty((), dtype=torch.float32, device=dev)
                 dsum = torch.empty((), dtype=torch.float32, device=dev)
                 _lib.check(lib.sr_mean_f32(other.data_ptr(), other.numel(), shift.data_ptr(), ws.data_ptr(), wsb, _stream(dev)),
@@ -364,13 +370,18 @@ class BCELogitsFn(torch.autograd.Function):
                 dother = torch.empty(ctx.other_shape, dtype=torch.float32, device=dev)
                 _lib.check(lib.sr_fill_scaled_f32(g.data_ptr(), dsum.data_ptr(), -1.0 / dother.numel(), dother.data_ptr(),
                                                   dother.numel(), _stream(dev)), 'sr_fill_scaled_f32')
+        if dx is not None:
+            dx = dx.to(ctx.dtypes[0])
+        if dother is not None:
+            dother = dother.to(ctx.dtypes[1])
         return dx, dother, None, None
 
 
 def mean(x):
-    """torch.mean(x.detach()) as one HIP reduction (logging of out_d_real / out_d_fake, esrgan_model.py:77-78)."""
+    """torch.mean(x.detach()) as one HIP reduction (logging of out_d_real / out_d_fake, esrgan_model.py:77-78); fp32 result for
+    any floating input."""
     lib = _lib.load()
-    x = x.detach().contiguous()
+    x = x.detach().contiguous().float()
     dev = x.device
     out = torch.empty((), dtype=torch.float32, device=dev)
     wsb = lib.sr_reduce_workspace_bytes(8)

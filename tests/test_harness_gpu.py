@@ -106,10 +106,14 @@ def test_device_ssim_matches_host(cuda):
     g = torch.Generator().manual_seed(11)
     gt = torch.rand(2, 3, 48, 64, generator=g)
     sr = (gt + 0.08 * torch.randn(2, 3, 48, 64, generator=g)).clamp(-0.1, 1.1)
-    got = ssim_device(sr.to(cuda), gt.to(cuda), crop_border=4)
-    for i in range(2):
-        a, b = tensor2img(sr[i:i + 1], rgb2bgr=True, min_max=(0, 1)), tensor2img(gt[i:i + 1], rgb2bgr=True, min_max=(0, 1))
-        assert abs(got[i] - calculate_ssim(a, b, 4)) < 2e-5, (got[i], calculate_ssim(a, b, 4))
+    # bright, low-texture content one grey level apart: the fp32 window moments must not cancel
+    gt_b = (240 + torch.randn(2, 3, 48, 64, generator=g)).round().clamp(0, 255)
+    sr_b = (gt_b + torch.randint(0, 2, gt_b.shape, generator=g) * 2 - 1).clamp(0, 255) / 255
+    for s, t in ((sr, gt), (sr_b, gt_b / 255)):
+        got = ssim_device(s.to(cuda), t.to(cuda), crop_border=4)
+        for i in range(2):
+            a, b = tensor2img(s[i:i + 1], rgb2bgr=True, min_max=(0, 1)), tensor2img(t[i:i + 1], rgb2bgr=True, min_max=(0, 1))
+            assert abs(got[i] - calculate_ssim(a, b, 4)) <= 1e-6, (got[i], calculate_ssim(a, b, 4))
     assert abs(ssim_device(gt.to(cuda), gt.to(cuda))[0] - 1.0) < 1e-6
 
 
