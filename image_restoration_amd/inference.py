@@ -6,7 +6,7 @@ network, clamp to [0,1], RGB->BGR HWC, *255 round (tensor2img, img_util.py:38-94
 sr_model.py:148).  Large frames go through the tiler (tiling.py).
 
     python -m image_restoration_amd.inference --input crop.png --output out.png --model_path net_g.pth \
-        [--num_block 23 --num_feat 64 --tile 512 --tile_pad 16 --compute_dtype fp32|bf16]
+        [--num_block 23 --num_feat 64 --tile 512 --tile_pad 16 --compute_dtype fp32|bf16 --niqe_params niqe_pris_params.npz]
     python -m torch.distributed.run --nproc-per-node 8 -m image_restoration_amd.inference --launcher pytorch --tile 512 ...
 """
 import argparse
@@ -19,6 +19,7 @@ import torch
 from .archs import build_network
 from . import watchdog
 from .tiling import tiled_forward
+from .metrics.niqe import load_niqe_params, niqe_device
 from .utils.img_util import img2tensor, tensor2img
 
 
@@ -49,13 +50,19 @@ def load_generator(args, device):
 def restore(net, img_bgr_u8, tile=0, tile_pad=16, scale=4, rank=0, world_size=1):
     """uint8 BGR image -> uint8 BGR x`scale` image.  With world_size > 1 (one process per GPU, every rank calls this with the
     same image) the tiles are sharded over the ranks and the result is assembled on rank 0 (None elsewhere)."""
+    y = restore_tensor(net, img_bgr_u8, tile, tile_pad, scale, rank, world_size)
+    return None if y is None else tensor2img(y, rgb2bgr=True, min_max=(0, 1))
+
+
+def restore_tensor(net, img_bgr_u8, tile=0, tile_pad=16, scale=4, rank=0, world_size=1):
+    """restore() before tensor2img: the [1, 3, H, W] RGB float output on the device (None off rank 0)."""
     x = img2tensor(img_bgr_u8.astype(np.float32) / 255., bgr2rgb=True, float32=True).unsqueeze(0).to(next(net.parameters()).device)
     with torch.no_grad():
         if tile and (max(x.shape[2:]) > tile or world_size > 1):
             y = tiled_forward(net, x, tile, tile_pad, scale, rank=rank, world_size=world_size)
         else:
             y = watchdog.guarded(lambda: net(x), 'restore') if rank == 0 else None   # tiled_forward guards itself
-    return None if y is None else tensor2img(y, rgb2bgr=True, min_max=(0, 1))
+    return y
 
 
 def main(argv=None):
@@ -75,6 +82,9 @@ def main(argv=None):
     ap.add_argument('--dist_backend', default='nccl', help='process-group backend of --launcher pytorch (nccl = RCCL)')
     ap.add_argument('--compute_dtype', choices=('fp32', 'bf16'), default='fp32',
                     help='fp32 = the reference arithmetic; bf16 = reduced-precision kernels (about 6x faster)')
+    ap.add_argument('--niqe_params', default=None, metavar='PATH',
+                    help="print the NIQE of each restored image (no reference needed; computed on the device); PATH is BasicSR's "
+                         'niqe_pris_params.npz, the pristine model')
     args = ap.parse_args(argv)
     rank, world = 0, 1
     if args.launcher == 'pytorch':
@@ -83,15 +93,20 @@ def main(argv=None):
         rank, world = get_dist_info()
         if not args.tile:
             ap.error('--launcher pytorch shards tiles: give --tile')
+    if args.niqe_params:
+        load_niqe_params(args.niqe_params)  # a missing pristine model fails before any image is restored
     net = load_generator(args, torch.device('cuda'))
     paths = sorted(glob.glob(os.path.join(args.input, '*'))) if os.path.isdir(args.input) else [args.input]
     for p in paths:
-        out = restore(net, imread_bgr(p), args.tile, args.tile_pad, args.scale, rank, world)
-        if out is None:
+        y = restore_tensor(net, imread_bgr(p), args.tile, args.tile_pad, args.scale, rank, world)
+        if y is None:
             continue
+        out = tensor2img(y, rgb2bgr=True, min_max=(0, 1))
         dst = os.path.join(args.output, os.path.basename(p)) if os.path.isdir(args.input) else args.output
         imwrite_bgr(dst, out)
         print(f'{p} -> {dst} {out.shape}')
+        if args.niqe_params:
+            print(f'{dst} NIQE {niqe_device(y, 0, args.niqe_params)[0]:.4f}')
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

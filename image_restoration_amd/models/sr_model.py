@@ -147,17 +147,20 @@ class SRModel(BaseModel):
         the loader and logged; metric options come from opt['val']['metrics'] ({name: {type: calculate_psnr |
         calculate_ssim, crop_border, test_y_channel}}).  PSNR / SSIM without test_y_channel are reduced on the device
         from the fp32 output with tensor2img's quantisation (metrics/psnr.py: no device->host image copy); other
-        metric options take the reference's host route through tensor2img."""
+        metric options take the reference's host route through tensor2img.  The no-reference NIQE (calculate_niqe) is scored
+        from the device output with or without GT (metrics/niqe.py: niqe_device); every metric is averaged over the images
+        it scored."""
         import os.path as osp
-        from ..metrics import psnr_device, ssim_device
+        from ..metrics import niqe_device, psnr_device, ssim_device
         from ..utils.img_util import tensor2img
         from ..utils.registry import METRIC_REGISTRY
         dataset_name = dataloader.dataset.opt['name'] if hasattr(dataloader.dataset, 'opt') else 'val'
         val_opt = self.opt.get('val') or {}
         metrics = val_opt.get('metrics')
+        no_ref = {m for m, o in (metrics or {}).items() if o.get('type') == 'calculate_niqe'}
         if metrics is not None:
             self.metric_results = {m: 0 for m in metrics.keys()}
-        idx, scored = -1, 0
+        idx, scored = -1, {m: 0 for m in (metrics or {})}
         for idx, val_data in enumerate(dataloader):
             self.feed_data(val_data)
             self.test()
@@ -172,10 +175,21 @@ class SRModel(BaseModel):
                 os.makedirs(osp.dirname(path), exist_ok=True)
                 Image.fromarray(np.ascontiguousarray(tensor2img([out[0:1].cpu()], rgb2bgr=False))).save(path)
             if metrics is not None and gt is None and idx == 0:
-                self.logger.warning(f'{dataset_name} has no ground truth: images only, no metrics.')
+                if not no_ref:
+                    self.logger.warning(f'{dataset_name} has no ground truth: images only, no metrics.')
+                elif len(no_ref) < len(metrics):
+                    self.logger.warning(f'{dataset_name} has no ground truth: no-reference metrics only '
+                                        f'({", ".join(sorted(no_ref))}).')
+            for mname in sorted(no_ref):
+                mopt = metrics[mname]
+                self.metric_results[mname] += niqe_device(out[0:1], mopt.get('crop_border', 0), mopt.get('pris_params'),
+                                                          mopt.get('convert_to', 'y'))[0]
+                scored[mname] += 1
             if metrics is not None and gt is not None:
-                scored += 1
                 for mname, mopt in metrics.items():
+                    if mname in no_ref:
+                        continue
+                    scored[mname] += 1
                     mopt = dict(mopt)
                     mtype = mopt.pop('type')
                     crop = mopt.get('crop_border', 0)
@@ -188,9 +202,8 @@ class SRModel(BaseModel):
             if hasattr(self, 'gt'):
                 del self.gt
             del self.lq, self.output
-        if metrics is not None and scored > 0:
-            for m in self.metric_results:
-                self.metric_results[m] /= scored
+        if metrics is not None and any(scored.values()):
+            self.metric_results = {m: v / scored[m] for m, v in self.metric_results.items() if scored[m] > 0}
             log = f'Validation {dataset_name}\n' + ''.join(f'\t # {m}: {v:.4f}\n' for m, v in self.metric_results.items())
             self.logger.info(log)
             if tb_logger:

@@ -146,3 +146,16 @@ def smooth_pairs(seed, n, size, scale=4):
     low = torch.rand(n, 3, size // 8 + 2, size // 8 + 2, generator=g)
     gt = F.interpolate(low, scale_factor=8, mode='bicubic', align_corners=False)[:, :, 8:8 + size, 8:8 + size].clamp(0, 1)
     return F.avg_pool2d(gt, scale), gt.contiguous()
+
+
+def niqe_image(seed, h, w, c=3):
+    """Seeded uint8 HWC image with some spatial structure for the NIQE fixtures: box-smoothed noise plus a gradient plus fine
+    noise (float64 elementwise arithmetic only, so the bytes are the same on every machine)."""
+    rng = np.random.default_rng(seed)
+    x = rng.random((h, w, c))
+    for _ in range(3):
+        x = (x + np.roll(x, 1, 0) + np.roll(x, -1, 0) + np.roll(x, 1, 1) + np.roll(x, -1, 1)) / 5
+    x = (x - x.min()) / (x.max() - x.min())
+    g = np.linspace(0, 1, w)[None, :, None] * np.linspace(0.3, 1, h)[:, None, None]
+    x = 0.6 * x + 0.3 * g + 0.1 * rng.random((h, w, c))
+    return np.clip(np.round(x * 255), 0, 255).astype(np.uint8)

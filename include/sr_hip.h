@@ -315,6 +315,23 @@ int sr_psnr_sse_f32(const float* a, const float* b, int n, int c, int h, int w, 
 int sr_ssim_sum_f32(const float* a, const float* b, int n, int c, int h, int w, int crop_border, float* sum, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* NIQE, the no-reference metric (basicsr/metrics/niqe.py:65-189), as two stages on the device; the host
+ * (image_restoration_amd/metrics/niqe.py) fits the moments and scores them against the pristine model.
+ * sr_niqe_luma_f32: NCHW float img in [0,1] (c = 3: RGB, c = 1: grey) -> y[n][yh][yw], the reference's float32 Y
+ *   (to_y_channel of the tensor2img-quantised BGR image, metric_util.py:35-47) of the region at (crop_border, crop_border);
+ *   yh, yw positive multiples of 96 (niqe.py:96-100 cuts the image to whole blocks).
+ * sr_niqe_moments_f32: per 96x96 block of y (scale 1) or 48x48 block of its 2x downscale (scale 2: the 2x2 cell mean, the
+ *   exact 2x cv2.resize of niqe.py:127-129), blocks in the reference's order (block column outer, block row inner):
+ *   moments[n][block][field][5] (fp64) = n_neg, sum b^2|b<0, n_pos, sum b^2|b>0, sum |b| of the MSCN (field 0) and of its
+ *   products with the block rolled by (0,1) (1,0) (1,1) (1,-1) (fields 1-4, niqe.py:38-62).  The MSCN (niqe.py:109-112:
+ *   7x7 convolutions with the edge replicated, float64 taps rounded to float32) is the reference's float32 value bit for bit;
+ *   mscn_out (nullable) receives it as [n][yh/scale][yw/scale].  host_window: the 7x7 fp64 gaussian_window of the pristine
+ *   model.  Scale 2 needs ws >= sr_niqe_workspace_bytes(n, yh, yw) bytes (scale 1 needs none). */
+size_t sr_niqe_workspace_bytes(int n, int yh, int yw);
+int sr_niqe_luma_f32(const float* img, int n, int c, int h, int w, int crop_border, float* y, int yh, int yw, void* stream);
+int sr_niqe_moments_f32(const float* y, int n, int yh, int yw, int scale, const double* host_window, double* moments,
+                        float* mscn_out, void* ws, size_t ws_bytes, void* stream);
+
 /* VGG feature extractor of PerceptualLoss (vgg_arch.py:55-162, losses.py:249-356): nn.MaxPool2d(2, 2) on CB8 (floor
  * mode; backward routes a window's gradient to its first maximum in scan order, like torch), the input normalisation
  * y[n][c] = x[n][c] * a[c] + b[c] on NCHW (b NULL = its backward), and a stand-alone LeakyReLU / ReLU (slope 0) for
