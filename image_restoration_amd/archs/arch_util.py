@@ -60,3 +60,17 @@ def make_layer(basic_block, num_basic_block, **kwarg):
     """nn.Sequential of `num_basic_block` blocks (reference arch_util.py:43-56) — gives the
     ``body.{i}.`` state_dict prefix."""
     return nn.Sequential(*[basic_block(**kwarg) for _ in range(num_basic_block)])
+
+
+class ResidualBlockNoBN(nn.Module):
+    """Parameters of ``x + res_scale * conv2(relu(conv1(x)))`` (reference arch_util.py:59-87): conv1 / conv2 are
+    num_feat -> num_feat 3x3 convs with bias, initialised kaiming_normal * 0.1, bias 0 (``pytorch_init=False``) or like
+    nn.Conv2d.  No forward: the owning network (MSRResNet) issues the two convs through libsr_hip.so."""
+
+    def __init__(self, num_feat=64, res_scale=1, pytorch_init=False):
+        super().__init__()
+        self.res_scale = res_scale
+        self.conv1 = Conv3x3Params(num_feat, num_feat)
+        self.conv2 = Conv3x3Params(num_feat, num_feat)
+        if not pytorch_init:
+            default_init_weights([self.conv1, self.conv2], 0.1)

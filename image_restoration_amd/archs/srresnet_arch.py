@@ -1,0 +1,146 @@
+"""MSRResNet (modified SRResNet, x2 / x3 / x4) on the MI355X HIP path.
+
+Same constructor, forward contract, state_dict keys and initialisation as the reference
+``basicsr/archs/srresnet_arch.py:9-68``, so ``network_g: {type: MSRResNet, ...}`` option blocks and BasicSR
+checkpoints drop in.  The modules only hold parameters; the network is a composition of per-layer launches:
+
+    conv_first          sr_conv3x3_f32, LeakyReLU(0.1) in the epilogue
+    body.{i}            conv1: sr_conv3x3_f32 with ReLU (act_slope 0); conv2: the residual x + res_scale*conv in the epilogue
+    upconv1[, upconv2]  sr_conv3x3_f32 with LeakyReLU(0.1), then sr_cb8_pixel_shuffle_f32 (the activation commutes with it)
+    conv_hr             sr_conv3x3_f32, LeakyReLU(0.1)
+    conv_last           sr_conv3x3_f32 storing NCHW, then sr_bilinear_up_f32 adds the bilinear base into that output
+
+Training goes through one autograd function for the whole network (srresnet_autograd.py).
+"""
+import torch
+from torch import nn
+
+from .. import _lib, hip_ops
+from ..utils.registry import ARCH_REGISTRY
+from .arch_util import Conv3x3Params, ResidualBlockNoBN, default_init_weights, make_layer
+
+LRELU = 0.1
+
+
+@ARCH_REGISTRY.register()
+class MSRResNet(nn.Module):
+    """MSRResNet(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4).
+
+    forward(x [N, num_in_ch, H, W] fp32 on a HIP device) -> [N, num_out_ch, upscale*H, upscale*W].
+    ``upscale`` must be 2, 3 or 4 (ValueError otherwise; the reference silently builds a net without upsampling).
+    ``num_feat`` must be a positive multiple of 8: every activation lives in whole 8-channel CB8 blocks, so no pad
+    channel ever sits between two layers.  num_in_ch == num_out_ch (the bilinear base is added to the output).
+    """
+
+    def __init__(self, num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4):
+        super().__init__()
+        if upscale not in (2, 3, 4):
+            raise ValueError(f'MSRResNet supports upscale 2, 3 and 4, got {upscale!r}')
+        if not isinstance(num_feat, int) or num_feat <= 0 or num_feat % 8:
+            raise ValueError(f'MSRResNet needs num_feat to be a positive multiple of 8 (CB8 activations), got {num_feat!r}')
+        if num_block < 0:
+            raise ValueError(f'num_block must be >= 0, got {num_block!r}')
+        self.upscale = upscale
+        self.num_in_ch, self.num_out_ch, self.num_feat, self.num_block = num_in_ch, num_out_ch, num_feat, num_block
+
+        self.conv_first = Conv3x3Params(num_in_ch, num_feat)
+        self.body = make_layer(ResidualBlockNoBN, num_block, num_feat=num_feat)
+        if upscale in (2, 3):
+            self.upconv1 = Conv3x3Params(num_feat, num_feat * upscale * upscale)
+        else:
+            self.upconv1 = Conv3x3Params(num_feat, num_feat * 4)
+            self.upconv2 = Conv3x3Params(num_feat, num_feat * 4)
+        self.conv_hr = Conv3x3Params(num_feat, num_feat)
+        self.conv_last = Conv3x3Params(num_feat, num_out_ch)
+
+        default_init_weights([self.conv_first, self.upconv1, self.conv_hr, self.conv_last], 0.1)
+        if upscale == 4:
+            default_init_weights(self.upconv2, 0.1)
+        self._packs = {}
+        self._pack_gen = 0
+        self._grad_sink = None  # set by optim.FlatAdam: weight gradients are added straight into its arena
+
+    # ------------------------------------------------------------------ HIP plumbing
+    def ups(self):
+        """(conv, r) of the upsampling stages, in forward order."""
+        return [(self.upconv1, 2), (self.upconv2, 2)] if self.upscale == 4 else [(self.upconv1, self.upscale)]
+
+    def convs(self):
+        """Every conv in state_dict order."""
+        out = [self.conv_first]
+        for blk in self.body:
+            out += [blk.conv1, blk.conv2]
+        return out + [c for c, _ in self.ups()] + [self.conv_hr, self.conv_last]
+
+    def _param_list(self):
+        """Parameters in state_dict order (weight, bias per conv)."""
+        return [t for c in self.convs() for t in (c.weight, c.bias)]
+
+    def invalidate_packed(self):
+        """Call after parameter memory was written behind torch's version counters (fused Adam, EMA, a broadcast)."""
+        self._pack_gen += 1
+
+    def packed(self, conv, mode=0):
+        """Weight image of ``conv`` (mode 0: forward, 1: data gradient), rebuilt when the parameter storage, its version,
+        the FlatAdam epoch of the parameter or this net's generation (invalidate_packed) changed."""
+        w, b = conv.weight, conv.bias
+        sig = (w.data_ptr(), w._version, getattr(w, '_sr_epoch', (0,))[0], b.data_ptr(), b._version, self._pack_gen)
+        key = (id(conv), mode)
+        hit = self._packs.get(key)
+        if hit is not None and hit[0] == sig:
+            return hit[1]
+        if w.dtype != torch.float32 or b.dtype != torch.float32:
+            raise _lib.SrHipError('MSRResNet parameters must be fp32')
+        pc = hip_ops.PackedConv(w, b if mode == 0 else None, mode=mode)
+        self._packs[key] = (sig, pc)
+        return pc
+
+    def _apply(self, fn, *args, **kwargs):
+        self._packs = {}
+        return super()._apply(fn, *args, **kwargs)
+
+    def run_forward(self, x, keep=False):
+        """The forward as per-layer launches on the current stream.  ``keep``: also return what the backward reads
+        (CB8 activations: input, conv_first output, per block the ReLU output and the block output, per upsampling stage
+        the shuffled output, conv_hr output)."""
+        n, _, h, w = x.shape
+        s, nf = self.upscale, self.num_feat
+        with torch.cuda.device(x.device):
+            xc = hip_ops.nchw_to_cb8(x)
+            feat = hip_ops.conv3x3(xc, self.packed(self.conv_first), act_slope=LRELU)
+            saved = dict(x=xc, feat0=feat, blocks=[], ups=[]) if keep else None
+            for blk in self.body:
+                t = hip_ops.conv3x3(feat, self.packed(blk.conv1), act_slope=0.0)
+                feat = hip_ops.conv3x3(t, self.packed(blk.conv2), alpha=float(blk.res_scale), res1=feat, beta1=1.0)
+                if keep:
+                    saved['blocks'].append((t, feat))
+            for conv, r in self.ups():
+                u = hip_ops.conv3x3(feat, self.packed(conv), act_slope=LRELU)
+                feat = hip_ops.pixel_shuffle(u, nf, r)
+                del u
+                if keep:
+                    saved['ups'].append(feat)
+            hr = hip_ops.conv3x3(feat, self.packed(self.conv_hr), act_slope=LRELU)
+            if keep:
+                saved['hr'] = hr
+            if self.num_out_ch <= 4:
+                y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=x.device)
+                hip_ops.conv3x3(hr, self.packed(self.conv_last), out_nchw=y)
+            else:
+                y = hip_ops.cb8_to_nchw(hip_ops.conv3x3(hr, self.packed(self.conv_last)), self.num_out_ch)
+            hip_ops.bilinear_up(x, s, out=y)   # out += F.interpolate(x, scale_factor=s, mode='bilinear')
+        return y, saved
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise _lib.SrHipError('MSRResNet.forward runs only on a HIP device (no CPU fallback): move the module '
+                                  'and input with .to("cuda")')
+        if x.dim() != 4 or x.size(1) != self.num_in_ch:
+            raise ValueError(f'expected [N, {self.num_in_ch}, H, W], got {tuple(x.shape)}')
+        if self.num_in_ch != self.num_out_ch:
+            raise ValueError('MSRResNet adds the bilinear upsampled input to its output: num_in_ch must equal num_out_ch')
+        x = x.contiguous().float()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list())):
+            from .srresnet_autograd import msrresnet_apply
+            return msrresnet_apply(self, x)
+        return self.run_forward(x)[0]

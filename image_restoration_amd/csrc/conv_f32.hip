@@ -1004,5 +1004,10 @@ extern "C" const char* sr_kernel_name(int id) {
   if (id == 43) return "conv_bf16_kernelILi2ELi1ELi4ELb0E";
   if (id == 15) return "conv_f32_kernelILi1ELi1ELi3ELb0E";
   if (id == 41) return "conv_f32_kernelILi2ELi1ELi3ELb0E";
+  if (id >= 70 && id < 74) {  // upsample_ops.hip
+    static const char* unames[4] = {"cb8_pixel_shuffle_kernel", "cb8_pixel_unshuffle_kernel", "bilinear_up_nchw_kernel",
+                                    "bilinear_up_nchw_bwd_kernel"};
+    return unames[id - 70];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -218,9 +218,10 @@ def conv3x3_chain(steps, sync=None, call_index=0):
     return outs, sync
 
 
-def conv3x3_wgrad(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=False, scale=1.0, want_bias=True):
+def conv3x3_wgrad(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=False, scale=1.0, want_bias=True, out=None):
     """(dweight [cout,cin,3,3], dbias [cout]) of a 3x3 conv whose source was ``src`` (CB8) and whose
-    pre-activation output gradient is ``dy`` (CB8) — one sr_conv3x3_wgrad_f32 call."""
+    pre-activation output gradient is ``dy`` (CB8) — one sr_conv3x3_wgrad_f32 call.  ``out`` = (dweight, dbias or None):
+    device pointers (ints) the gradients are ADDED into (accumulate = 1, e.g. a FlatAdam gradient arena) instead."""
     lib = _lib.load()
     first_seg = cin if first_seg is None else first_seg
     cin_pad = lib.sr_conv3x3_cin_pad(cin, first_seg, seg)
@@ -228,19 +229,27 @@ def conv3x3_wgrad(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=False, 
     H, W = (2 * src.h, 2 * src.w) if upsample else (src.h, src.w)
     assert (dy.n, dy.h, dy.w) == (src.n, H, W) and dy.channels >= (cout + 7) // 8 * 8
     dev = src.device
+    if out is not None:
+        return _wgrad_launch(lib, src, dy, cout, cin, first_seg, seg, cin_pad, upsample, scale, H, W, out[0], out[1], 1)
     dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=dev)
     db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_bias else None
+    _wgrad_launch(lib, src, dy, cout, cin, first_seg, seg, cin_pad, upsample, scale, H, W, dw.data_ptr(),
+                  db.data_ptr() if db is not None else None, 0)
+    return dw, db
+
+
+def _wgrad_launch(lib, src, dy, cout, cin, first_seg, seg, cin_pad, upsample, scale, H, W, dw_ptr, db_ptr, accumulate):
+    dev = src.device
     nbytes = lib.sr_conv3x3_wgrad_slab_bytes(src.n, H, W)
     slab = scratch(dev, nbytes, 'slab')
     d = _lib.WgradDesc()
     d.x, d.x_img_stride, d.cin_pad, d.in_h, d.in_w, d.upsample = src.ptr, src.img_stride, cin_pad, src.h, src.w, int(upsample)
     d.dy, d.dy_img_stride = dy.ptr, dy.img_stride
     d.cout, d.cin, d.first_seg, d.seg, d.n, d.scale = cout, cin, first_seg, seg, src.n, scale
-    d.dweight, d.dbias, d.accumulate = dw.data_ptr(), (db.data_ptr() if db is not None else None), 0
+    d.dweight, d.dbias, d.accumulate = dw_ptr, db_ptr, accumulate
     d.slab, d.slab_bytes = slab.data_ptr(), nbytes
     with torch.cuda.device(dev):
         _lib.check(lib.sr_conv3x3_wgrad_f32(C.byref(d), _stream(dev)), 'sr_conv3x3_wgrad_f32')
-    return dw, db
 
 
 def upsample2x_bwd(g, mask=None, mask_slope=0.2):
@@ -264,6 +273,66 @@ def cb8_axpby(dst, src, a=1.0, b=1.0):
         _lib.check(lib.sr_cb8_axpby_f32(dst.ptr, dst.img_stride, src.ptr, src.img_stride, a, b, dst.n, dst.cbn, dst.h,
                                         dst.w, _stream(dst.device)), 'sr_cb8_axpby_f32')
     return dst
+
+
+def pixel_shuffle(src, channels, r):
+    """nn.PixelShuffle(r) on CB8 (r in {2, 3}): ``src`` holds r*r*channels real channels -> CB8 of ``channels`` at r x the
+    size — sr_cb8_pixel_shuffle_f32."""
+    lib = _lib.load()
+    assert src.channels >= channels * r * r
+    out = CB8.empty(src.n, channels, src.h * r, src.w * r, src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(lib.sr_cb8_pixel_shuffle_f32(src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, src.h, src.w, r,
+                                                _stream(src.device)), 'sr_cb8_pixel_shuffle_f32')
+    return out
+
+
+def pixel_unshuffle(src, channels, r):
+    """nn.PixelUnshuffle(r) on CB8, the shuffle's backward: ``channels`` real channels of ``src`` -> CB8 of r*r*channels at
+    1/r of the size — sr_cb8_pixel_unshuffle_f32."""
+    lib = _lib.load()
+    assert src.channels >= channels and src.h % r == 0 and src.w % r == 0
+    out = CB8.empty(src.n, channels * r * r, src.h // r, src.w // r, src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(lib.sr_cb8_pixel_unshuffle_f32(src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, out.h, out.w, r,
+                                                  _stream(src.device)), 'sr_cb8_pixel_unshuffle_f32')
+    return out
+
+
+def bilinear_up(x, s, out=None):
+    """F.interpolate(x, scale_factor=s, mode='bilinear', align_corners=False) on NCHW fp32, s in {2, 3, 4} —
+    sr_bilinear_up_f32.  ``out``: an NCHW tensor [N, C, s*H, s*W] the result is ADDED into (returned)."""
+    _need_cuda(x, 'bilinear_up')
+    lib = _lib.load()
+    x = x.contiguous().float()
+    n, c, h, w = x.shape
+    acc = out is not None
+    if out is None:
+        out = torch.empty((n, c, h * s, w * s), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (n, c, h * s, w * s)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.sr_bilinear_up_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, s, int(acc), _stream(x.device)),
+                   'sr_bilinear_up_f32')
+    return out
+
+
+def bilinear_up_bwd(g, s, out=None):
+    """Adjoint of bilinear_up (gather form, bit-reproducible): g [N, C, s*H, s*W] -> [N, C, H, W] — sr_bilinear_up_bwd_f32.
+    ``out``: an NCHW tensor the result is ADDED into (returned)."""
+    _need_cuda(g, 'bilinear_up_bwd')
+    lib = _lib.load()
+    g = g.contiguous().float()
+    n, c, hh, ww = g.shape
+    assert hh % s == 0 and ww % s == 0
+    h, w = hh // s, ww // s
+    acc = out is not None
+    if out is None:
+        out = torch.empty((n, c, h, w), dtype=torch.float32, device=g.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (n, c, h, w)
+    with torch.cuda.device(g.device):
+        _lib.check(lib.sr_bilinear_up_bwd_f32(g.data_ptr(), out.data_ptr(), n, c, h, w, s, int(acc), _stream(g.device)),
+                   'sr_bilinear_up_bwd_f32')
+    return out
 
 
 class PackedConv4x4s2:

@@ -1,4 +1,4 @@
-"""Single-image / folder super-resolution with an RRDBNet checkpoint on the HIP path.
+"""Single-image / folder super-resolution with an RRDBNet or MSRResNet checkpoint on the HIP path.
 
 The reference's inference.py serves a different model (GFPGANv1OCR, inference.py:28-40); what this script keeps is
 its I/O convention: read BGR uint8, /255, BGR->RGB CHW float (img2tensor, img_util.py:9-35),
@@ -7,6 +7,7 @@ sr_model.py:148).  Large frames go through the tiler (tiling.py).
 
     python -m image_restoration_amd.inference --input crop.png --output out.png --model_path net_g.pth \
         [--num_block 23 --num_feat 64 --tile 512 --tile_pad 16 --compute_dtype fp32|bf16 --niqe_params niqe_pris_params.npz]
+    python -m image_restoration_amd.inference --arch MSRResNet --scale 3 --input crop.png --output out.png --model_path net_g.pth
     python -m torch.distributed.run --nproc-per-node 8 -m image_restoration_amd.inference --launcher pytorch --tile 512 ...
 """
 import argparse
@@ -35,12 +36,28 @@ def imwrite_bgr(path, img):
     Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(path)
 
 
+ARCH_DEFAULT_BLOCKS = {'RRDBNet': 23, 'MSRResNet': 16}
+
+
+def generator_options(args):
+    """network_g option block of the command line.  RRDBNet: scale 1/2/4, fp32 or bf16; MSRResNet: upscale 2/3/4, fp32 only."""
+    arch = getattr(args, 'arch', 'RRDBNet')
+    num_block = getattr(args, 'num_block', None)
+    num_block = ARCH_DEFAULT_BLOCKS[arch] if num_block is None else num_block
+    if arch == 'MSRResNet':
+        if args.scale not in (2, 3, 4):
+            raise ValueError(f'--arch MSRResNet takes --scale 2, 3 or 4, not {args.scale}')
+        if getattr(args, 'compute_dtype', 'fp32') != 'fp32':
+            raise ValueError('--arch MSRResNet runs in fp32 only (no --compute_dtype bf16)')
+        return dict(type='MSRResNet', num_in_ch=3, num_out_ch=3, num_feat=args.num_feat, num_block=num_block, upscale=args.scale)
+    return dict(type='RRDBNet', num_in_ch=3, num_out_ch=3, scale=args.scale, num_feat=args.num_feat, num_block=num_block,
+                num_grow_ch=args.num_grow_ch, compute_dtype=getattr(args, 'compute_dtype', 'fp32'))
+
+
 def load_generator(args, device):
     if not args.model_path:
         torch.manual_seed(0)  # no checkpoint: every rank of a sharded run must still hold the same (random) weights
-    net = build_network(dict(type='RRDBNet', num_in_ch=3, num_out_ch=3, scale=args.scale, num_feat=args.num_feat,
-                             num_block=args.num_block, num_grow_ch=args.num_grow_ch,
-                             compute_dtype=getattr(args, 'compute_dtype', 'fp32')))
+    net = build_network(generator_options(args))
     if args.model_path:
         from .utils.checkpoint import load_generator_weights
         load_generator_weights(net, args.model_path, strict=True)  # BasicSR files and official ESRGAN key names
@@ -72,7 +89,9 @@ def main(argv=None):
     ap.add_argument('--model_path', default=None)
     ap.add_argument('--scale', type=int, default=4)
     ap.add_argument('--num_feat', type=int, default=64)
-    ap.add_argument('--num_block', type=int, default=23)
+    ap.add_argument('--arch', choices=('RRDBNet', 'MSRResNet'), default='RRDBNet',
+                    help='generator: RRDBNet (ESRGAN; --scale 1/2/4) or MSRResNet (--scale 2/3/4, fp32)')
+    ap.add_argument('--num_block', type=int, default=None, help='default: 23 for RRDBNet, 16 for MSRResNet')
     ap.add_argument('--num_grow_ch', type=int, default=32)
     ap.add_argument('--tile', type=int, default=0)
     ap.add_argument('--tile_pad', type=int, default=16)
@@ -86,6 +105,10 @@ def main(argv=None):
                     help="print the NIQE of each restored image (no reference needed; computed on the device); PATH is BasicSR's "
                          'niqe_pris_params.npz, the pristine model')
     args = ap.parse_args(argv)
+    try:
+        generator_options(args)
+    except ValueError as e:
+        ap.error(str(e))
     rank, world = 0, 1
     if args.launcher == 'pytorch':
         from .utils.dist_util import get_dist_info, init_dist

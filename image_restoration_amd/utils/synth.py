@@ -57,6 +57,41 @@ def rrdbnet_state_dict(seed=0, **cfg):
     return sd
 
 
+def msrresnet_param_shapes(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4):
+    """(name, shape) in state_dict order of MSRResNet (srresnet_arch.py:30-44)."""
+    out = []
+
+    def conv(name, ci, co):
+        out.append((f'{name}.weight', (co, ci, 3, 3)))
+        out.append((f'{name}.bias', (co,)))
+
+    conv('conv_first', num_in_ch, num_feat)
+    for b in range(num_block):
+        conv(f'body.{b}.conv1', num_feat, num_feat)
+        conv(f'body.{b}.conv2', num_feat, num_feat)
+    if upscale == 4:
+        conv('upconv1', num_feat, num_feat * 4)
+        conv('upconv2', num_feat, num_feat * 4)
+    else:
+        conv('upconv1', num_feat, num_feat * upscale * upscale)
+    conv('conv_hr', num_feat, num_feat)
+    conv('conv_last', num_feat, num_out_ch)
+    return out
+
+
+def msrresnet_state_dict(seed=0, **cfg):
+    """OrderedDict name -> np.float32 array for MSRResNet(**cfg): residual-block convs ~ kaiming_normal * 0.1 (the
+    reference's init), the others ~ U(+-1/sqrt(fan_in)) so that the head and tail carry signal; small non-zero biases."""
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    shapes = msrresnet_param_shapes(**cfg)
+    for i in range(0, len(shapes), 2):
+        (wn, ws), (bn, _) = shapes[i], shapes[i + 1]
+        w, b = conv_params(rng, ws, rdb_style=wn.startswith('body.'))
+        sd[wn], sd[bn] = w, b
+    return sd
+
+
 def rdb_state_dict(seed, num_feat=64, num_grow_ch=32, prefix=''):
     rng = np.random.default_rng(seed)
     sd = OrderedDict()

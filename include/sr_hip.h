@@ -636,6 +636,25 @@ int sr_unet_backward_bf16(const sr_unet_cfg* cfg, const void* packed, const void
 int sr_set_backward_wgrad_deferred(int on);
 int sr_backward_lane_join(void* stream);
 
+/* ------------------------------------------------ MSRResNet upsampling ---- */
+/* nn.PixelShuffle(r) of the MSRResNet tail (srresnet_arch.py:37-44,62-65), r in {2, 3}, CB8 -> CB8:
+ *   dst[n][c][r*h + i][r*w + j] = src[n][c*r*r + i*r + j][h][w]   (torch's channel order, as in sr_cb8_to_nchw_f32's shuffle)
+ * src has ceil(r*r*c/8) channel blocks at h x w, dst ceil(c/8) blocks at r*h x r*w; pad channels of dst are written 0.
+ * A pure permutation: the LeakyReLU that follows the shuffle in the reference runs in the upconv's epilogue (it is elementwise).
+ * Launch-profiler kernel id 70. */
+int sr_cb8_pixel_shuffle_f32(const float* src, int64_t src_img_stride, float* dst, int64_t dst_img_stride, int n, int c, int h,
+                             int w, int r, void* stream);
+/* Its inverse (nn.PixelUnshuffle(r)), the shuffle's backward: src ceil(c/8) blocks at r*h x r*w -> dst ceil(r*r*c/8) blocks at
+ * h x w; pad channels of dst are written 0.  Kernel id 71. */
+int sr_cb8_pixel_unshuffle_f32(const float* src, int64_t src_img_stride, float* dst, int64_t dst_img_stride, int n, int c, int h,
+                               int w, int r, void* stream);
+/* F.interpolate(x, scale_factor=s, mode='bilinear', align_corners=False), s in {2, 3, 4}, NCHW fp32 (srresnet_arch.py:66):
+ * x [n][c][h][w] -> y [n][c][s*h][s*w]; accumulate = 1 adds into y (the `out += base` of :67).  Any h, w >= 1.  Kernel id 72.
+ * sr_bilinear_up_bwd_f32 is its adjoint g [n][c][s*h][s*w] -> dx [n][c][h][w] in gather form: each dx element sums the output
+ * window that reaches it in a fixed order, without atomics (bit-reproducible); accumulate = 1 adds into dx.  Kernel id 73. */
+int sr_bilinear_up_f32(const float* x, float* y, int n, int c, int h, int w, int s, int accumulate, void* stream);
+int sr_bilinear_up_bwd_f32(const float* g, float* dx, int n, int c, int h, int w, int s, int accumulate, void* stream);
+
 /* ------------------------------------------------------------ measurement ---- */
 
 /* Opt-in per-launch timing used by bench.py's roofline line: between sr_profile_start and
