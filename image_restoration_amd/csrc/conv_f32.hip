@@ -1009,5 +1009,10 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "bilinear_up_nchw_bwd_kernel"};
     return unames[id - 70];
   }
+  if (id >= 74 && id < 81) {  // channel_attention.hip
+    static const char* cnames[7] = {"ca_partial_kernelILb0E", "ca_squeeze_finish_kernel", "ca_excite_kernel", "ca_partial_kernelILb1E",
+                                    "ca_bwd_finish_kernel", "ca_wgrad_kernel", "ca_bwd_apply_kernel"};
+    return cnames[id - 74];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

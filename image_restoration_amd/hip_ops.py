@@ -335,6 +335,72 @@ def bilinear_up_bwd(g, s, out=None):
     return out
 
 
+def _ca_workspace(lib, dev, n, nf, hid, h, w):
+    nbytes = lib.sr_ca_workspace_bytes(n, nf, hid, h, w)
+    return scratch(dev, nbytes, 'ca'), nbytes
+
+
+def ca_squeeze(u, w1, b1, w2, b2):
+    """RCAN channel attention, the squeeze: p = mean_hw u, h = relu(W1 p + b1), s = sigmoid(W2 h + b2) for the CB8 tensor ``u``
+    (all its channels).  W1 [hid, nf, 1, 1], W2 [nf, hid, 1, 1] as stored.  Returns (p [N, nf], h [N, hid], s [N, nf]) —
+    sr_ca_squeeze_f32."""
+    lib = _lib.load()
+    n, nf, hid = u.n, u.channels, w1.shape[0]
+    assert tuple(w1.shape[:2]) == (hid, nf) and tuple(w2.shape[:2]) == (nf, hid)
+    dev = u.device
+    p = torch.empty((n, nf), dtype=torch.float32, device=dev)
+    hb = torch.empty((n, hid), dtype=torch.float32, device=dev)
+    s = torch.empty((n, nf), dtype=torch.float32, device=dev)
+    ws, nbytes = _ca_workspace(lib, dev, n, nf, hid, u.h, u.w)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_ca_squeeze_f32(u.ptr, u.img_stride, n, nf, u.h, u.w, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                                         b2.data_ptr(), hid, p.data_ptr(), hb.data_ptr(), s.data_ptr(), ws.data_ptr(), nbytes,
+                                         _stream(dev)), 'sr_ca_squeeze_f32')
+    return p, hb, s
+
+
+def ca_excite(x, u, s, res_scale=1.0, out=None):
+    """out = x + res_scale * (u * s[n][c]) on CB8 (out allocated if None; may be x) — sr_ca_excite_f32."""
+    lib = _lib.load()
+    if out is None:
+        out = CB8.empty(u.n, u.channels, u.h, u.w, u.device)
+    assert x.channels == u.channels == out.channels and s.is_contiguous()
+    with torch.cuda.device(u.device):
+        _lib.check(lib.sr_ca_excite_f32(x.ptr, x.img_stride, u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n,
+                                        u.channels, u.h, u.w, float(res_scale), _stream(u.device)), 'sr_ca_excite_f32')
+    return out
+
+
+def ca_bwd(g, u, res_scale, w1, w2, p, hb, s, grads=None, accumulate=False):
+    """Adjoint of the squeeze given g = dL/d(excite output): returns q [N, nf] = dL/dp / (H*W), the pooled part of dL/du.
+    ``grads`` = (dW1, db1, dW2, db2) device pointers (ints or None) the weight gradients are written (or, accumulate, added)
+    into — sr_ca_bwd_f32."""
+    lib = _lib.load()
+    n, nf, hid = u.n, u.channels, w1.shape[0]
+    assert g.channels == nf and (g.n, g.h, g.w) == (n, u.h, u.w)
+    dev = u.device
+    q = torch.empty((n, nf), dtype=torch.float32, device=dev)
+    ws, nbytes = _ca_workspace(lib, dev, n, nf, hid, u.h, u.w)
+    d = tuple(grads) if grads is not None else (None, None, None, None)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_ca_bwd_f32(g.ptr, g.img_stride, u.ptr, u.img_stride, n, nf, u.h, u.w, float(res_scale), w1.data_ptr(),
+                                     w2.data_ptr(), hid, p.data_ptr(), hb.data_ptr(), s.data_ptr(), d[0], d[1], d[2], d[3],
+                                     int(accumulate), q.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)), 'sr_ca_bwd_f32')
+    return q
+
+
+def ca_bwd_apply(g, s, q, res_scale=1.0, out=None):
+    """du = (res_scale * g) * s[n][c] + q[n][c] on CB8 (out allocated if None; may be g) — sr_ca_bwd_apply_f32."""
+    lib = _lib.load()
+    if out is None:
+        out = CB8.empty(g.n, g.channels, g.h, g.w, g.device)
+    assert out.channels == g.channels
+    with torch.cuda.device(g.device):
+        _lib.check(lib.sr_ca_bwd_apply_f32(g.ptr, g.img_stride, s.data_ptr(), q.data_ptr(), out.ptr, out.img_stride, g.n, g.channels,
+                                           g.h, g.w, float(res_scale), _stream(g.device)), 'sr_ca_bwd_apply_f32')
+    return out
+
+
 class PackedConv4x4s2:
     """Parity-pass weight images of a 4x4 / stride 2 / pad 1 conv (sr_conv4x4s2_pack_f32); mode 1 = data gradient."""
 

@@ -115,6 +115,11 @@ def uniform_input(seed, shape):
     return np.random.default_rng(seed).random(shape, dtype=np.float32)
 
 
+def gaussian(seed, shape):
+    """N(0, 1) draws in float64 rounded to fp32: upstream gradients of the golden backward runs."""
+    return np.random.default_rng(seed).standard_normal(shape).astype(np.float32)
+
+
 def signed_input(seed, shape, scale=1.0):
     """Zero-mean features for block-level tests."""
     return ((np.random.default_rng(seed).random(shape, dtype=np.float32) * 2 - 1) * np.float32(scale)).astype(np.float32)
@@ -194,3 +199,44 @@ def niqe_image(seed, h, w, c=3):
     g = np.linspace(0, 1, w)[None, :, None] * np.linspace(0.3, 1, h)[:, None, None]
     x = 0.6 * x + 0.3 * g + 0.1 * rng.random((h, w, c))
     return np.clip(np.round(x * 255), 0, 255).astype(np.uint8)
+
+
+def rcan_param_shapes(num_in_ch=3, num_out_ch=3, num_feat=64, num_group=10, num_block=16, squeeze_factor=16, upscale=4, **_):
+    """(name, shape) in state_dict order of RCAN (rcan_arch.py:27-135; Upsample of arch_util.py)."""
+    out = []
+    hid = num_feat // squeeze_factor
+
+    def conv(name, ci, co, k=3):
+        out.append((f'{name}.weight', (co, ci, k, k)))
+        out.append((f'{name}.bias', (co,)))
+
+    conv('conv_first', num_in_ch, num_feat)
+    for g in range(num_group):
+        for b in range(num_block):
+            pre = f'body.{g}.residual_group.{b}.rcab'
+            conv(f'{pre}.0', num_feat, num_feat)
+            conv(f'{pre}.2', num_feat, num_feat)
+            conv(f'{pre}.3.attention.1', num_feat, hid, 1)
+            conv(f'{pre}.3.attention.3', hid, num_feat, 1)
+        conv(f'body.{g}.conv', num_feat, num_feat)
+    conv('conv_after_body', num_feat, num_feat)
+    stages = [3] if upscale == 3 else [2] * (int(upscale).bit_length() - 1)
+    for i, r in enumerate(stages):
+        conv(f'upsample.{2 * i}', num_feat, r * r * num_feat)
+    conv('conv_last', num_feat, num_out_ch)
+    return out
+
+
+def rcan_state_dict(seed=0, **cfg):
+    """OrderedDict name -> np.float32 array for RCAN(**cfg): the 3x3 convs inside the body ~ kaiming_normal * 0.1 (so that
+    the residual chain stays of the input's size over many blocks), the others and the attention's 1x1 convs
+    ~ U(+-1/sqrt(fan_in)); small non-zero biases, larger (+-0.5) on the attention so its ReLU and sigmoid see both signs."""
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    shapes = rcan_param_shapes(**cfg)
+    for i in range(0, len(shapes), 2):
+        (wn, ws), (bn, _) = shapes[i], shapes[i + 1]
+        ca = '.attention.' in wn
+        w, b = conv_params(rng, ws, rdb_style=wn.startswith('body.') and not ca, bias_scale=0.5 if ca else 0.05)
+        sd[wn], sd[bn] = w, b
+    return sd

@@ -655,6 +655,33 @@ int sr_cb8_pixel_unshuffle_f32(const float* src, int64_t src_img_stride, float* 
 int sr_bilinear_up_f32(const float* x, float* y, int n, int c, int h, int w, int s, int accumulate, void* stream);
 int sr_bilinear_up_bwd_f32(const float* g, float* dx, int n, int c, int h, int w, int s, int accumulate, void* stream);
 
+/* -------------------------------------------------- RCAN channel attention ---- */
+/* ChannelAttention of RCAN's residual channel-attention block (rcan_arch.py:8-46), fp32, CB8 tensors of nf channels
+ * (nf a multiple of 8, at most 512; channel slices through the image strides), hid = nf / squeeze_factor in [1, nf], any h, w >= 1:
+ *   p[n][c] = mean_hw u[n][c][.][.],  h[n] = relu(W1 p[n] + b1),  s[n] = sigmoid(W2 h[n] + b2),  out = x + res_scale * (u * s)
+ * W1 / W2 are the 1x1 conv weights as stored ([hid][nf][1][1] / [nf][hid][1][1]); p, h, s are [n][nf] / [n][hid] / [n][nf].
+ * The reductions over the image run as per-(image, channel block, band) partials in the caller's workspace
+ * (sr_ca_workspace_bytes, SR_ENOSPACE when smaller) and a fixed-order finish: no atomics, so every launch is bit-reproducible.
+ *   sr_ca_squeeze_f32    p, h and s (which the backward reads).  Kernel ids 74 (partials), 75 (finish + MLP).
+ *   sr_ca_excite_f32     out = x + res_scale * (u * s), one streaming pass; out may be x.  Kernel id 76.
+ *   sr_ca_bwd_f32        given g = dL/dout: ds = res_scale * sum_hw g*u, the sigmoid / W2 / ReLU / W1 adjoints, and
+ *                        q[n][c] = dp[n][c] / (h*w); dW1, db1, dW2, db2 summed over the batch in order (NULL: skipped;
+ *                        accumulate = 1 adds into them).  Kernel ids 77 (partials), 78 (per-image adjoint), 79 (weight gradients).
+ *   sr_ca_bwd_apply_f32  du = (res_scale * g) * s + q: the gradient at u, the input of the attention; du may be g.  Kernel id 80.
+ * dL/dx of the excite is g itself (the identity path); callers add it where the block's input gradient is formed. */
+size_t sr_ca_workspace_bytes(int n, int nf, int hid, int h, int w);
+int sr_ca_squeeze_f32(const float* u, int64_t u_img_stride, int n, int nf, int h, int w, const float* w1, const float* b1,
+                      const float* w2, const float* b2, int hid, float* p, float* hbuf, float* s, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int sr_ca_excite_f32(const float* x, int64_t x_img_stride, const float* u, int64_t u_img_stride, const float* s, float* out,
+                     int64_t out_img_stride, int n, int nf, int h, int w, float res_scale, void* stream);
+int sr_ca_bwd_f32(const float* g, int64_t g_img_stride, const float* u, int64_t u_img_stride, int n, int nf, int h, int w,
+                  float res_scale, const float* w1, const float* w2, int hid, const float* p, const float* hbuf, const float* s,
+                  float* dw1, float* db1, float* dw2, float* db2, int accumulate, float* q, void* workspace, size_t workspace_bytes,
+                  void* stream);
+int sr_ca_bwd_apply_f32(const float* g, int64_t g_img_stride, const float* s, const float* q, float* du, int64_t du_img_stride,
+                        int n, int nf, int h, int w, float res_scale, void* stream);
+
 /* ------------------------------------------------------------ measurement ---- */
 
 /* Opt-in per-launch timing used by bench.py's roofline line: between sr_profile_start and
