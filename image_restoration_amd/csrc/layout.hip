@@ -219,6 +219,9 @@ extern "C" int sr_upsample2x_bwd_f32(const float* g, int64_t g_img_stride, float
                                      int h, int w, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SR_CHECK_ARG(g && dst && n > 0 && cblocks > 0 && h > 0 && w > 0, "sr_upsample2x_bwd_f32: bad argument");
+  SR_CHECK_ARG((uintptr_t)g % 16 == 0 && (uintptr_t)dst % 16 == 0 && (uintptr_t)mask % 16 == 0 && g_img_stride % 4 == 0 &&
+                   dst_img_stride % 4 == 0 && (!mask || mask_img_stride % 4 == 0),
+               "sr_upsample2x_bwd_f32: g, dst and mask must be 16-byte aligned");
   const long long total = (long long)n * cblocks * h * w * 2;
   hipLaunchKernelGGL(up2x_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, g,
                      (long long)g_img_stride, dst, (long long)dst_img_stride, mask, (long long)mask_img_stride,
@@ -231,6 +234,8 @@ extern "C" int sr_cb8_axpby_f32(float* dst, int64_t dst_img_stride, const float*
                                 float b, int n, int cblocks, int h, int w, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SR_CHECK_ARG(dst && src && n > 0 && cblocks > 0 && h > 0 && w > 0, "sr_cb8_axpby_f32: bad argument");
+  SR_CHECK_ARG((uintptr_t)dst % 16 == 0 && (uintptr_t)src % 16 == 0 && dst_img_stride % 4 == 0 && src_img_stride % 4 == 0,
+               "sr_cb8_axpby_f32: dst and src must be 16-byte aligned");
   const long long per_img4 = (long long)cblocks * h * w * 2;
   const long long total = per_img4 * n;
   hipLaunchKernelGGL(cb8_axpby_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, dst,

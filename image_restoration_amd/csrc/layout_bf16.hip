@@ -164,6 +164,7 @@ extern "C" int sr_nchw_to_cb16_bf16(const float* src, void* dst, int N, int C, i
   SR_CHECK_ARG(src && dst && N > 0 && C > 0 && H > 0 && W > 0, "sr_nchw_to_cb16_bf16: bad argument");
   SR_CHECK_ARG(unshuffle == 1 || unshuffle == 2 || unshuffle == 4, "sr_nchw_to_cb16_bf16: unshuffle must be 1, 2 or 4");
   SR_CHECK_ARG(dst_cblocks * 16 >= C * unshuffle * unshuffle, "sr_nchw_to_cb16_bf16: dst_cblocks too small");
+  SR_CHECK_ARG((uintptr_t)dst % 16 == 0 && dst_img_stride % 8 == 0, "sr_nchw_to_cb16_bf16: dst must be 16-byte aligned");
   const long long total = (long long)N * dst_cblocks * H * W * 2;
   hipLaunchKernelGGL(nchw_to_cb16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, (__bf16*)dst, C, H,
                      W, unshuffle, dst_cblocks, (long long)dst_img_stride, total);
@@ -254,6 +255,9 @@ extern "C" int sr_upsample2x_bwd_bf16(const void* g, int64_t g_img_stride, void*
                                       void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SR_CHECK_ARG(g && dst && n > 0 && cblocks > 0 && h > 0 && w > 0, "sr_upsample2x_bwd_bf16: bad argument");
+  SR_CHECK_ARG((uintptr_t)g % 16 == 0 && (uintptr_t)dst % 16 == 0 && (uintptr_t)mask % 16 == 0 && g_img_stride % 8 == 0 &&
+                   dst_img_stride % 8 == 0 && (!mask || mask_img_stride % 8 == 0),
+               "sr_upsample2x_bwd_bf16: g, dst and mask must be 16-byte aligned");
   const long long total = (long long)n * cblocks * h * w * 2;
   hipLaunchKernelGGL(up2x_bwd16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const __bf16*)g,
                      (long long)g_img_stride, (__bf16*)dst, (long long)dst_img_stride, (const __bf16*)mask,
@@ -266,6 +270,8 @@ extern "C" int sr_cb16_axpby_bf16(void* dst, int64_t dst_img_stride, const void*
                                   int n, int cblocks, int h, int w, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SR_CHECK_ARG(dst && src && n > 0 && cblocks > 0 && h > 0 && w > 0, "sr_cb16_axpby_bf16: bad argument");
+  SR_CHECK_ARG((uintptr_t)dst % 16 == 0 && (uintptr_t)src % 16 == 0 && dst_img_stride % 8 == 0 && src_img_stride % 8 == 0,
+               "sr_cb16_axpby_bf16: dst and src must be 16-byte aligned");
   const long long per_img8 = (long long)cblocks * h * w * 2;
   const long long total = per_img8 * n;
   hipLaunchKernelGGL(cb16_axpby_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (__bf16*)dst,

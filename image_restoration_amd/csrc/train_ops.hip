@@ -660,7 +660,9 @@ inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
 
 // ===================================================================== C ABI
 extern "C" size_t sr_reduce_workspace_bytes(int channels) {
-  const size_t cb = (size_t)(channels + 7) / 8;
+  // partials of the CB8 reductions [cb8][RED_SPLITS][8][2] and of their CB16 twins (disc_bf16.hip) [cb16][RED_SPLITS][16][2]:
+  // the channel count is rounded up to whole 16-channel blocks so the larger of the two always fits
+  const size_t cb = (size_t)(channels + 15) / 16 * 2;
   return (cb * RED_SPLITS * 16 + 4 * RED_SPLITS + 64) * sizeof(float);
 }
 

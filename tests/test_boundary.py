@@ -123,6 +123,42 @@ def test_argument_errors_are_codes_with_messages_not_crashes():
     assert failed(lib.sr_gan_point_loss_fwd_f32(256, 16, 9, 0.0, 1.0, 256, 256, 1 << 20, None), 'bad argument')
 
 
+def test_misaligned_vector_accesses_are_refused_before_any_launch():
+    """The layout helpers move 16 bytes per access (float4 / 8 x bf16): a destination, source, mask or image stride that is
+    not 16-byte aligned is an argument error of every one of them, reported before anything is launched."""
+    lib = _lib.load()
+
+    def refused(rc, name):
+        msg = lib.sr_last_error().decode()
+        return rc < 0 and name in msg and 'aligned' in msg
+    A, M = 4096, 4096 + 8    # aligned / 8-byte-misaligned placeholders: never dereferenced
+    assert refused(lib.sr_nchw_to_cb8_f32(A, M, 1, 3, 4, 4, 1, 1, 128, None), 'sr_nchw_to_cb8_f32')
+    assert refused(lib.sr_nchw_to_cb8_f32(A, A, 1, 3, 4, 4, 1, 1, 130, None), 'sr_nchw_to_cb8_f32')
+    assert refused(lib.sr_nchw_to_cb16_bf16(A, M, 1, 3, 4, 4, 1, 1, 256, None), 'sr_nchw_to_cb16_bf16')
+    assert refused(lib.sr_nchw_to_cb16_bf16(A, A, 1, 3, 4, 4, 1, 1, 260, None), 'sr_nchw_to_cb16_bf16')
+    for fn, name, q in ((lib.sr_upsample2x_bwd_f32, 'sr_upsample2x_bwd_f32', 4), (lib.sr_upsample2x_bwd_bf16, 'sr_upsample2x_bwd_bf16', 8)):
+        assert refused(fn(M, 512, A, 128, None, 0, 0.2, 1, 1, 4, 4, None), name)
+        assert refused(fn(A, 512, M, 128, None, 0, 0.2, 1, 1, 4, 4, None), name)
+        assert refused(fn(A, 512, A, 128, M, 128, 0.2, 1, 1, 4, 4, None), name)
+        assert refused(fn(A, 512 + q // 2, A, 128, None, 0, 0.2, 1, 1, 4, 4, None), name)
+        assert refused(fn(A, 512, A, 128 + q // 2, None, 0, 0.2, 1, 1, 4, 4, None), name)
+        assert refused(fn(A, 512, A, 128, A, 128 + q // 2, 0.2, 1, 1, 4, 4, None), name)
+    for fn, name, q in ((lib.sr_cb8_axpby_f32, 'sr_cb8_axpby_f32', 4), (lib.sr_cb16_axpby_bf16, 'sr_cb16_axpby_bf16', 8)):
+        assert refused(fn(M, 128, A, 128, 1.0, 1.0, 1, 1, 4, 4, None), name)
+        assert refused(fn(A, 128, M, 128, 1.0, 1.0, 1, 1, 4, 4, None), name)
+        assert refused(fn(A, 128 + q // 2, A, 128, 1.0, 1.0, 1, 1, 4, 4, None), name)
+        assert refused(fn(A, 128, A, 128 + q // 2, 1.0, 1.0, 1, 1, 4, 4, None), name)
+
+
+def test_reduce_workspace_holds_the_partials_of_both_layouts():
+    """sr_reduce_workspace_bytes(c) covers the partial sums of the CB8 reductions ([ceil(c/8)][64][8][2] floats, train_ops.hip)
+    and of their CB16 twins ([ceil(c/16)][64][16][2], disc_bf16.hip) for every channel count."""
+    lib = _lib.load()
+    for c in range(1, 1025):
+        need = max(-(-c // 8) * 64 * 8 * 2, -(-c // 16) * 64 * 16 * 2) * 4
+        assert lib.sr_reduce_workspace_bytes(c) >= need, c
+
+
 def test_whole_discriminator_driver_plans_without_a_gpu():
     """sr_vgg_*: the host-only helpers (plan, sizes) and the argument checks of the drivers — no launch happens."""
     lib = _lib.load()

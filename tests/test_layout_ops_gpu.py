@@ -1,0 +1,795 @@
+"""The layout, resampling and bf16 helper kernels against float64 (and, where the kernel's arithmetic is a short fixed sequence,
+against a bit-exact float32 emulation of that sequence): sr_nchw_to_cb8_f32 / sr_cb8_to_nchw_f32 / sr_upsample2x_bwd_f32 /
+sr_cb8_axpby_f32 (layout.hip), their CB16 twins (layout_bf16.hip), the bf16 helpers of the discriminators (disc_bf16.hip) and the
+eval mode (train = 0) of sr_bn_lrelu_{fwd,bwd}_{f32,bf16}.
+
+Comparison policy.
+  - Pure data movement (the NCHW <-> CB conversions with their fused pixel (un)shuffle, sr_cb16_unshuffle2_bf16 both ways, the bf16
+    max-pool forward) is compared bit for bit as int32 / int16 views, so signed zeros count.  The fp32 -> bf16 conversion of
+    sr_nchw_to_cb16_bf16 is pinned bit for bit to torch's round-to-nearest-even (ties to even, overflow to inf, subnormals kept).
+  - Single-rounding arithmetic is compared bit for bit against a torch float32 emulation that keeps the kernel's order (the library
+    builds with -ffp-contract=off and without fast-math, so float32 `((a + b) + c) + d` on the host is what the kernel computes), and
+    against float64 within a bound.  EPS = 2^-24 (fp32 unit roundoff), EPS16 = 2^-8 (bf16: 8 significand bits).  With S the sum
+    of the absolute values of the terms and r the float64 result:
+      up2x_bwd        ((a + b) + c) + d, then * slope where mask <= 0:  |y - r| <= 3 EPS S |f| (+ EPS |r| for the slope product),
+                      f the mask factor; bf16 adds one rounding of the fp32 result, EPS16 |r|.
+      axpby           a d + b s: two products and a sum, |y - r| <= EPS S + EPS |r| (fp32); bf16: 2 EPS S + EPS16 |r|.
+      add16, lrelu    one rounding to bf16: EPS16 |r| (+ 2^-134, half the smallest bf16 subnormal, where the result can be
+                      subnormal).
+      fork_bwd        bf16(g_u + g_skip), then bf16(. * slope) where mask <= 0: two bf16 roundings, 2.01 EPS16 |r|.
+  - Reductions and interpolation are compared with float64 within bounds derived from the kernel's own summation order:
+      bilinear x2 fwd  each output is wy0 (wx0 a00 + wx1 a01) + wy1 (wx0 a10 + wx1 a11); the weights are 0, 1/4, 3/4 or 1, so the
+                       products of bf16 values are exact and three fp32 sums / products round: 4 EPS S, plus EPS16 |r| for the bf16
+                       store.  S = the same interpolation of |t|.  With src2 the interpolated tensor is bf16(src + src2), emulated.
+      bilinear x2 bwd  a sequential sum of 16 exact products (weights are sums of quarters): 16 EPS S + EPS16 |r|, S = the adjoint
+                       applied to |g|; the masked form multiplies by the slope first (+1 EPS).
+      BN eval fwd      (x - mean) invstd gamma + beta with invstd = rsqrtf(var + eps) (one rounding of the sum, <= 2 ulp of rsqrtf):
+                       8 EPS (|xhat gamma| + |beta|) + EPS_out |r|.
+      BN eval bwd      dx = gamma invstd dz: 7 EPS |dx|; dgamma, dbeta: sums of M = n h w terms in a fixed order, (M + 6) EPS S.
+  The bf16 max-pool uses fmaxf, which does not propagate NaN as torch does; NaN inputs are outside what is pinned here.  A ±0 tie
+  of the forward yields +0 (IEEE maximum orders -0 < +0); the backward's tie rule is torch's: the first maximum in scan order.
+
+Every destination is allocated with slack (padding between images, channel blocks around a window, a tail) filled with a NaN
+sentinel bit pattern before the call, and every slack element must come back bit-identical; sources carry the same sentinel in
+their slack, so a kernel reading outside its window poisons the result.  All slack lies inside the allocations.
+
+Negative controls: every check is also run once on a copy of the result with one planted error (one bit flipped for the bit-exact
+checks, an error of 1.05 bounds for the float64 checks, one slack element overwritten for the sentinel checks) and must fail.
+"""
+import ctypes as C
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from image_restoration_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+EPS = 2.0 ** -24
+EPS16 = 2.0 ** -8
+TINY = 1e-300
+ETA16 = 2.0 ** -134         # half the smallest bf16 subnormal: the absolute floor of one bf16 rounding
+S32 = 0x7FC0DEAD            # fp32 sentinel: a quiet NaN with a payload
+S16 = 0x7FDE                # bf16 sentinel: a quiet NaN with a payload
+
+
+@pytest.fixture(scope='module')
+def lib():
+    return _lib.load()
+
+
+def _st():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _ok(rc, what):
+    _lib.check(rc, what)
+    torch.cuda.synchronize()
+
+
+def _ibits(t):
+    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+# ------------------------------------------------------------------------------------------------------------- buffers
+class Buf:
+    """A sentinel-filled device allocation holding n images of `blocks` channel blocks [h][w][blk] at a per-image stride of
+    blocks * h * w * blk + pad elements, plus a tail.  `win(cb0, cbn)` is the view of channel blocks cb0 .. cb0 + cbn."""
+
+    def __init__(self, n, blocks, h, w, dtype, pad=0, tail=64, cuda='cuda:0'):
+        self.blk = 8 if dtype == torch.float32 else 16
+        self.n, self.blocks, self.h, self.w, self.dtype = n, blocks, h, w, dtype
+        self.stride = blocks * h * w * self.blk + pad
+        size = n * self.stride + tail
+        if dtype == torch.float32:
+            self.flat = torch.full((size,), S32, dtype=torch.int32, device=cuda).view(torch.float32)
+        else:
+            self.flat = torch.full((size,), S16, dtype=torch.int16, device=cuda).view(torch.bfloat16)
+        self.written = torch.zeros(size, dtype=torch.bool)
+
+    def win(self, cb0=0, cbn=None):
+        cbn = self.blocks - cb0 if cbn is None else cbn
+        plane = self.h * self.w * self.blk
+        return self.flat[:self.n * self.stride].view(self.n, self.stride)[:, cb0 * plane:(cb0 + cbn) * plane].view(
+            self.n, cbn, self.h, self.w, self.blk)
+
+    def ptr(self, cb0=0):
+        return self.flat.data_ptr() + cb0 * self.h * self.w * self.blk * self.flat.element_size()
+
+    def mark(self, cb0=0, cbn=None):
+        """Declares channel blocks cb0 .. cb0 + cbn of every image as the kernel's output window."""
+        cbn = self.blocks - cb0 if cbn is None else cbn
+        plane = self.h * self.w * self.blk
+        self.written[:self.n * self.stride].view(self.n, self.stride)[:, cb0 * plane:(cb0 + cbn) * plane] = True
+
+    def put(self, vals, cb0=0):
+        self.win(cb0, vals.shape[1]).copy_(vals.to(self.dtype))
+
+
+def _untouched(buf, what):
+    bits = _ibits(buf.flat).cpu()
+    keep = ~buf.written
+    sentinel = S32 if buf.dtype == torch.float32 else S16
+    bad = keep & (bits != sentinel)
+    assert not bool(bad.any()), (what, 'slack changed', int(bad.sum()), int(bad.nonzero()[0]))
+
+
+def _neg_untouched(buf, what):
+    idx = int((~buf.written).nonzero()[-1])
+    saved = buf.flat[idx:idx + 1].clone()
+    buf.flat[idx] = 1.0
+    with pytest.raises(AssertionError):
+        _untouched(buf, what)
+    buf.flat[idx:idx + 1].copy_(saved)
+
+
+def _same_bits(got, exp, what):
+    g, e = _ibits(got.cpu().contiguous()), _ibits(exp.cpu().contiguous().to(got.dtype))
+    bad = g != e
+    assert not bool(bad.any()), (what, int(bad.sum()), 'of', g.numel())
+
+
+def _neg_same_bits(got, exp, what):
+    g = got.cpu().contiguous().clone()
+    _ibits(g).view(-1)[-1] ^= 1
+    with pytest.raises(AssertionError):
+        _same_bits(g, exp, what)
+
+
+def _within(got, ref, bound, what):
+    got = got.cpu().double()
+    err = (got - ref).abs()
+    bad = ~(err <= bound)      # NaN fails
+    assert not bool(bad.any()), (what, int(bad.sum()), float((err / bound).nan_to_num(1e9).max()))
+
+
+def _neg_within(got, ref, bound, what):
+    g = got.cpu().double().contiguous().clone()
+    ref, bound = ref.contiguous(), bound.contiguous()
+    i = int(bound.view(-1).argmax())
+    r = ref.view(-1)[i]
+    planted = r + 1.05 * bound.view(-1)[i]
+    g.view(-1)[i] = planted if bool(planted != r) else torch.nextafter(r, torch.tensor(float('inf'), dtype=torch.float64))
+    with pytest.raises(AssertionError):
+        _within(g, ref, bound, what)
+
+
+def _pinned(got, exp, ref, bound, what):
+    """Bit-exact against the emulation, within the bound of float64, each with its negative control."""
+    _same_bits(got, exp, what)
+    _within(got, ref, bound, what)
+    _neg_same_bits(got, exp, what)
+    _neg_within(got, ref, bound, what)
+
+
+def _checked_slack(buf, what):
+    _untouched(buf, what)
+    _neg_untouched(buf, what)
+
+
+# ------------------------------------------------------------------------------------------------------- layout helpers
+def _to_cb(x, blk, blocks):
+    """NCHW -> [n][blocks][h][w][blk], channels beyond x's zero."""
+    n, c, h, w = x.shape
+    xp = torch.zeros((n, blocks * blk, h, w), dtype=x.dtype)
+    xp[:, :c] = x
+    return xp.view(n, blocks, blk, h, w).permute(0, 1, 3, 4, 2).contiguous()
+
+
+def _from_cb(t):
+    n, cb, h, w, blk = t.shape
+    return t.permute(0, 1, 4, 2, 3).reshape(n, cb * blk, h, w)
+
+
+def _u2_to_plain(t):
+    """[n][4 cb][h][w][16] (channel (2 ry + rx) cb + c) -> [n][cb][2h][2w][16]."""
+    n, cb4, h, w, b = t.shape
+    cb = cb4 // 4
+    return t.reshape(n, 2, 2, cb, h, w, b).permute(0, 3, 4, 1, 5, 2, 6).reshape(n, cb, 2 * h, 2 * w, b)
+
+
+def _plain_to_u2(t):
+    n, cb, h2, w2, b = t.shape
+    h, w = h2 // 2, w2 // 2
+    return t.reshape(n, cb, h, 2, w, 2, b).permute(0, 3, 5, 1, 2, 4, 6).reshape(n, 4 * cb, h, w, b)
+
+
+def _bf(t):
+    """float values rounded to bf16 (round to nearest even), back as float32."""
+    return t.to(torch.bfloat16).float()
+
+
+def _specials32():
+    """fp32 values where an fp32 -> bf16 conversion goes wrong: exact ties between bf16 neighbours (even and odd lower
+    neighbour, both signs), values just off the tie, values above the largest bf16 (round to it or overflow to inf), fp32
+    subnormals (including ties), ±0, ±inf."""
+    bits = []
+    for b in (0x3F80, 0x3F81, 0x4049, 0x404A, 0x0080, 0x7F7E, 0x7F7F, 0x0001, 0x0002):
+        for sign in (0, 0x8000):
+            hb = (b | sign) << 16
+            bits += [hb | 0x8000, hb | 0x7FFF, hb | 0x8001]
+    bits += [0x7F7FFFFF, 0x7F7F7FFF, 0xFF7F8000, 0x00000001, 0x80000001, 0x00008000, 0x00018000, 0x007FFFFF,
+             0x00000000, 0x80000000, 0x7F800000, 0xFF800000]
+    t = torch.tensor([b - (1 << 32) if b >= 1 << 31 else b for b in bits], dtype=torch.int32)
+    return t.view(torch.float32)
+
+
+# ========================================================================= NCHW -> CB8 / CB16 (pixel unshuffle fused)
+CONV_CASES = [  # n, c, h, w (destination), u, extra dst blocks, dst image padding (elements)
+    (1, 3, 5, 7, 1, 0, 0), (2, 3, 4, 6, 2, 1, 16), (1, 1, 1, 1, 1, 0, 0), (1, 3, 1, 1, 4, 0, 0), (3, 5, 3, 5, 2, 2, 48),
+    (2, 17, 3, 2, 1, 1, 32), (1, 2, 7, 9, 4, 0, 16), (2, 40, 1, 3, 1, 0, 8),
+]
+
+
+@pytest.mark.parametrize('case', CONV_CASES)
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+def test_nchw_to_cb(cuda, lib, case, dt):
+    n, c, h, w, u, extra, pad = case
+    dtype = torch.float32 if dt == 'f32' else torch.bfloat16
+    blk = 8 if dt == 'f32' else 16
+    blocks = -(-c * u * u // blk) + extra
+    torch.manual_seed(c * 31 + h * 7 + w + u)
+    x = torch.randn(n, c, h * u, w * u) * 3
+    flat = x.view(-1)
+    flat[0] = -0.0                          # a signed zero must stay signed
+    if dt == 'bf16':
+        sp = _specials32()
+        k = min(sp.numel(), flat.numel() - 1)
+        flat[1:1 + k] = sp[:k]
+    dst = Buf(n, blocks, h, w, dtype, pad=pad, cuda=cuda)
+    dst.mark()
+    fn = lib.sr_nchw_to_cb8_f32 if dt == 'f32' else lib.sr_nchw_to_cb16_bf16
+    xd = x.to(cuda)                         # device copies stay bound while the kernel runs
+    _ok(fn(xd.data_ptr(), dst.ptr(), n, c, h, w, u, blocks, dst.stride, _st()), 'nchw_to_cb')
+    exp = _to_cb(F.pixel_unshuffle(x, u), blk, blocks).to(dtype)     # torch's own conversion: RNE
+    got = dst.win().cpu()
+    _same_bits(got, exp, 'nchw_to_cb')
+    _neg_same_bits(got, exp, 'nchw_to_cb')
+    pad_ch = _from_cb(got.float())[:, c * u * u:]
+    assert bool((_ibits(pad_ch) == 0).all()), 'padding channels must be exactly +0'
+    _checked_slack(dst, 'nchw_to_cb')
+
+
+def test_nchw_to_cb16_rounding_specials(cuda, lib):
+    """Every special value of _specials32 in one image: the conversion equals torch's round-to-nearest-even bit for bit,
+    and differs from truncation somewhere (so a truncating kernel cannot pass)."""
+    sp = _specials32()
+    m = sp.numel()
+    x = sp.view(1, m, 1, 1)
+    blocks = -(-m // 16)
+    dst = Buf(1, blocks, 1, 1, torch.bfloat16, cuda=cuda)
+    dst.mark()
+    xd = x.to(cuda)
+    _ok(lib.sr_nchw_to_cb16_bf16(xd.data_ptr(), dst.ptr(), 1, m, 1, 1, 1, blocks, dst.stride, _st()), 'nchw_to_cb16')
+    got = _from_cb(dst.win().cpu())[0, :m, 0, 0]
+    exp = sp.to(torch.bfloat16)
+    _same_bits(got, exp, 'cb16 rounding')
+    trunc = (sp.view(torch.int32) >> 16).to(torch.int16)
+    assert bool((trunc != _ibits(exp)).any())
+    _checked_slack(dst, 'cb16 rounding')
+
+
+# ========================================================================= CB8 / CB16 -> NCHW (pixel shuffle fused)
+@pytest.mark.parametrize('case', [(1, 3, 5, 7, 1, 0), (2, 3, 4, 6, 2, 24), (3, 2, 3, 5, 4, 8), (2, 17, 1, 1, 1, 40),
+                                  (1, 5, 1, 9, 2, 16), (2, 1, 7, 1, 4, 0)])
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+def test_cb_to_nchw_is_the_adjoint_and_the_inverse(cuda, lib, case, dt):
+    n, c, h, w, u, pad = case
+    dtype = torch.float32 if dt == 'f32' else torch.bfloat16
+    blk = 8 if dt == 'f32' else 16
+    blocks = -(-c * u * u // blk)
+    torch.manual_seed(c + 13 * u + h)
+    y = _bf(torch.randn(n, blocks, h, w, blk)) if dt == 'bf16' else torch.randn(n, blocks, h, w, blk)
+    src = Buf(n, blocks, h, w, dtype, pad=pad, cuda=cuda)   # NaN sentinel in the padding between images: must not be read
+    src.put(y)
+    out_numel = n * c * h * u * w * u
+    dst = torch.full((out_numel + 64,), S32, dtype=torch.int32, device=cuda).view(torch.float32)
+    fn = lib.sr_cb8_to_nchw_f32 if dt == 'f32' else lib.sr_cb16_to_nchw_f32
+    _ok(fn(src.ptr(), src.stride, dst.data_ptr(), n, c, h, w, u, _st()), 'cb_to_nchw')
+    got = dst[:out_numel].view(n, c, h * u, w * u).cpu()
+    exp = F.pixel_shuffle(_from_cb(y)[:, :c * u * u], u)
+    _same_bits(got, exp, 'cb_to_nchw')
+    _neg_same_bits(got, exp, 'cb_to_nchw')
+    tail = _ibits(dst[out_numel:]).cpu()
+    assert bool((tail == S32).all()), 'cb_to_nchw wrote past its output'
+    # <U x, y> = <x, U^T y> in float64, with U = the unshuffling conversion of this library (x bf16-representable: U exact)
+    x = torch.randn(n, c, h * u, w * u)
+    x = _bf(x) if dt == 'bf16' else x
+    ux = Buf(n, blocks, h, w, dtype, cuda=cuda)
+    fwd = lib.sr_nchw_to_cb8_f32 if dt == 'f32' else lib.sr_nchw_to_cb16_bf16
+    xd = x.to(cuda)
+    _ok(fwd(xd.data_ptr(), ux.ptr(), n, c, h, w, u, blocks, ux.stride, _st()), 'nchw_to_cb')
+    lhs = float((ux.win().cpu().double() * y.double()).sum())
+    rhs = float((x.double() * got.double()).sum())
+    scale = float((ux.win().cpu().double().abs() * y.double().abs()).sum())
+    assert abs(lhs - rhs) <= 1e-12 * scale, ('adjoint', lhs, rhs)
+    # round trip: shuffle(unshuffle(x)) == x bit for bit
+    back = torch.empty(n * c * h * u * w * u, device=cuda)
+    _ok(fn(ux.ptr(), ux.stride, back.data_ptr(), n, c, h, w, u, _st()), 'cb_to_nchw')
+    _same_bits(back.view_as(x).cpu(), x, 'round trip')
+
+
+# ========================================================================= nearest-x2 backward (+ LeakyReLU mask)
+def _mask_values(shape, dtype):
+    """Mask tensor: random signs, with +0, -0, the smallest positive subnormal and negatives planted."""
+    m = torch.randn(shape)
+    tiny = torch.tensor([1], dtype=torch.int32).view(torch.float32) if dtype == torch.float32 else \
+        torch.tensor([1], dtype=torch.int16).view(torch.bfloat16).float()
+    flat = m.view(-1)
+    k = flat.numel()
+    flat[0:k:5] = 0.0
+    flat[1:k:5] = -0.0
+    flat[2:k:7] = tiny
+    flat[3:k:11] = -tiny
+    return m.to(dtype)
+
+
+def _f32(v):
+    """A Python float as the kernel receives it (a float argument)."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def _mask_factor(m, slope):
+    return torch.where(m.double() > 0, torch.ones((), dtype=torch.float64), torch.full((), _f32(slope), dtype=torch.float64))
+
+
+UP_CASES = [  # n, cblocks, h, w (destination), masked, slope, g / dst / mask padding
+    (1, 1, 1, 1, False, 0.2, (0, 0, 0)), (2, 3, 3, 5, True, 0.2, (32, 16, 48)), (2, 2, 4, 3, True, 0.0, (0, 64, 16)),
+    (3, 1, 5, 7, False, 0.2, (16, 0, 0)), (1, 4, 2, 9, True, 0.2, (0, 0, 0)),
+]
+
+
+@pytest.mark.parametrize('case', UP_CASES)
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+def test_upsample2x_bwd(cuda, lib, case, dt):
+    n, cbn, h, w, masked, slope, (pg, pd, pm) = case
+    dtype = torch.float32 if dt == 'f32' else torch.bfloat16
+    blk = 8 if dt == 'f32' else 16
+    torch.manual_seed(n * 100 + cbn * 10 + h + w)
+    g = (torch.randn(n, cbn, 2 * h, 2 * w, blk) * 2).to(dtype)
+    gb = Buf(n, cbn, 2 * h, 2 * w, dtype, pad=pg, cuda=cuda)
+    gb.put(g)
+    dst = Buf(n, cbn, h, w, dtype, pad=pd, cuda=cuda)
+    dst.mark()
+    mask = mb = None
+    if masked:
+        mask = _mask_values((n, cbn, h, w, blk), dtype)
+        mb = Buf(n, cbn, h, w, dtype, pad=pm, cuda=cuda)
+        mb.put(mask)
+    fn = lib.sr_upsample2x_bwd_f32 if dt == 'f32' else lib.sr_upsample2x_bwd_bf16
+    _ok(fn(gb.ptr(), gb.stride, dst.ptr(), dst.stride, mb.ptr() if masked else None, mb.stride if masked else 0, slope, n, cbn,
+           h, w, _st()), 'upsample2x_bwd')
+    gf = g.float()
+    a, b, c, d = gf[:, :, 0::2, 0::2], gf[:, :, 0::2, 1::2], gf[:, :, 1::2, 0::2], gf[:, :, 1::2, 1::2]
+    v = ((a + b) + c) + d                                               # the kernel's order, fp32
+    g64 = g.double()
+    terms = [g64[:, :, i::2, j::2] for i in (0, 1) for j in (0, 1)]
+    ref = sum(terms)
+    S = sum(t.abs() for t in terms)
+    fac = torch.ones_like(ref)
+    if masked:
+        fac = _mask_factor(mask, slope)
+        v = torch.where(mask.float() > 0, v, v * torch.tensor(slope, dtype=torch.float32))
+        ref = ref * fac
+    exp = v.to(dtype)
+    bound = 3 * EPS * S * fac + EPS * ref.abs() + (EPS16 * ref.abs() if dt == 'bf16' else 0) + TINY
+    got = dst.win().cpu()
+    _pinned(got, exp, ref, bound, 'upsample2x_bwd')
+    _checked_slack(dst, 'upsample2x_bwd')
+
+
+# ========================================================================= axpby on a channel-block window
+@pytest.mark.parametrize('ab', [(1.0, 1.0), (0.75, -1.3), (-1.0, 1.0), (1.0, -1.0), (0.0, 2.5)])
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+def test_cb_axpby_window(cuda, lib, ab, dt):
+    a, b = _f32(ab[0]), _f32(ab[1])
+    dtype = torch.float32 if dt == 'f32' else torch.bfloat16
+    n, total_blocks, cb0, cbn, h, w = 3, 5, 2, 2, 3, 5          # the window of a concat buffer (rrdbnet.hip: the trunk slot)
+    torch.manual_seed(int(a * 10 + b * 100) & 0xFFFF)
+    blk = 8 if dt == 'f32' else 16
+    d0 = torch.randn(n, cbn, h, w, blk).to(dtype)
+    s = torch.randn(n, cbn, h, w, blk).to(dtype)
+    d0.view(-1)[0] = -0.0
+    s.view(-1)[0] = 0.0
+    dst = Buf(n, total_blocks, h, w, dtype, pad=16, cuda=cuda)
+    dst.put(d0, cb0)
+    dst.mark(cb0, cbn)
+    src = Buf(n, cbn, h, w, dtype, pad=48, cuda=cuda)
+    src.put(s)
+    fn = lib.sr_cb8_axpby_f32 if dt == 'f32' else lib.sr_cb16_axpby_bf16
+    _ok(fn(dst.ptr(cb0), dst.stride, src.ptr(), src.stride, a, b, n, cbn, h, w, _st()), 'axpby')
+    af, bf = torch.tensor(a, dtype=torch.float32), torch.tensor(b, dtype=torch.float32)
+    exp = (af * d0.float() + bf * s.float()).to(dtype)
+    ref = a * d0.double() + b * s.double()
+    S = (a * d0.double()).abs() + (b * s.double()).abs()
+    bound = (EPS * S + EPS * ref.abs()) if dt == 'f32' else (2 * EPS * S + EPS16 * ref.abs())
+    got = dst.win(cb0, cbn).cpu()
+    _pinned(got, exp, ref, bound + TINY, 'axpby')
+    _checked_slack(dst, 'axpby')
+
+
+# ========================================================================= bf16 element-wise helpers
+def _slope_values(n):
+    """x in bf16 with ±0, values whose product with the slope rounds, large and tiny magnitudes."""
+    x = torch.randn(n) * 4
+    x[0], x[1] = 0.0, -0.0
+    x[2:6] = torch.tensor([-1.0078125, -3.0, -0.1, -255.0])
+    x[6:8] = torch.tensor([1e-38, -1e-38])
+    return x.to(torch.bfloat16)
+
+
+@pytest.mark.parametrize('n', [8, 256 * 8, 256 * 8 + 8])
+@pytest.mark.parametrize('slope', [0.2, 0.0])
+def test_lrelu_fwd_bwd_bf16(cuda, lib, n, slope):
+    torch.manual_seed(n)
+    x = _slope_values(n)
+    gy = (torch.randn(n) * 3).to(torch.bfloat16)
+    gy[0:4] = torch.tensor([1.0, -1.0, 3.0, -5.0])
+    tail = 64
+    xs = x.to(cuda)
+    gys = gy.to(cuda)
+    out = torch.full((n + tail,), S16, dtype=torch.int16, device=cuda).view(torch.bfloat16)
+    _ok(lib.sr_lrelu_fwd_bf16(xs.data_ptr(), out.data_ptr(), slope, n, _st()), 'lrelu_fwd_bf16')
+    got = out[:n].cpu()
+    fac = _mask_factor(x, slope)
+    sl = torch.tensor(slope, dtype=torch.float32)
+    exp = torch.where(x.float() > 0, x.float(), x.float() * sl).to(torch.bfloat16)
+    ref = x.double() * fac
+    _pinned(got, exp, ref, EPS16 * ref.abs() + ETA16, 'lrelu_fwd_bf16')
+    assert bool((_ibits(out[n:]).cpu() == S16).all())
+    # backward from the saved output y: dz = y > 0 ? gy : bf16(gy * slope)
+    y = got
+    yd = y.to(cuda)
+    _ok(lib.sr_lrelu_bwd_bf16(gys.data_ptr(), yd.data_ptr(), out.data_ptr(), slope, n, _st()), 'lrelu_bwd_bf16')
+    got = out[:n].cpu()
+    fac = _mask_factor(y, slope)
+    exp = torch.where(y.float() > 0, gy.float(), gy.float() * sl).to(torch.bfloat16)
+    ref = gy.double() * fac
+    _pinned(got, exp, ref, EPS16 * ref.abs() + ETA16, 'lrelu_bwd_bf16')
+    assert bool((_ibits(out[n:]).cpu() == S16).all())
+
+
+@pytest.mark.parametrize('shape', [(1, 1, 1, 1), (2, 3, 4, 5), (1, 2, 9, 16)])
+def test_lrelu_bwd_diff_u2_bf16(cuda, lib, shape):
+    n, cbn, h, w = shape                          # u2 (small) dims; the plain tensors are 2h x 2w
+    torch.manual_seed(n + cbn + h + w)
+    x0 = (torch.randn(n, cbn, 2 * h, 2 * w, 16) * 2).to(torch.bfloat16)
+    xs = x0.clone()
+    i16 = _ibits(xs).view(-1)
+    k = i16.numel()
+    sel = torch.arange(k) % 4                      # 0: equal, 1: one ulp up, 2: one ulp down, 3: random
+    i16[sel == 1] += 1
+    i16[sel == 2] -= 1
+    xs.view(-1)[sel == 3] = torch.randn(int((sel == 3).sum())).to(torch.bfloat16)
+    xs.view(-1)[0], x0.view(-1)[0] = 0.0, -0.0    # +0 - (-0) is 0: not > 0
+    gy = (torch.randn(n, cbn, 2 * h, 2 * w, 16) * 3).to(torch.bfloat16)
+    slope = 0.2
+    dz = Buf(n, cbn, 2 * h, 2 * w, torch.bfloat16, cuda=cuda)
+    dz.mark()
+    x0u = _plain_to_u2(x0).contiguous()
+    gyd, xsd, x0d = gy.to(cuda), xs.to(cuda), x0u.to(cuda)
+    _ok(lib.sr_lrelu_bwd_diff_u2_bf16(gyd.data_ptr(), xsd.data_ptr(), x0d.data_ptr(), dz.ptr(), slope,
+                                      n, cbn, h, w, _st()), 'lrelu_bwd_diff_u2')
+    pos = xs.double() > x0.double()                # exact sign of the difference
+    assert bool(pos.any()) and bool((~pos).any())
+    exp = torch.where(pos, gy.float(), gy.float() * torch.tensor(slope, dtype=torch.float32)).to(torch.bfloat16)
+    ref = gy.double() * torch.where(pos, 1.0, _f32(slope)).double()
+    _pinned(dz.win().cpu(), exp, ref, EPS16 * ref.abs() + TINY, 'lrelu_bwd_diff_u2')
+    _checked_slack(dz, 'lrelu_bwd_diff_u2')
+
+
+@pytest.mark.parametrize('n', [8, 256 * 8 + 8])
+def test_cb16_add_bf16(cuda, lib, n):
+    torch.manual_seed(n + 1)
+    a = (torch.randn(n) * 3).to(torch.bfloat16)
+    b = (torch.randn(n) * 3).to(torch.bfloat16)
+    b[: n // 2] = (-a[: n // 2].float() * (1 + torch.randn(n // 2) * 1e-2)).to(torch.bfloat16)   # cancellation
+    b[0] = -a[0]
+    out = torch.full((n + 64,), S16, dtype=torch.int16, device=cuda).view(torch.bfloat16)
+    ad, bd = a.to(cuda), b.to(cuda)
+    _ok(lib.sr_cb16_add_bf16(ad.data_ptr(), bd.data_ptr(), out.data_ptr(), n, _st()), 'cb16_add')
+    ref = a.double() + b.double()
+    _pinned(out[:n].cpu(), (a.float() + b.float()).to(torch.bfloat16), ref, EPS16 * ref.abs() + TINY, 'cb16_add')
+    assert bool((_ibits(out[n:]).cpu() == S16).all())
+
+
+@pytest.mark.parametrize('shape', [(1, 1, 1, 1), (2, 2, 3, 5)])
+def test_cb16_add_u2_bf16(cuda, lib, shape):
+    n, cbn, h, w = shape
+    torch.manual_seed(7 + h)
+    a = (torch.randn(n, cbn, 2 * h, 2 * w, 16) * 3).to(torch.bfloat16)
+    bp = (torch.randn(n, cbn, 2 * h, 2 * w, 16) * 3).to(torch.bfloat16)
+    out = Buf(n, cbn, 2 * h, 2 * w, torch.bfloat16, cuda=cuda)
+    out.mark()
+    ad, bd = a.to(cuda), _plain_to_u2(bp).contiguous().to(cuda)
+    _ok(lib.sr_cb16_add_u2_bf16(ad.data_ptr(), bd.data_ptr(), out.ptr(), n, cbn, h, w,
+                                _st()), 'cb16_add_u2')
+    ref = a.double() + bp.double()
+    _pinned(out.win().cpu(), (a.float() + bp.float()).to(torch.bfloat16), ref, EPS16 * ref.abs() + TINY, 'cb16_add_u2')
+    _checked_slack(out, 'cb16_add_u2')
+
+
+@pytest.mark.parametrize('shape', [(1, 1, 1, 1, 0, 0), (2, 2, 3, 5, 32, 16), (1, 3, 4, 1, 0, 48)])
+def test_cb16_unshuffle2_both_ways(cuda, lib, shape):
+    n, cbn, h, w, ps, pd = shape
+    torch.manual_seed(h * w + cbn)
+    x = (torch.randn(n, cbn, 2 * h, 2 * w, 16)).to(torch.bfloat16)
+    x.view(-1)[0] = -0.0
+    src = Buf(n, cbn, 2 * h, 2 * w, torch.bfloat16, pad=ps, cuda=cuda)
+    src.put(x)
+    dst = Buf(n, 4 * cbn, h, w, torch.bfloat16, pad=pd, cuda=cuda)
+    dst.mark()
+    _ok(lib.sr_cb16_unshuffle2_bf16(src.ptr(), src.stride, dst.ptr(), dst.stride, n, cbn, h, w, 0, _st()), 'unshuffle2')
+    exp = _plain_to_u2(x)
+    # the definition: channel (2 ry + rx) C + c of the unshuffled tensor is pixel (2y + ry, 2x + rx) of channel c
+    nchw = _from_cb(x.float())
+    alt = torch.cat([nchw[:, :, ry::2, rx::2] for ry in (0, 1) for rx in (0, 1)], 1)
+    assert torch.equal(_from_cb(exp.float()), alt)
+    got = dst.win().cpu()
+    _same_bits(got, exp, 'unshuffle2')
+    _neg_same_bits(got, exp, 'unshuffle2')
+    _checked_slack(dst, 'unshuffle2')
+    back = Buf(n, cbn, 2 * h, 2 * w, torch.bfloat16, pad=ps + 16, cuda=cuda)
+    back.mark()
+    _ok(lib.sr_cb16_unshuffle2_bf16(dst.ptr(), dst.stride, back.ptr(), back.stride, n, cbn, h, w, 1, _st()), 'unshuffle2 inverse')
+    _same_bits(back.win().cpu(), x, 'unshuffle2 inverse')
+    _neg_same_bits(back.win().cpu(), x, 'unshuffle2 inverse')
+    _checked_slack(back, 'unshuffle2 inverse')
+
+
+# ========================================================================= fork backward (skip + unshuffled gradient + mask)
+@pytest.mark.parametrize('u2,skip,masked', [(False, False, False), (False, True, False), (False, False, True),
+                                             (False, True, True), (True, False, True), (True, True, True)])
+def test_cb16_fork_bwd(cuda, lib, u2, skip, masked):
+    n, cbn, h, w, slope = 2, 2, 3, 5, 0.2
+    torch.manual_seed(int(u2) * 4 + int(skip) * 2 + int(masked))
+    gu = (torch.randn(n, 4 * cbn, h, w, 16) * 2).to(torch.bfloat16)
+    gs = (torch.randn(n, cbn, 2 * h, 2 * w, 16) * 2).to(torch.bfloat16)
+    mplain = _mask_values((n, cbn, 2 * h, 2 * w, 16), torch.bfloat16)
+    mdev = _plain_to_u2(mplain).contiguous() if u2 else mplain
+    dz = Buf(n, cbn, 2 * h, 2 * w, torch.bfloat16, cuda=cuda)
+    dz.mark()
+    fn = lib.sr_cb16_fork_bwd_u2_bf16 if u2 else lib.sr_cb16_fork_bwd_bf16
+    gsd, gud, md = gs.to(cuda), gu.to(cuda), mdev.to(cuda)
+    _ok(fn(gsd.data_ptr() if skip else None, gud.data_ptr(), md.data_ptr() if masked else None, dz.ptr(),
+           slope, n, cbn, h, w, _st()), 'fork_bwd')
+    gup = _u2_to_plain(gu)
+    s = (gup.float() + gs.float()).to(torch.bfloat16) if skip else gup       # round the sum to bf16, then apply the mask
+    ref = gup.double() + (gs.double() if skip else 0)
+    if masked:
+        s = torch.where(mplain.float() > 0, s.float(), s.float() * torch.tensor(slope, dtype=torch.float32)).to(torch.bfloat16)
+        ref = ref * _mask_factor(mplain, slope)
+    rounds = int(skip) + int(masked)
+    bound = 1.01 * rounds * EPS16 * ref.abs() + TINY
+    _pinned(dz.win().cpu(), s, ref, bound, 'fork_bwd')
+    _checked_slack(dz, 'fork_bwd')
+
+
+# ========================================================================= bf16 max-pool 2x2
+def _pool_input(n, cbn, h, w, content):
+    torch.manual_seed(h * 100 + w + len(content))
+    if content == 'random':
+        x = torch.randn(n, cbn, h, w, 16)
+    else:   # few distinct values: two-, three- and four-way ties everywhere, and ±0 ties
+        vals = torch.tensor([0.0, -0.0, 1.0, -1.0, 0.5])
+        x = vals[torch.randint(0, 5, (n, cbn, h, w, 16))]
+    return x.to(torch.bfloat16)
+
+
+@pytest.mark.parametrize('hw', [(2, 2), (5, 7), (8, 6), (3, 2)])
+@pytest.mark.parametrize('content', ['random', 'ties'])
+def test_maxpool2x2_bf16(cuda, lib, hw, content):
+    h, w = hw
+    n, cbn = 2, 2
+    x = _pool_input(n, cbn, h, w, content)
+    oh, ow = h // 2, w // 2
+    y = Buf(n, cbn, oh, ow, torch.bfloat16, cuda=cuda)
+    y.mark()
+    xd = x.to(cuda)
+    _ok(lib.sr_maxpool2x2_fwd_bf16(xd.data_ptr(), y.ptr(), n, cbn, h, w, _st()), 'maxpool_fwd_bf16')
+    x64 = _from_cb(x.double()).requires_grad_(True)
+    ref, idx = F.max_pool2d(x64, 2, 2, return_indices=True)
+    # the value is torch's; a ±0 tie gives +0 (fmaxf, IEEE maximum)
+    win = x.float()[:, :, :2 * oh, :2 * ow].reshape(n, cbn, oh, 2, ow, 2, 16)
+    has_pos0 = (_ibits(win.to(torch.bfloat16)) == 0).any(3).any(4)
+    exp = _to_cb(ref.detach(), 16, cbn).float()
+    exp = torch.where((exp == 0) & has_pos0, torch.zeros(()), exp)
+    got = y.win().cpu()
+    _same_bits(got, exp.to(torch.bfloat16), 'maxpool_fwd_bf16')
+    _neg_same_bits(got, exp.to(torch.bfloat16), 'maxpool_fwd_bf16')
+    _checked_slack(y, 'maxpool_fwd_bf16')
+    # backward: the gradient of a window goes to its first maximum in scan order; the last odd row / column gets zero
+    dy = (torch.randn(n, cbn, oh, ow, 16) * 2).to(torch.bfloat16)
+    dx = Buf(n, cbn, h, w, torch.bfloat16, cuda=cuda)
+    dx.mark()
+    dyd = dy.to(cuda)
+    _ok(lib.sr_maxpool2x2_bwd_bf16(xd.data_ptr(), dyd.data_ptr(), dx.ptr(), n, cbn, h, w, _st()), 'maxpool_bwd_bf16')
+    ref.backward(_from_cb(dy.double()))
+    expg = _to_cb(x64.grad, 16, cbn)
+    got = dx.win().cpu()
+    _same_bits(got, expg.to(torch.bfloat16), 'maxpool_bwd_bf16')
+    _neg_same_bits(got, expg.to(torch.bfloat16), 'maxpool_bwd_bf16')
+    _checked_slack(dx, 'maxpool_bwd_bf16')
+    if content == 'ties':   # the case has two-, three- and four-way ties of the maximum, and ±0 ties
+        ties = (win == win.amax((3, 5), keepdim=True)).sum((3, 5))
+        assert {2, 3, 4} <= set(ties.unique().tolist())
+        assert bool(((win.amax((3, 5)) == 0) & has_pos0 & (_ibits(win.to(torch.bfloat16)) == -32768).any(3).any(4)).any())
+
+
+# ========================================================================= bf16 bilinear x2 (both tile seams)
+BIL_SHAPES = [(7, 31), (8, 32), (9, 33), (17, 64), (9, 65), (1, 33), (17, 1), (1, 1), (8, 66)]
+
+
+def _bil_ref(t64):
+    return F.interpolate(t64, scale_factor=2, mode='bilinear', align_corners=False)
+
+
+@pytest.mark.parametrize('hw', BIL_SHAPES)
+@pytest.mark.parametrize('variant', ['plain', 'src2', 'src2_u2'])
+def test_bilinear2x_fwd_bf16(cuda, lib, hw, variant):
+    h, w = hw
+    if variant == 'src2_u2' and (h % 2 or w % 2):
+        h, w = h + h % 2, w + w % 2
+    n, cbn = 2, 2
+    torch.manual_seed(h * 1000 + w)
+    s = (torch.randn(n, cbn, h, w, 16) * 2).to(torch.bfloat16)
+    src = Buf(n, cbn, h, w, torch.bfloat16, pad=32, cuda=cuda)
+    src.put(s)
+    t = s.float()
+    s2p = None
+    if variant != 'plain':
+        s2 = (torch.randn(n, cbn, h, w, 16) * 2).to(torch.bfloat16)
+        t = (t + s2.float()).to(torch.bfloat16).float()          # bf16(src + src2), the documented pre-rounding
+        if variant == 'src2':
+            s2b = Buf(n, cbn, h, w, torch.bfloat16, pad=16, cuda=cuda)
+            s2b.put(s2)
+        else:
+            u = _plain_to_u2(s2)
+            s2b = Buf(n, 4 * cbn, h // 2, w // 2, torch.bfloat16, pad=48, cuda=cuda)
+            s2b.put(u)
+        s2p = s2b
+    dst = Buf(n, cbn, 2 * h, 2 * w, torch.bfloat16, pad=16, cuda=cuda)
+    dst.mark()
+    fn = lib.sr_bilinear2x_fwd_u2_bf16 if variant == 'src2_u2' else lib.sr_bilinear2x_fwd_bf16
+    _ok(fn(src.ptr(), src.stride, s2p.ptr() if s2p else None, s2p.stride if s2p else 0, dst.ptr(), dst.stride, n, cbn, h, w, _st()),
+        'bilinear2x_fwd_bf16')
+    t64 = _from_cb(t.double())
+    ref = _to_cb(_bil_ref(t64), 16, cbn)
+    S = _to_cb(_bil_ref(t64.abs()), 16, cbn)
+    bound = 4 * EPS * S + (EPS16 + EPS) * ref.abs() + TINY
+    got = dst.win().cpu()
+    _within(got, ref, bound, 'bilinear2x_fwd_bf16')
+    _neg_within(got, ref, bound, 'bilinear2x_fwd_bf16')
+    _checked_slack(dst, 'bilinear2x_fwd_bf16')
+
+
+@pytest.mark.parametrize('hw', BIL_SHAPES)
+@pytest.mark.parametrize('variant', ['plain', 'masked', 'masked_plain_out'])
+def test_bilinear2x_bwd_bf16(cuda, lib, hw, variant):
+    h, w = hw
+    n, cbn, slope = 2, 2, 0.2
+    torch.manual_seed(h * 1000 + w + 1)
+    g = (torch.randn(n, cbn, 2 * h, 2 * w, 16) * 2).to(torch.bfloat16)
+    gb = Buf(n, cbn, 2 * h, 2 * w, torch.bfloat16, pad=32, cuda=cuda)
+    gb.put(g)
+    gsrc = Buf(n, cbn, h, w, torch.bfloat16, pad=16, cuda=cuda)
+    gsrc.mark()
+    g64 = _from_cb(g.double())
+    x64 = torch.zeros(n, cbn * 16, h, w, dtype=torch.float64, requires_grad=True)
+    _bil_ref(x64).backward(g64)
+    ref = _to_cb(x64.grad, 16, cbn)
+    xa = torch.zeros_like(x64, requires_grad=True)
+    _bil_ref(xa).backward(g64.abs())
+    S = _to_cb(xa.grad, 16, cbn)
+    if variant == 'plain':
+        _ok(lib.sr_bilinear2x_bwd_bf16(gb.ptr(), gb.stride, gsrc.ptr(), gsrc.stride, n, cbn, h, w, _st()), 'bilinear2x_bwd_bf16')
+        bound = 16 * EPS * S + (EPS16 + EPS) * ref.abs() + TINY
+        got = gsrc.win().cpu()
+        _within(got, ref, bound, 'bilinear2x_bwd_bf16')
+        _neg_within(got, ref, bound, 'bilinear2x_bwd_bf16')
+        _checked_slack(gsrc, 'bilinear2x_bwd_bf16')
+        return
+    mask = _mask_values((n, cbn, h, w, 16), torch.bfloat16)
+    mb = Buf(n, cbn, h, w, torch.bfloat16, pad=48, cuda=cuda)
+    mb.put(mask)
+    plain = None
+    if variant == 'masked_plain_out':
+        plain = Buf(n, cbn, h, w, torch.bfloat16, pad=64, cuda=cuda)
+        plain.mark()
+    _ok(lib.sr_bilinear2x_bwd_lrelu_bf16(gb.ptr(), gb.stride, gsrc.ptr(), gsrc.stride, mb.ptr(), mb.stride, slope,
+                                         plain.ptr() if plain else None, plain.stride if plain else 0, n, cbn, h, w, _st()),
+        'bilinear2x_bwd_lrelu_bf16')
+    fac = _mask_factor(mask, slope)
+    refm = ref * fac
+    bound = 17 * EPS * S * fac + (EPS16 + EPS) * refm.abs() + TINY
+    got = gsrc.win().cpu()
+    _within(got, refm, bound, 'bilinear2x_bwd_lrelu_bf16')
+    _neg_within(got, refm, bound, 'bilinear2x_bwd_lrelu_bf16')
+    _checked_slack(gsrc, 'bilinear2x_bwd_lrelu_bf16')
+    if plain:
+        bound = 16 * EPS * S + (EPS16 + EPS) * ref.abs() + TINY
+        gotp = plain.win().cpu()
+        _within(gotp, ref, bound, 'bilinear2x_bwd_lrelu_bf16 plain')
+        _neg_within(gotp, ref, bound, 'bilinear2x_bwd_lrelu_bf16 plain')
+        _checked_slack(plain, 'bilinear2x_bwd_lrelu_bf16 plain')
+        # the masked output is the plain one with the LeakyReLU derivative applied to the same fp32 sum
+        assert bool((_ibits(got)[mask.float() > 0] == _ibits(gotp)[mask.float() > 0]).all())
+
+
+# ========================================================================= BatchNorm + LeakyReLU, eval mode
+@pytest.mark.parametrize('c', [5, 20])
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+def test_bn_lrelu_eval_mode(cuda, lib, c, dt):
+    n, h, w, slope, eps = 2, 5, 7, 0.2, _f32(1e-5)
+    dtype = torch.float32 if dt == 'f32' else torch.bfloat16
+    blk = 8 if dt == 'f32' else 16
+    blocks = -(-c // blk)
+    torch.manual_seed(c)
+    x = (torch.randn(n, c, h, w) * 1.5 + 0.3).to(dtype)
+    gamma, beta = torch.rand(c) + 0.5, torch.rand(c) - 0.5
+    rm, rv = torch.randn(c) * 0.3, torch.rand(c) + 0.5
+    xb = Buf(n, blocks, h, w, dtype, pad=16, cuda=cuda)
+    xb.put(_to_cb(x.float(), blk, blocks))
+    yb = Buf(n, blocks, h, w, dtype, pad=32, cuda=cuda)
+    yb.mark()
+    rmd, rvd = rm.to(cuda), rv.to(cuda)
+    gd, bd = gamma.to(cuda), beta.to(cuda)
+    smean, sinv = torch.empty(c, device=cuda), torch.empty(c, device=cuda)
+    wsb = lib.sr_reduce_workspace_bytes(c)
+    ws = torch.full((wsb + 4096,), 0xAB, dtype=torch.uint8, device=cuda)   # the tail must stay as it is
+    fwd = lib.sr_bn_lrelu_fwd_f32 if dt == 'f32' else lib.sr_bn_lrelu_fwd_bf16
+    _ok(fwd(xb.ptr(), xb.stride, yb.ptr(), yb.stride, n, c, h, w, gd.data_ptr(), bd.data_ptr(), rmd.data_ptr(), rvd.data_ptr(), 0,
+            0.1, eps, slope, smean.data_ptr(), sinv.data_ptr(), ws.data_ptr(), wsb, _st()), 'bn_lrelu_fwd eval')
+    assert torch.equal(_ibits(rmd.cpu()), _ibits(rm)) and torch.equal(_ibits(rvd.cpu()), _ibits(rv)), 'running buffers changed'
+    assert torch.equal(_ibits(smean.cpu()), _ibits(rm)), 'eval mode normalises with the running mean'
+    bn = torch.nn.BatchNorm2d(c, eps=eps).double().eval()
+    with torch.no_grad():
+        bn.weight.copy_(gamma.double())
+        bn.bias.copy_(beta.double())
+        bn.running_mean.copy_(rm.double())
+        bn.running_var.copy_(rv.double())
+    x64 = x.double().requires_grad_(True)
+    z64 = bn(x64)
+    ref = F.leaky_relu(z64, _f32(slope))
+    inv64 = 1.0 / torch.sqrt(rv.double() + eps)
+    xhat = (x.double() - rm.double().view(1, c, 1, 1)) * inv64.view(1, c, 1, 1)
+    S = (xhat * gamma.double().view(1, c, 1, 1)).abs() + beta.double().abs().view(1, c, 1, 1)
+    eout = EPS if dt == 'f32' else EPS16
+    bound = 8 * EPS * S + eout * ref.abs().detach() + TINY
+    got_cb = yb.win().cpu()
+    got = _from_cb(got_cb.float())
+    _within(got[:, :c], ref.detach(), bound, 'bn_lrelu_fwd eval')
+    _neg_within(got[:, :c], ref.detach(), bound, 'bn_lrelu_fwd eval')
+    assert bool((_ibits(got[:, c:]) == 0).all()), 'padding channels must be +0'
+    _checked_slack(yb, 'bn_lrelu_fwd eval')
+    # backward from the saved output y: dz = dy * lrelu'(y), dx = gamma invstd dz; dgamma, dbeta = sums over n h w
+    dy = (torch.randn(n, c, h, w)).to(dtype)
+    dyb = Buf(n, blocks, h, w, dtype, pad=48, cuda=cuda)
+    dyb.put(_to_cb(dy.float(), blk, blocks))
+    dxb = Buf(n, blocks, h, w, dtype, pad=16, cuda=cuda)
+    dxb.mark()
+    dgam, dbet = torch.full((c,), float('nan'), device=cuda), torch.full((c,), float('nan'), device=cuda)
+    bwd = lib.sr_bn_lrelu_bwd_f32 if dt == 'f32' else lib.sr_bn_lrelu_bwd_bf16
+    _ok(bwd(xb.ptr(), xb.stride, dyb.ptr(), dyb.stride, yb.ptr(), yb.stride, dxb.ptr(), dxb.stride, n, c, h, w, gd.data_ptr(),
+            smean.data_ptr(), sinv.data_ptr(), 0, slope, dgam.data_ptr(), dbet.data_ptr(), ws.data_ptr(), wsb, _st()),
+        'bn_lrelu_bwd eval')
+    yv = got[:, :c].double()
+    dz = dy.double() * torch.where(yv > 0, 1.0, _f32(slope)).double()
+    z64.backward(dz)
+    eval_dx = x64.grad
+    dx_bound = 7 * EPS * eval_dx.abs() + eout * eval_dx.abs() + TINY
+    gdx = _from_cb(dxb.win().cpu().float())
+    _within(gdx[:, :c], eval_dx, dx_bound, 'bn_lrelu_bwd eval dx')
+    _neg_within(gdx[:, :c], eval_dx, dx_bound, 'bn_lrelu_bwd eval dx')
+    assert bool((_ibits(gdx[:, c:]) == 0).all()), 'padding channels must be +0'
+    _checked_slack(dxb, 'bn_lrelu_bwd eval')
+    M = n * h * w
+    Sg = (dz.abs() * xhat.abs()).sum((0, 2, 3))
+    Sb = dz.abs().sum((0, 2, 3))
+    for got_v, ref_v, S_v, what in ((dgam, bn.weight.grad, Sg, 'dgamma'), (dbet, bn.bias.grad, Sb, 'dbeta')):
+        bnd = (M + 6) * EPS * S_v + TINY
+        _within(got_v.cpu(), ref_v, bnd, what)
+        _neg_within(got_v.cpu(), ref_v, bnd, what)
+    assert bool((ws[wsb:] == 0xAB).all()), 'the reductions wrote past sr_reduce_workspace_bytes(c)'
+
