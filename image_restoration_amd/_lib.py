@@ -1,4 +1,4 @@
-"""ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h).
+"""ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h and include/sr_hip_ridnet.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -293,6 +293,40 @@ SIGNATURES.update({
 })
 SIGNATURES.update({'sr_vgg_num_params': (C.c_int, [C.POINTER(VGGCfg)]), 'sr_vgg_num_batchnorm': (C.c_int, [C.POINTER(VGGCfg)])})
 
+
+class ConvdDesc(C.Structure):
+    """struct sr_convd_desc (include/sr_hip_ridnet.h)."""
+    _fields_ = [('base', ConvDesc), ('ksize', C.c_int), ('dilation', C.c_int), ('post_act', C.c_int), ('out_pre', C.c_void_p),
+                ('out_pre_img_stride', C.c_int64)]
+
+
+class ConvdWgradDesc(C.Structure):
+    """struct sr_convd_wgrad_desc (include/sr_hip_ridnet.h)."""
+    _fields_ = [('base', WgradDesc), ('ksize', C.c_int), ('dilation', C.c_int)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_ridnet.h declares (kept apart from SIGNATURES, which mirrors sr_hip.h)
+RIDNET_SIGNATURES = {
+    'sr_convk_packed_weight_floats': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'sr_convk_pack_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'sr_convd_f32': (C.c_int, [C.POINTER(ConvdDesc), C.c_void_p]),
+    'sr_convd_wgrad_slab_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'sr_convd_wgrad_f32': (C.c_int, [C.POINTER(ConvdWgradDesc), C.c_void_p]),
+    'sr_ridnet_mean_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'sr_ridnet_sub_mean_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p]),
+    'sr_ridnet_add_mean_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_int, C.c_void_p]),
+    'sr_ridnet_sub_mean_bwd_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sr_ridnet_add_mean_bwd_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sr_ca_scale_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p]),
+    'sr_cb8_relu_mask_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -305,7 +339,7 @@ def load():
         raise SrHipError(f'{LIB_PATH} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                          '(or `make -C image_restoration_amd/csrc`). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1014,5 +1014,11 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "ca_bwd_finish_kernel", "ca_wgrad_kernel", "ca_bwd_apply_kernel"};
     return cnames[id - 74];
   }
+  if (id >= 81 && id < 91) {  // ridnet_ops.hip (include/sr_hip_ridnet.h)
+    static const char* rnames[10] = {"convd_f32_kernel", "convd_f32_kernel", "wgradd_f32_kernel", "wgradd_f32_kernel",
+                                     "sub_mean_kernel", "add_mean_kernel", "mean_bwd_partial_kernel", "mean_bwd_finish_kernel",
+                                     "cb8_stream_kernelILb1E", "cb8_stream_kernelILb0E"};
+    return rnames[id - 81];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -401,6 +401,171 @@ def ca_bwd_apply(g, s, q, res_scale=1.0, out=None):
     return out
 
 
+# ---- RIDNet: dilated 3x3 / 1x1 convolutions, the MeanShift ends, attention scale (include/sr_hip_ridnet.h) ----
+
+class PackedConvK:
+    """MFMA operand image of a k x k conv, k in {1, 3}, dense cin (sr_convk_pack_f32); mode 1 = data gradient.  A 3x3 image
+    serves every dilation."""
+
+    def __init__(self, weight, bias=None, mode=0):
+        _need_cuda(weight, 'PackedConvK')
+        lib = _lib.load()
+        weight = weight.detach().contiguous().float()
+        cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+        assert weight.shape[2:] in ((1, 1), (3, 3)), weight.shape
+        self.ksize, self.mode = k, mode
+        if mode == 0:
+            self.cout, self.src_channels = cout, (cin + 7) // 8 * 8
+        else:
+            self.cout, self.src_channels = (cin + 7) // 8 * 8, (cout + 7) // 8 * 8
+        dev = weight.device
+        self.w = torch.empty(lib.sr_convk_packed_weight_floats(cout, cin, k, mode), dtype=torch.float32, device=dev)
+        self.b = None
+        if mode == 0 and bias is not None:
+            bias = bias.detach().contiguous().float()
+            self.b = torch.empty(lib.sr_conv3x3_packed_bias_floats(cout), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.sr_convk_pack_f32(weight.data_ptr(), bias.data_ptr() if self.b is not None else None, cout, cin, k, mode,
+                                             self.w.data_ptr(), self.b.data_ptr() if self.b is not None else None, _stream(dev)),
+                       'sr_convk_pack_f32')
+
+
+def convd(src, pc, dilation=1, out=None, *, post_act=False, out_pre=None, **kw):
+    """Stride-1 "same" k x k conv (k = pc.ksize; dilation 1..4 for k = 3) — one sr_convd_f32 launch.
+    post_act False: out = alpha*act(conv+bias) + beta1*res1 + beta2*res2 (conv3x3's epilogue); True: out = act(alpha*(conv+bias) +
+    beta1*res1 + beta2*res2).  ``out_pre``: a CB8 window that also receives alpha*act(conv+bias) (post_act False).  Other keywords
+    as conv3x3 (act_slope, alpha, res1/beta1, res2/beta2, accumulate, mask/mask_cb0/mask_slope)."""
+    lib = _lib.load()
+    base, ret = _conv_desc_f32(src, pc, out, **kw)
+    d = _lib.ConvdDesc()
+    d.base, d.ksize, d.dilation, d.post_act = base, getattr(pc, 'ksize', 3), int(dilation), int(post_act)
+    if out_pre is not None:
+        assert (out_pre.n, out_pre.h, out_pre.w) == (ret.n, ret.h, ret.w) and out_pre.channels >= ret.channels
+        d.out_pre, d.out_pre_img_stride = out_pre.ptr, out_pre.img_stride
+    with torch.cuda.device(src.device):
+        _lib.check(lib.sr_convd_f32(C.byref(d), _stream(src.device)), 'sr_convd_f32')
+    return ret
+
+
+def convd_wgrad(src, dy, cout, cin, ksize=3, dilation=1, *, scale=1.0, want_bias=True, out=None):
+    """(dweight [cout, cin, k, k], dbias [cout]) of a convd conv from its source ``src`` and its pre-activation output gradient
+    ``dy`` (CB8) — one sr_convd_wgrad_f32 call.  ``out`` = (dweight, dbias or None) device pointers the gradients are ADDED into."""
+    lib = _lib.load()
+    cin_pad = (cin + 7) // 8 * 8
+    assert src.channels == cin_pad, (src.channels, cin_pad)
+    assert (dy.n, dy.h, dy.w) == (src.n, src.h, src.w) and dy.channels >= (cout + 7) // 8 * 8
+    dev = src.device
+    if out is not None:
+        dw_ptr, db_ptr, acc = out[0], out[1], 1
+        dw = db = None
+    else:
+        dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=dev)
+        db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_bias else None
+        dw_ptr, db_ptr, acc = dw.data_ptr(), (db.data_ptr() if db is not None else None), 0
+    nbytes = lib.sr_convd_wgrad_slab_bytes(src.n, src.h, src.w, cout, cin, ksize, dilation)
+    slab = scratch(dev, nbytes, 'slab')
+    d = _lib.ConvdWgradDesc()
+    b = d.base
+    b.x, b.x_img_stride, b.cin_pad, b.in_h, b.in_w, b.upsample = src.ptr, src.img_stride, cin_pad, src.h, src.w, 0
+    b.dy, b.dy_img_stride = dy.ptr, dy.img_stride
+    b.cout, b.cin, b.first_seg, b.seg, b.n, b.scale = cout, cin, cin, 0, src.n, scale
+    b.dweight, b.dbias, b.accumulate = dw_ptr, db_ptr, acc
+    b.slab, b.slab_bytes = slab.data_ptr(), nbytes
+    d.ksize, d.dilation = ksize, dilation
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_convd_wgrad_f32(C.byref(d), _stream(dev)), 'sr_convd_wgrad_f32')
+    return dw, db
+
+
+def ridnet_sub_mean(x, w, b):
+    """s = W x + b (RIDNet's sub_mean, a trainable 3-channel 1x1 conv) from NCHW fp32 ``x`` [N, 3, H, W] into a one-block CB8
+    tensor (channels 3..7 zero) — sr_ridnet_sub_mean_f32."""
+    _need_cuda(x, 'ridnet_sub_mean')
+    lib = _lib.load()
+    n, c, h, ww = x.shape
+    assert c == 3 and x.is_contiguous()
+    out = CB8.empty(n, 8, h, ww, x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.sr_ridnet_sub_mean_f32(x.data_ptr(), w.data_ptr(), b.data_ptr(), out.ptr, out.img_stride, n, h, ww,
+                                              _stream(x.device)), 'sr_ridnet_sub_mean_f32')
+    return out
+
+
+def ridnet_add_mean(x, t, w, b):
+    """y = x + W t + b (add_mean plus RIDNet's global residual): ``x`` NCHW [N, 3, H, W], ``t`` the tail conv's CB8 output —
+    sr_ridnet_add_mean_f32."""
+    lib = _lib.load()
+    n, _, h, ww = x.shape
+    y = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.sr_ridnet_add_mean_f32(x.data_ptr(), t.ptr, t.img_stride, w.data_ptr(), b.data_ptr(), y.data_ptr(), n, h, ww,
+                                              _stream(x.device)), 'sr_ridnet_add_mean_f32')
+    return y
+
+
+def _mean_ws(lib, dev, n, h, w):
+    nbytes = lib.sr_ridnet_mean_workspace_bytes(n, h, w)
+    return scratch(dev, nbytes, 'ridnet_mean'), nbytes
+
+
+def ridnet_sub_mean_bwd(x, g, w, dw=None, db=None, accumulate=False, want_dx=False, dx_res=None):
+    """Adjoint of ridnet_sub_mean given g = dL/ds (CB8): dW, db written (accumulate: added) through the device pointers ``dw`` /
+    ``db`` (ints or None); returns dx = W^T g (+ dx_res, NCHW) when ``want_dx`` — sr_ridnet_sub_mean_bwd_f32."""
+    lib = _lib.load()
+    n, _, h, ww = x.shape
+    dev = x.device
+    dx = torch.empty_like(x) if want_dx else None
+    ws, nbytes = _mean_ws(lib, dev, n, h, ww)
+    if dx_res is not None:
+        assert dx_res.is_contiguous() and dx_res.shape == x.shape
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_ridnet_sub_mean_bwd_f32(x.data_ptr(), g.ptr, g.img_stride, w.data_ptr(), dw, db, int(accumulate),
+                                                  dx.data_ptr() if dx is not None else None,
+                                                  dx_res.data_ptr() if dx_res is not None else None, n, h, ww, ws.data_ptr(), nbytes,
+                                                  _stream(dev)), 'sr_ridnet_sub_mean_bwd_f32')
+    return dx
+
+
+def ridnet_add_mean_bwd(g, t, w, dw=None, db=None, accumulate=False):
+    """Adjoint of ridnet_add_mean's mix given g = dL/dy (NCHW): dW, db through device pointers (as ridnet_sub_mean_bwd); returns
+    dt = W^T g as a one-block CB8 tensor (channels 3..7 zero) — sr_ridnet_add_mean_bwd_f32."""
+    lib = _lib.load()
+    g = g.contiguous()
+    n, _, h, ww = g.shape
+    dev = g.device
+    dt = CB8.empty(n, 8, h, ww, dev)
+    ws, nbytes = _mean_ws(lib, dev, n, h, ww)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_ridnet_add_mean_bwd_f32(g.data_ptr(), t.ptr, t.img_stride, w.data_ptr(), dw, db, int(accumulate), dt.ptr,
+                                                  dt.img_stride, n, h, ww, ws.data_ptr(), nbytes, _stream(dev)),
+                   'sr_ridnet_add_mean_bwd_f32')
+    return dt
+
+
+def ca_scale(u, s, out=None):
+    """out = u * s[n][c] on CB8 (RIDNet's channel attention, no identity) — sr_ca_scale_f32."""
+    lib = _lib.load()
+    if out is None:
+        out = CB8.empty(u.n, u.channels, u.h, u.w, u.device)
+    assert out.channels == u.channels and s.is_contiguous() and tuple(s.shape) == (u.n, u.channels)
+    with torch.cuda.device(u.device):
+        _lib.check(lib.sr_ca_scale_f32(u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n, u.channels, u.h, u.w,
+                                       _stream(u.device)), 'sr_ca_scale_f32')
+    return out
+
+
+def relu_mask(g, mask, slope=0.0, out=None):
+    """out = mask > 0 ? g : slope * g on CB8 windows of equal shape — sr_cb8_relu_mask_f32."""
+    lib = _lib.load()
+    if out is None:
+        out = CB8.empty(g.n, g.channels, g.h, g.w, g.device)
+    assert (mask.n, mask.cbn, mask.h, mask.w) == (g.n, g.cbn, g.h, g.w) and out.cbn == g.cbn
+    with torch.cuda.device(g.device):
+        _lib.check(lib.sr_cb8_relu_mask_f32(g.ptr, g.img_stride, mask.ptr, mask.img_stride, float(slope), out.ptr, out.img_stride, g.n,
+                                            g.cbn, g.h, g.w, _stream(g.device)), 'sr_cb8_relu_mask_f32')
+    return out
+
+
 class PackedConv4x4s2:
     """Parity-pass weight images of a 4x4 / stride 2 / pad 1 conv (sr_conv4x4s2_pack_f32); mode 1 = data gradient."""
 

@@ -1,4 +1,5 @@
-"""Single-image / folder super-resolution with an RRDBNet, MSRResNet or RCAN checkpoint on the HIP path.
+"""Single-image / folder super-resolution with an RRDBNet, MSRResNet or RCAN checkpoint, or denoising with a RIDNet one, on the
+HIP path.
 
 The reference's inference.py serves a different model (GFPGANv1OCR, inference.py:28-40); what this script keeps is
 its I/O convention: read BGR uint8, /255, BGR->RGB CHW float (img2tensor, img_util.py:9-35),
@@ -9,6 +10,7 @@ sr_model.py:148).  Large frames go through the tiler (tiling.py).
         [--num_block 23 --num_feat 64 --tile 512 --tile_pad 16 --compute_dtype fp32|bf16 --niqe_params niqe_pris_params.npz]
     python -m image_restoration_amd.inference --arch MSRResNet --scale 3 --input crop.png --output out.png --model_path net_g.pth
     python -m image_restoration_amd.inference --arch RCAN --scale 4 --input crop.png --output out.png --model_path RCAN_BIX4-official.pth
+    python -m image_restoration_amd.inference --arch RIDNet --input noisy.png --output clean.png --model_path RIDNet.pth
     python -m torch.distributed.run --nproc-per-node 8 -m image_restoration_amd.inference --launcher pytorch --tile 512 ...
 """
 import argparse
@@ -37,15 +39,22 @@ def imwrite_bgr(path, img):
     Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(path)
 
 
-ARCH_DEFAULT_BLOCKS = {'RRDBNet': 23, 'MSRResNet': 16, 'RCAN': 20}
+ARCH_DEFAULT_BLOCKS = {'RRDBNet': 23, 'MSRResNet': 16, 'RCAN': 20, 'RIDNet': 4}
 
 
 def generator_options(args):
     """network_g option block of the command line.  RRDBNet: scale 1/2/4, fp32 or bf16; MSRResNet: upscale 2/3/4, fp32 only;
-    RCAN: upscale 2/3/4/8, fp32 only, 20 blocks per group by default (the released checkpoints' layout)."""
+    RCAN: upscale 2/3/4/8, fp32 only, 20 blocks per group by default (the released checkpoints' layout); RIDNet: scale 1 (a
+    denoiser), fp32 only, 4 EAMs by default, --num_feat = mid_channels."""
     arch = getattr(args, 'arch', 'RRDBNet')
     num_block = getattr(args, 'num_block', None)
     num_block = ARCH_DEFAULT_BLOCKS[arch] if num_block is None else num_block
+    if arch == 'RIDNet':
+        if args.scale != 1:
+            raise ValueError(f'--arch RIDNet is a denoiser: it takes --scale 1 only, not {args.scale}')
+        if getattr(args, 'compute_dtype', 'fp32') != 'fp32':
+            raise ValueError('--arch RIDNet runs in fp32 only (no --compute_dtype bf16)')
+        return dict(type='RIDNet', in_channels=3, mid_channels=args.num_feat, out_channels=3, num_block=num_block)
     if arch == 'RCAN':
         if args.scale not in (2, 3, 4, 8):
             raise ValueError(f'--arch RCAN takes --scale 2, 3, 4 or 8, not {args.scale}')
@@ -96,18 +105,20 @@ def main(argv=None):
     ap.add_argument('--input', required=True, help='image file or folder')
     ap.add_argument('--output', required=True, help='output file or folder')
     ap.add_argument('--model_path', default=None)
-    ap.add_argument('--scale', type=int, default=4)
+    ap.add_argument('--scale', type=int, default=None, help='default: 1 for RIDNet, 4 otherwise')
     ap.add_argument('--num_feat', type=int, default=64)
-    ap.add_argument('--arch', choices=('RRDBNet', 'MSRResNet', 'RCAN'), default='RRDBNet',
-                    help='generator: RRDBNet (ESRGAN; --scale 1/2/4), MSRResNet (--scale 2/3/4, fp32) or RCAN (--scale 2/3/4/8, fp32)')
+    ap.add_argument('--arch', choices=('RRDBNet', 'MSRResNet', 'RCAN', 'RIDNet'), default='RRDBNet',
+                    help='generator: RRDBNet (ESRGAN; --scale 1/2/4), MSRResNet (--scale 2/3/4, fp32), RCAN (--scale 2/3/4/8, fp32) '
+                         'or the RIDNet denoiser (--scale 1, fp32)')
     ap.add_argument('--num_block', type=int, default=None,
-                    help='default: 23 for RRDBNet, 16 for MSRResNet, 20 (blocks per residual group) for RCAN')
+                    help='default: 23 for RRDBNet, 16 for MSRResNet, 20 (blocks per residual group) for RCAN, 4 (EAMs) for RIDNet')
     ap.add_argument('--num_group', type=int, default=10, help='RCAN: residual groups')
     ap.add_argument('--squeeze_factor', type=int, default=16, help='RCAN: channel-attention squeeze factor')
     ap.add_argument('--num_grow_ch', type=int, default=32)
     ap.add_argument('--tile', type=int, default=0,
-                    help='split frames larger than this into tiles (0: whole image).  RCAN: its channel attention pools over each '
-                         'tile, so a tiled RCAN output differs from the whole-image one')
+                    help='split frames larger than this into tiles (0: whole image).  RCAN and RIDNet: their channel attention '
+                         'pools over each tile, so a tiled output differs from the whole-image one (RIDNet\'s receptive field '
+                         'without the attention has a radius of about 50 pixels: --tile_pad 16 still leaves seams)')
     ap.add_argument('--tile_pad', type=int, default=16)
     ap.add_argument('--launcher', choices=('none', 'pytorch'), default='none',
                     help="pytorch: started by torch.distributed.run, one process per GPU; the tiles of every image (--tile) are "
@@ -119,6 +130,8 @@ def main(argv=None):
                     help="print the NIQE of each restored image (no reference needed; computed on the device); PATH is BasicSR's "
                          'niqe_pris_params.npz, the pristine model')
     args = ap.parse_args(argv)
+    if args.scale is None:
+        args.scale = 1 if args.arch == 'RIDNet' else 4
     try:
         generator_options(args)
     except ValueError as e:

@@ -240,3 +240,55 @@ def rcan_state_dict(seed=0, **cfg):
         w, b = conv_params(rng, ws, rdb_style=wn.startswith('body.') and not ca, bias_scale=0.5 if ca else 0.05)
         sd[wn], sd[bn] = w, b
     return sd
+
+
+def ridnet_param_shapes(in_channels=3, mid_channels=64, out_channels=3, num_block=4, **_):
+    """(name, shape) in state_dict (= named_parameters) order of RIDNet (ridnet_arch.py:138-180)."""
+    out = []
+    mid, hid = mid_channels, mid_channels // 16
+
+    def conv(name, ci, co, k=3):
+        out.append((f'{name}.weight', (co, ci, k, k)))
+        out.append((f'{name}.bias', (co,)))
+
+    conv('sub_mean', in_channels, in_channels, 1)
+    conv('add_mean', out_channels, out_channels, 1)
+    conv('head', in_channels, mid)
+    for b in range(num_block):
+        pre = f'body.{b}'
+        conv(f'{pre}.merge.dilation1.0', mid, mid)
+        conv(f'{pre}.merge.dilation1.2', mid, mid)
+        conv(f'{pre}.merge.dilation2.0', mid, mid)
+        conv(f'{pre}.merge.dilation2.2', mid, mid)
+        conv(f'{pre}.merge.aggregation.0', 2 * mid, mid)
+        conv(f'{pre}.block1.conv1', mid, mid)
+        conv(f'{pre}.block1.conv2', mid, mid)
+        conv(f'{pre}.block2.body.0', mid, mid)
+        conv(f'{pre}.block2.body.2', mid, mid)
+        conv(f'{pre}.block2.body.4', mid, mid, 1)
+        conv(f'{pre}.ca.attention.1', mid, hid, 1)
+        conv(f'{pre}.ca.attention.3', hid, mid, 1)
+    conv('tail', mid, out_channels)
+    return out
+
+
+def ridnet_state_dict(seed=0, img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040), **cfg):
+    """OrderedDict name -> np.float32 array for RIDNet(**cfg): the MeanShift layers near their initial eye(3) and
+    -/+ img_range * mean, perturbed (+-0.05 on the mix, +-1 on the bias) so that both act as full 3x3 mixes; ResidualBlockNoBN's
+    convs ~ kaiming_normal * 0.1 as initialised there; every other conv ~ U(+-1/sqrt(fan_in)) with small non-zero biases, larger
+    (+-0.5) on the attention so its ReLU and sigmoid see both signs."""
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    shapes = ridnet_param_shapes(**cfg)
+    mean = np.asarray(rgb_mean, np.float64)
+    for i in range(0, len(shapes), 2):
+        (wn, ws), (bn, _) = shapes[i], shapes[i + 1]
+        if wn in ('sub_mean.weight', 'add_mean.weight'):
+            sign = -1.0 if wn.startswith('sub') else 1.0
+            w = np.eye(3, dtype=np.float32).reshape(3, 3, 1, 1) + (rng.random(ws, dtype=np.float32) * 2 - 1) * np.float32(0.05)
+            b = (sign * img_range * mean + (rng.random(3) * 2 - 1)).astype(np.float32)
+        else:
+            ca = '.attention.' in wn
+            w, b = conv_params(rng, ws, rdb_style='.block1.' in wn, bias_scale=0.5 if ca else 0.05)
+        sd[wn], sd[bn] = w.astype(np.float32), b
+    return sd
