@@ -128,3 +128,25 @@ def test_loss_oracle(golden):
     a, b = torch.from_numpy(g['gan_map_a']), torch.from_numpy(g['gan_map_b'])
     _close(D.gan_loss(a - b.mean(), True, False, 5e-3), g['gan_map_real1_disc0_rel1_loss'], 1e-8)
     _close(D.gan_loss(a, False, True, 5e-3), g['gan_map_real0_disc1_rel0_loss'], 1e-7)
+
+
+def test_ridnet_oracle_forward_and_backward(golden):
+    """oracle/ridnet_ref.py in float64 against the reference's RIDNet (g_w_ridnet, both fixture shapes): the output within the
+    reference's own float32 distance from float64 (the fixture's y is the float32 run), dL/dx and every parameter gradient
+    within the float32 rounding they are stored with (2^-24 relative) plus 1e-9 of the tensor's largest magnitude."""
+    from oracle import ridnet_ref as RR
+    g = golden('g_w_ridnet')
+    cfg = dict(in_channels=3, mid_channels=16, out_channels=3, num_block=2)
+    for i in (0, 1):
+        sd = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in synth.ridnet_state_dict(400 + i, **cfg).items()}
+        x = torch.from_numpy(g[f'fwd{i}_x']).double().requires_grad_(True)
+        y = RR.ridnet_forward(x, sd, num_block=2)
+        err = float((y.detach() - torch.from_numpy(g[f'fwd{i}_y']).double()).abs().max())
+        assert err <= float(g[f'fwd{i}_y32_err']) * (1 + 1e-6) + 1e-9, (i, err, float(g[f'fwd{i}_y32_err']))
+        y.backward(torch.from_numpy(synth.gaussian(int(g[f'fwd{i}_gy_seed']), tuple(x.shape))).double())
+        names = sorted(k[len(f'fwd{i}_grad64.'):] for k in g if k.startswith(f'fwd{i}_grad64.'))
+        assert names == sorted(sd)
+        for key, got in [('dx64', x.grad)] + [(f'grad64.{k}', v.grad) for k, v in sd.items()]:
+            want = torch.from_numpy(g[f'fwd{i}_{key}']).double()
+            bound = 2.0 ** -24 * want.abs() + 1e-9 * float(want.abs().max()) + 1e-30
+            assert bool(((got - want).abs() <= bound).all()), (i, key, float((got - want).abs().max()))

@@ -543,3 +543,63 @@ def test_srmodel_steps_are_bit_reproducible(cuda):
     p1, l1 = run()
     p2, l2 = run()
     assert all(torch.equal(a, b) for a, b in zip(p1, p2)) and l1 == l2
+
+
+def test_small_net_on_the_8_row_path_matches_the_float64_oracle(cuda):
+    """The fixture's small net (mid 16, 2 EAMs) at batch 4 of 128^2: at cout 16 that is 4 strips x 16 row tiles x 4 images =
+    256 workgroups, so every sr_convd_f32 launch takes the 8-row tiles (asserted through the restated dispatch of
+    tests/test_convd_ops_gpu.py on the profiled launches).  Forward, dL/dx and every parameter gradient against autograd
+    through oracle/ridnet_ref.py in float64 (pinned to the reference by tests/test_oracle.py).  Bounds: the forward within 10x
+    the float32 oracle's own distance from float64 (features are in the hundreds), never below 1e-4; gradients, as
+    tests/test_backward_gpu.py states for whole networks, relative-L2 < 2e-3 and max-relative < 2e-2, or 5x the float32
+    oracle's own distance from float64 where that is larger (the G-i rule of tests/test_training_gpu.py): a ReLU pre-activation
+    within rounding of zero may take the other branch in float32, and at 65536 pixels per image with features in the hundreds
+    the float32 oracle itself moves a dilated layer's gradient by ~1e-3; a missed halo row or a wrong tile is O(1) on the
+    elements it touches."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_convd_ops_gpu import _convd_instance
+    from oracle import ridnet_ref as RR
+    sd_np = synth.ridnet_state_dict(400, **SMALL_CFG)
+    x_np = synth.uniform_input(430, (4, 3, 128, 128))
+    gy_np = synth.gaussian(431, (4, 3, 128, 128))
+    net = _load(ira.build_network(dict(type='RIDNet', **SMALL_CFG)), sd_np, cuda).train()
+    x = torch.from_numpy(x_np).to(cuda).requires_grad_(True)
+    lib = _lib.load()
+    out = {}
+
+    def run():
+        out['y'] = net(x)
+        out['y'].backward(torch.from_numpy(gy_np).to(cuda))
+        torch.cuda.synchronize()
+    recs = _profiled(lib, run)
+    convd = [r for r in recs if r.kernel_id in (81, 82)]
+    assert len(convd) >= 2 * 6, len(convd)      # per EAM, forward alone: d = 2, 3, 4, the aggregation, block1's post_act, the 1x1
+    for r in convd:
+        assert (r.n, r.h, r.w) == (4, 128, 128) and _convd_instance(3, 1, r.cout, r.n, r.h, r.w)[1:] == (2, 16), (r.cout, r.cin)
+    sd = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in sd_np.items()}
+    xr = torch.from_numpy(x_np).double().requires_grad_(True)
+    yr = RR.ridnet_forward(xr, sd, num_block=2)
+    yr.backward(torch.from_numpy(gy_np).double())
+    sd32 = {k: torch.from_numpy(v).clone().requires_grad_(True) for k, v in sd_np.items()}
+    x32 = torch.from_numpy(x_np).clone().requires_grad_(True)
+    y32 = RR.ridnet_forward(x32, sd32, num_block=2)
+    y32.backward(torch.from_numpy(gy_np))
+    y32 = y32.detach()
+    tol = max(1e-4, 10 * float((y32.double() - yr.detach()).abs().max()))
+    err = float((out['y'].detach().cpu().double() - yr.detach()).abs().max())
+    assert err < tol, (err, tol)
+
+    def rel(a, b):
+        a, b = a.detach().cpu().double(), b.detach().double()
+        return float((a - b).norm() / max(float(b.norm()), 1e-30)), float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
+    def check(got, want, q32, what):
+        r2, rm = rel(got, want)
+        n2, nm = rel(q32, want)
+        assert r2 < max(2e-3, 5 * n2) and rm < max(2e-2, 5 * nm), (what, r2, rm, n2, nm)
+    check(x.grad, xr.grad, x32.grad, 'dx')
+    params = dict(net.named_parameters())
+    assert sorted(params) == sorted(sd)
+    for k, p in sd.items():
+        check(params[k].grad, p.grad, sd32[k].grad, k)

@@ -21,7 +21,7 @@ from image_restoration_amd.utils.options import load_yaml
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'sr_hip_ridnet.h')
 OPTION_FILES = sorted(glob.glob(os.path.join(ROOT, 'options', '*', 'RIDNet', '*.yml')))
-_GPU = 'tests/test_ridnet_gpu.py::'
+_GPU = 'tests/test_convd_ops_gpu.py::'
 
 
 def _net(**kw):
@@ -154,15 +154,15 @@ def test_inference_help_warns_that_attention_pools_per_tile(capsys):
 
 # ------------------------------------------------------------------------------------------ ledger of sr_hip_ridnet.h
 PINNED = {
-    'sr_convk_pack_f32': _GPU + 'test_convd_forward_matches_float64',
-    'sr_convd_f32': _GPU + 'test_convd_forward_matches_float64',
-    'sr_convd_wgrad_f32': _GPU + 'test_convd_weight_gradient_matches_float64_and_is_bit_reproducible',
-    'sr_ridnet_sub_mean_f32': _GPU + 'test_mean_shift_ends_match_float64',
-    'sr_ridnet_add_mean_f32': _GPU + 'test_mean_shift_ends_match_float64',
-    'sr_ridnet_sub_mean_bwd_f32': _GPU + 'test_mean_shift_ends_match_float64',
-    'sr_ridnet_add_mean_bwd_f32': _GPU + 'test_mean_shift_ends_match_float64',
-    'sr_ca_scale_f32': _GPU + 'test_attention_scale_and_relu_mask',
-    'sr_cb8_relu_mask_f32': _GPU + 'test_attention_scale_and_relu_mask',
+    'sr_convk_pack_f32': _GPU + 'test_convd_forward',
+    'sr_convd_f32': _GPU + 'test_convd_forward',
+    'sr_convd_wgrad_f32': _GPU + 'test_convd_weight_gradient',
+    'sr_ridnet_sub_mean_f32': _GPU + 'test_mean_shift_bands',
+    'sr_ridnet_add_mean_f32': _GPU + 'test_mean_shift_bands',
+    'sr_ridnet_sub_mean_bwd_f32': _GPU + 'test_mean_shift_bands',
+    'sr_ridnet_add_mean_bwd_f32': _GPU + 'test_mean_shift_bands',
+    'sr_ca_scale_f32': _GPU + 'test_ca_scale_bit_for_bit',
+    'sr_cb8_relu_mask_f32': _GPU + 'test_relu_mask_bit_for_bit',
 }
 _SIZE = 'size / workspace query: host arithmetic, no kernel'
 EXEMPT = {
@@ -187,11 +187,12 @@ def test_every_declared_entry_point_is_pinned_or_exempt_and_exported():
     lib = _lib.load()
     for s in declared:
         assert hasattr(lib, s), s
-    tree = ast.parse(open(os.path.join(ROOT, 'tests', 'test_ridnet_gpu.py')).read())
-    tests = {n.name for n in tree.body if isinstance(n, ast.FunctionDef) and n.name.startswith('test_')}
     for s, target in PINNED.items():
         path, _, func = target.partition('::')
-        assert path == 'tests/test_ridnet_gpu.py' and func in tests, (s, target)
+        assert re.fullmatch(r'tests/test_\w+_gpu\.py', path) and os.path.exists(os.path.join(ROOT, path)), (s, target)
+        tree = ast.parse(open(os.path.join(ROOT, path)).read())
+        tests = {n.name for n in tree.body if isinstance(n, ast.FunctionDef) and n.name.startswith('test_')}
+        assert func in tests, (s, target)
 
 
 def test_size_queries():
