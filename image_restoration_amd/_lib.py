@@ -1,4 +1,4 @@
-"""ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h and include/sr_hip_ridnet.h).
+"""ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h and include/sr_hip_gfpgan.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -327,6 +327,37 @@ RIDNET_SIGNATURES = {
                                        C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
+class GfpganStyleLayer(C.Structure):
+    """struct sr_gfpgan_style_layer (include/sr_hip_gfpgan.h)."""
+    _fields_ = [('mod_w', C.c_void_p), ('mod_b', C.c_void_p), ('q', C.c_void_p), ('cin', C.c_int), ('cout', C.c_int),
+                ('latent_index', C.c_int), ('wscale', C.c_float), ('s', C.c_void_p), ('d', C.c_void_p)]
+
+
+class GfpganTail(C.Structure):
+    """struct sr_gfpgan_tail (include/sr_hip_gfpgan.h)."""
+    _fields_ = [('demod', C.c_void_p), ('noise', C.c_void_p), ('noise_img_stride', C.c_int64), ('noise_strength', C.c_float),
+                ('sft_scale', C.c_void_p), ('sft_scale_img_stride', C.c_int64), ('sft_shift', C.c_void_p),
+                ('sft_shift_img_stride', C.c_int64), ('sft_c0', C.c_int), ('s_next', C.c_void_p)]
+
+
+class GfpganModconvDesc(C.Structure):
+    """struct sr_gfpgan_modconv_desc (include/sr_hip_gfpgan.h)."""
+    _fields_ = [('base', ConvDesc), ('tail', GfpganTail)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_gfpgan.h declares
+GFPGAN_SIGNATURES = {
+    'sr_gfpgan_style_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(GfpganStyleLayer), C.c_int, C.c_int,
+                                      C.c_void_p]),
+    'sr_gfpgan_norm_style_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'sr_gfpgan_modconv_f32': (C.c_int, [C.POINTER(GfpganModconvDesc), C.c_void_p]),
+    'sr_gfpgan_upconv_f32': (C.c_int, [C.POINTER(GfpganModconvDesc), C.c_void_p]),
+    'sr_gfpgan_blur_up_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_float,
+                                        C.POINTER(GfpganTail), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'sr_gfpgan_torgb_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -339,7 +370,7 @@ def load():
         raise SrHipError(f'{LIB_PATH} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                          '(or `make -C image_restoration_amd/csrc`). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

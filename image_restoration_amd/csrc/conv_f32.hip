@@ -1020,5 +1020,10 @@ extern "C" const char* sr_kernel_name(int id) {
                                      "cb8_stream_kernelILb1E", "cb8_stream_kernelILb0E"};
     return rnames[id - 81];
   }
+  if (id >= 91 && id < 97) {  // gfpgan_ops.hip (include/sr_hip_gfpgan.h)
+    static const char* fnames[6] = {"gfp_style_kernel", "gfp_modconv_kernel", "gfp_upconv_kernel", "gfp_blur_up_kernel",
+                                    "gfp_torgb_kernel", "gfp_norm_kernel"};
+    return fnames[id - 91];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -829,3 +829,148 @@ def conv3x3_wgrad_bf16(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=Fa
     with torch.cuda.device(dev):
         _lib.check(lib.sr_conv3x3_wgrad_bf16(C.byref(d), _stream(dev)), 'sr_conv3x3_wgrad_bf16')
     return dw, db
+
+
+# ---- GFPGANv1OCR: style coefficients, modulated and upsampling convs, ToRGB (include/sr_hip_gfpgan.h) ----
+
+def bilinear2x(src, out=None):
+    """F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) on a CB8 window — sr_bilinear2x_fwd_f32."""
+    lib = _lib.load()
+    if out is None:
+        out = CB8.empty(src.n, src.channels, 2 * src.h, 2 * src.w, src.device)
+    assert (out.n, out.cbn, out.h, out.w) == (src.n, src.cbn, 2 * src.h, 2 * src.w)
+    with torch.cuda.device(src.device):
+        _lib.check(lib.sr_bilinear2x_fwd_f32(src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, src.cbn, src.h, src.w,
+                                             _stream(src.device)), 'sr_bilinear2x_fwd_f32')
+    return out
+
+
+def cb8_channel_scale(u, s, n, out=None):
+    """out[n] = u[n or 0] * s[n][c] (sr_ca_scale_f32): ``u`` with one image is repeated over the batch of ``n`` (image stride 0),
+    as the decoder's constant input."""
+    lib = _lib.load()
+    assert u.n in (1, n) and s.is_contiguous() and tuple(s.shape) == (n, u.channels)
+    if out is None:
+        out = CB8.empty(n, u.channels, u.h, u.w, u.device)
+    with torch.cuda.device(u.device):
+        _lib.check(lib.sr_ca_scale_f32(u.ptr, 0 if u.n == 1 else u.img_stride, s.data_ptr(), out.ptr, out.img_stride, n, u.channels,
+                                       u.h, u.w, _stream(u.device)), 'sr_ca_scale_f32')
+    return out
+
+
+def gfpgan_tail(demod, noise=None, noise_strength=0.0, sft=None, sft_c0=0, s_next=None):
+    """struct sr_gfpgan_tail: ``demod`` [N, cout]; ``noise`` [1 or N, 1, H, W] (one map for the batch when its first dim is 1);
+    ``sft`` = (scale, shift) CB8 windows applied to channels >= ``sft_c0``; ``s_next`` [N, cout]."""
+    t = _lib.GfpganTail()
+    assert demod.is_contiguous() and demod.dtype == torch.float32
+    t.demod = demod.data_ptr()
+    if noise is not None:
+        assert noise.is_contiguous() and noise.dtype == torch.float32 and noise.dim() == 4 and noise.size(1) == 1
+        t.noise, t.noise_img_stride = noise.data_ptr(), (0 if noise.size(0) == 1 else noise[0].numel())
+        t.noise_strength = float(noise_strength)
+    if sft is not None:
+        sc, sh = sft
+        t.sft_scale, t.sft_scale_img_stride = sc.ptr, sc.img_stride
+        t.sft_shift, t.sft_shift_img_stride = sh.ptr, sh.img_stride
+        t.sft_c0 = int(sft_c0)
+    if s_next is not None:
+        assert s_next.is_contiguous() and tuple(s_next.shape) == tuple(demod.shape)
+        t.s_next = s_next.data_ptr()
+    return t
+
+
+def gfpgan_modconv(src, pc, tail, out=None, act_slope=0.2, alpha=2 ** 0.5):
+    """One StyleConv at the source's size — sr_gfpgan_modconv_f32.  ``src``: CB8 x * s[n]; ``pc``: PackedConvK (3x3) of the
+    shared weight with the StyleConv's activation bias; ``tail``: gfpgan_tail(...)."""
+    lib = _lib.load()
+    base, ret = _conv_desc_f32(src, pc, out, act_slope=act_slope, alpha=alpha)
+    d = _lib.GfpganModconvDesc()
+    d.base, d.tail = base, tail
+    with torch.cuda.device(src.device):
+        _lib.check(lib.sr_gfpgan_modconv_f32(C.byref(d), _stream(src.device)), 'sr_gfpgan_modconv_f32')
+    return ret
+
+
+def gfpgan_upconv(src, pc, out=None):
+    """conv_transpose2d(src, W^T, stride 2) as four output parities -> the raw CB8 map of (2h+1) x (2w+1) —
+    sr_gfpgan_upconv_f32."""
+    lib = _lib.load()
+    assert src.channels == pc.src_channels and pc.ksize == 3
+    if out is None:
+        out = CB8.empty(src.n, pc.cout, 2 * src.h + 1, 2 * src.w + 1, src.device)
+    assert (out.n, out.h, out.w) == (src.n, 2 * src.h + 1, 2 * src.w + 1) and out.channels >= pc.cout
+    d = _lib.GfpganModconvDesc()
+    b = d.base
+    b.in_, b.in_img_stride, b.cin_pad, b.in_h, b.in_w = src.ptr, src.img_stride, pc.src_channels, src.h, src.w
+    b.wpacked, b.cout, b.out, b.out_img_stride, b.n = pc.w.data_ptr(), pc.cout, out.ptr, out.img_stride, src.n
+    with torch.cuda.device(src.device):
+        _lib.check(lib.sr_gfpgan_upconv_f32(C.byref(d), _stream(src.device)), 'sr_gfpgan_upconv_f32')
+    return out
+
+
+def gfpgan_blur_up(t, bias, tail, out=None, act_slope=0.2, alpha=2 ** 0.5):
+    """The upsampling StyleConv's blur ([1,3,3,1]^2 / 64 * 4, pad 1) and tail: t (2h+1) x (2w+1) -> CB8 2h x 2w —
+    sr_gfpgan_blur_up_f32.  ``bias``: the activation bias [cout] (contiguous fp32)."""
+    lib = _lib.load()
+    h, w = (t.h - 1) // 2, (t.w - 1) // 2
+    assert t.h == 2 * h + 1 and t.w == 2 * w + 1 and bias.is_contiguous()
+    cout = bias.numel()
+    if out is None:
+        out = CB8.empty(t.n, cout, 2 * h, 2 * w, t.device)
+    assert (out.n, out.h, out.w) == (t.n, 2 * h, 2 * w) and out.channels == cout == t.channels
+    with torch.cuda.device(t.device):
+        _lib.check(lib.sr_gfpgan_blur_up_f32(t.ptr, t.img_stride, out.ptr, out.img_stride, bias.data_ptr(), act_slope, alpha,
+                                             C.byref(tail), t.n, cout, h, w, _stream(t.device)), 'sr_gfpgan_blur_up_f32')
+    return out
+
+
+def gfpgan_torgb(x, w, wscale, s, bias, skip=None, s_next=None):
+    """ToRGB of the decoder: y [N, 3, H, W] (NCHW) = modulated 1x1 (no demodulation) + bias + upfirdn2d(skip, up 2); with
+    ``s_next`` also x * s_next[n] (CB8), the next level's modulated input — sr_gfpgan_torgb_f32.  Returns (y, x_next or None)."""
+    lib = _lib.load()
+    n, c = x.n, x.channels
+    assert w.is_contiguous() and tuple(w.shape) == (3, c) and s.is_contiguous() and tuple(s.shape) == (n, c)
+    y = torch.empty((n, 3, x.h, x.w), dtype=torch.float32, device=x.device)
+    if skip is not None:
+        assert skip.is_contiguous() and tuple(skip.shape) == (n, 3, x.h // 2, x.w // 2)
+    xn = CB8.empty(n, c, x.h, x.w, x.device) if s_next is not None else None
+    with torch.cuda.device(x.device):
+        _lib.check(lib.sr_gfpgan_torgb_f32(x.ptr, x.img_stride, w.data_ptr(), float(wscale), s.data_ptr(), bias.data_ptr(),
+                                           skip.data_ptr() if skip is not None else None, y.data_ptr(),
+                                           xn.ptr if xn is not None else None, xn.img_stride if xn is not None else 0,
+                                           s_next.data_ptr() if s_next is not None else None, n, c, x.h, x.w,
+                                           _stream(x.device)), 'sr_gfpgan_torgb_f32')
+    return y, xn
+
+
+def gfpgan_style(latent, img_stride, row_stride, nsf, layers, n):
+    """Every layer's modulation s and demodulation d in one sr_gfpgan_style_f32 launch.  ``layers``: a ctypes array of
+    _lib.GfpganStyleLayer whose s / d pointers name the outputs."""
+    lib = _lib.load()
+    with torch.cuda.device(latent.device):
+        _lib.check(lib.sr_gfpgan_style_f32(latent.data_ptr(), img_stride, row_stride, nsf, layers, len(layers), n,
+                                           _stream(latent.device)), 'sr_gfpgan_style_f32')
+
+
+def gfpgan_norm_style(x, out=None):
+    """NormStyleCode on rows of a contiguous [N, nsf] tensor — sr_gfpgan_norm_style_f32."""
+    _need_cuda(x, 'gfpgan_norm_style')
+    lib = _lib.load()
+    assert x.is_contiguous() and x.dim() == 2 and x.dtype == torch.float32
+    out = torch.empty_like(x) if out is None else out
+    with torch.cuda.device(x.device):
+        _lib.check(lib.sr_gfpgan_norm_style_f32(x.data_ptr(), out.data_ptr(), x.size(0), x.size(1), _stream(x.device)),
+                   'sr_gfpgan_norm_style_f32')
+    return out
+
+
+def linear(x, w, b, act_slope=1.0, out=None):
+    """y = lrelu(x w^T + b, act_slope) on contiguous fp32 rows — sr_linear_fwd_f32."""
+    lib = _lib.load()
+    n, k = x.shape
+    assert x.is_contiguous() and w.is_contiguous() and w.shape[1] == k
+    y = torch.empty((n, w.shape[0]), dtype=torch.float32, device=x.device) if out is None else out
+    with torch.cuda.device(x.device):
+        _lib.check(lib.sr_linear_fwd_f32(x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), n, k,
+                                         w.shape[0], float(act_slope), _stream(x.device)), 'sr_linear_fwd_f32')
+    return y

@@ -1,16 +1,26 @@
-"""Single-image / folder super-resolution with an RRDBNet, MSRResNet or RCAN checkpoint, or denoising with a RIDNet one, on the
-HIP path.
+"""Single-image / folder super-resolution with an RRDBNet, MSRResNet or RCAN checkpoint, denoising with a RIDNet one, or licence-
+plate restoration with a GFPGANv1OCR one (the model the reference's inference.py:28-40 and its API scripts serve), on the HIP
+path.
 
-The reference's inference.py serves a different model (GFPGANv1OCR, inference.py:28-40); what this script keeps is
-its I/O convention: read BGR uint8, /255, BGR->RGB CHW float (img2tensor, img_util.py:9-35),
-network, clamp to [0,1], RGB->BGR HWC, *255 round (tensor2img, img_util.py:38-94 with min_max=(0,1) as
-sr_model.py:148).  Large frames go through the tiler (tiling.py).
+The SR / denoising archs keep the reference's I/O convention: read BGR uint8, /255, BGR->RGB CHW float
+(img2tensor, img_util.py:9-35), network, clamp to [0,1], RGB->BGR HWC, *255 round (tensor2img, img_util.py:38-94 with
+min_max=(0,1) as sr_model.py:148).  Large frames go through the tiler (tiling.py).
+
+GFPGANv1OCR (--arch GFPGANv1OCR, scale 1, fp32, no tiling): the image is resized bilinearly (align_corners=False, no antialias;
+exact cv2 parity is not claimed) to the network's input size, mapped to [-1, 1] (the training convention, mean / std 0.5; the
+reference's inference.py feeds [0, 1], a quirk not reproduced), restored with return_rgb=False, converted with
+tensor2img(min_max=(-1, 1)) and resized back to the input's size (inference.py:75).  The stored noise buffers are used, so the
+output is reproducible; --randomize_noise draws fresh noise per call as the reference's scripts do.  The defaults are the
+square product configuration of api_plate_oto.py / api1.py (256 x 256, num_style_feat 256, channel_multiplier 0.5, num_mlp 8,
+input_is_latent, different_w, sft_half).
 
     python -m image_restoration_amd.inference --input crop.png --output out.png --model_path net_g.pth \
         [--num_block 23 --num_feat 64 --tile 512 --tile_pad 16 --compute_dtype fp32|bf16 --niqe_params niqe_pris_params.npz]
     python -m image_restoration_amd.inference --arch MSRResNet --scale 3 --input crop.png --output out.png --model_path net_g.pth
     python -m image_restoration_amd.inference --arch RCAN --scale 4 --input crop.png --output out.png --model_path RCAN_BIX4-official.pth
     python -m image_restoration_amd.inference --arch RIDNet --input noisy.png --output clean.png --model_path RIDNet.pth
+    python -m image_restoration_amd.inference --arch GFPGANv1OCR --input plate.png --output restored.png --model_path net_g.pth \
+        [--input_width 256 --input_height 256 --num_style_feat 256 --channel_multiplier 0.5 --num_mlp 8 --randomize_noise]
     python -m torch.distributed.run --nproc-per-node 8 -m image_restoration_amd.inference --launcher pytorch --tile 512 ...
 """
 import argparse
@@ -19,6 +29,7 @@ import os
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from .archs import build_network
 from . import watchdog
@@ -47,6 +58,20 @@ def generator_options(args):
     RCAN: upscale 2/3/4/8, fp32 only, 20 blocks per group by default (the released checkpoints' layout); RIDNet: scale 1 (a
     denoiser), fp32 only, 4 EAMs by default, --num_feat = mid_channels."""
     arch = getattr(args, 'arch', 'RRDBNet')
+    if arch == 'GFPGANv1OCR':
+        if args.scale != 1:
+            raise ValueError(f'--arch GFPGANv1OCR restores at the input size: it takes --scale 1 only, not {args.scale}')
+        if getattr(args, 'compute_dtype', 'fp32') != 'fp32':
+            raise ValueError('--arch GFPGANv1OCR runs in fp32 only (no --compute_dtype bf16)')
+        if getattr(args, 'tile', 0):
+            raise ValueError('--arch GFPGANv1OCR restores the whole image at the network size: no --tile')
+        h, w = args.input_height, args.input_width
+        if h < 8 or h & (h - 1) or w < h or w % h:
+            raise ValueError(f'--arch GFPGANv1OCR needs --input_height a power of two >= 8 and --input_width a multiple of it, '
+                             f'got {w} x {h}')
+        return dict(type='GFPGANv1OCR', input_width=args.input_width, input_height=args.input_height,
+                    num_style_feat=args.num_style_feat, channel_multiplier=args.channel_multiplier, narrow=args.narrow,
+                    num_mlp=args.num_mlp, input_is_latent=True, different_w=True, sft_half=True)
     num_block = getattr(args, 'num_block', None)
     num_block = ARCH_DEFAULT_BLOCKS[arch] if num_block is None else num_block
     if arch == 'RIDNet':
@@ -100,6 +125,24 @@ def restore_tensor(net, img_bgr_u8, tile=0, tile_pad=16, scale=4, rank=0, world_
     return y
 
 
+def gfpgan_restore(net, img_bgr_u8, randomize_noise=False):
+    """uint8 BGR image -> uint8 BGR image of the same size through a GFPGANv1OCR: bilinear resize to the network's size, [0, 1] ->
+    [-1, 1], forward with return_rgb=False, tensor2img(min_max=(-1, 1)), bilinear resize back (module docstring)."""
+    h, w = img_bgr_u8.shape[:2]
+    x = img2tensor(img_bgr_u8.astype(np.float32) / 255., bgr2rgb=True, float32=True).unsqueeze(0)
+    if (h, w) != (net.input_height, net.input_width):
+        x = F.interpolate(x, size=(net.input_height, net.input_width), mode='bilinear', align_corners=False)
+    x = (x * 2 - 1).to(next(net.parameters()).device)
+    with torch.no_grad():
+        y, _ = watchdog.guarded(lambda: net(x, return_rgb=False, randomize_noise=randomize_noise), 'restore')
+    out = tensor2img(y, rgb2bgr=True, min_max=(-1, 1))
+    if out.shape[:2] != (h, w):
+        t = torch.from_numpy(out.astype(np.float32)).permute(2, 0, 1).unsqueeze(0)
+        t = F.interpolate(t, size=(h, w), mode='bilinear', align_corners=False)
+        out = np.ascontiguousarray(t[0].permute(1, 2, 0).round().clamp(0, 255).numpy().astype(np.uint8))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--input', required=True, help='image file or folder')
@@ -107,14 +150,22 @@ def main(argv=None):
     ap.add_argument('--model_path', default=None)
     ap.add_argument('--scale', type=int, default=None, help='default: 1 for RIDNet, 4 otherwise')
     ap.add_argument('--num_feat', type=int, default=64)
-    ap.add_argument('--arch', choices=('RRDBNet', 'MSRResNet', 'RCAN', 'RIDNet'), default='RRDBNet',
-                    help='generator: RRDBNet (ESRGAN; --scale 1/2/4), MSRResNet (--scale 2/3/4, fp32), RCAN (--scale 2/3/4/8, fp32) '
-                         'or the RIDNet denoiser (--scale 1, fp32)')
+    ap.add_argument('--arch', choices=('RRDBNet', 'MSRResNet', 'RCAN', 'RIDNet', 'GFPGANv1OCR'), default='RRDBNet',
+                    help='generator: RRDBNet (ESRGAN; --scale 1/2/4), MSRResNet (--scale 2/3/4, fp32), RCAN (--scale 2/3/4/8, fp32), '
+                         'the RIDNet denoiser (--scale 1, fp32) or the GFPGANv1OCR plate restorer (--scale 1, fp32, no --tile)')
     ap.add_argument('--num_block', type=int, default=None,
                     help='default: 23 for RRDBNet, 16 for MSRResNet, 20 (blocks per residual group) for RCAN, 4 (EAMs) for RIDNet')
     ap.add_argument('--num_group', type=int, default=10, help='RCAN: residual groups')
     ap.add_argument('--squeeze_factor', type=int, default=16, help='RCAN: channel-attention squeeze factor')
     ap.add_argument('--num_grow_ch', type=int, default=32)
+    ap.add_argument('--input_width', type=int, default=256, help='GFPGANv1OCR: network input width (a multiple of the height)')
+    ap.add_argument('--input_height', type=int, default=256, help='GFPGANv1OCR: network input height (a power of two >= 8)')
+    ap.add_argument('--num_style_feat', type=int, default=256, help='GFPGANv1OCR: style code width')
+    ap.add_argument('--channel_multiplier', type=float, default=0.5, help='GFPGANv1OCR: channel multiplier of the 64+ levels')
+    ap.add_argument('--narrow', type=float, default=1.0, help='GFPGANv1OCR: channel narrowing')
+    ap.add_argument('--num_mlp', type=int, default=8, help='GFPGANv1OCR: style MLP depth (8 in api1.py / api_plate_oto.py)')
+    ap.add_argument('--randomize_noise', action='store_true',
+                    help='GFPGANv1OCR: fresh noise per image (the reference scripts\' default) instead of the stored noise buffers')
     ap.add_argument('--tile', type=int, default=0,
                     help='split frames larger than this into tiles (0: whole image).  RCAN and RIDNet: their channel attention '
                          'pools over each tile, so a tiled output differs from the whole-image one (RIDNet\'s receptive field '
@@ -131,11 +182,13 @@ def main(argv=None):
                          'niqe_pris_params.npz, the pristine model')
     args = ap.parse_args(argv)
     if args.scale is None:
-        args.scale = 1 if args.arch == 'RIDNet' else 4
+        args.scale = 1 if args.arch in ('RIDNet', 'GFPGANv1OCR') else 4
     try:
         generator_options(args)
     except ValueError as e:
         ap.error(str(e))
+    if args.arch == 'GFPGANv1OCR' and (args.niqe_params or args.launcher != 'none'):
+        ap.error('--arch GFPGANv1OCR takes neither --niqe_params nor --launcher')
     rank, world = 0, 1
     if args.launcher == 'pytorch':
         from .utils.dist_util import get_dist_info, init_dist
@@ -148,6 +201,12 @@ def main(argv=None):
     net = load_generator(args, torch.device('cuda'))
     paths = sorted(glob.glob(os.path.join(args.input, '*'))) if os.path.isdir(args.input) else [args.input]
     for p in paths:
+        if args.arch == 'GFPGANv1OCR':
+            out = gfpgan_restore(net, imread_bgr(p), args.randomize_noise)
+            dst = os.path.join(args.output, os.path.basename(p)) if os.path.isdir(args.input) else args.output
+            imwrite_bgr(dst, out)
+            print(f'{p} -> {dst} {out.shape}')
+            continue
         y = restore_tensor(net, imread_bgr(p), args.tile, args.tile_pad, args.scale, rank, world)
         if y is None:
             continue

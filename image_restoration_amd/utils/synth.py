@@ -292,3 +292,37 @@ def ridnet_state_dict(seed=0, img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040),
             w, b = conv_params(rng, ws, rdb_style='.block1.' in wn, bias_scale=0.5 if ca else 0.05)
         sd[wn], sd[bn] = w.astype(np.float32), b
     return sd
+
+
+def gfpgan_param_shapes(**cfg):
+    """(name, shape) of every state_dict entry (parameters and the noise buffers, in state_dict order) of GFPGANv1OCR(**cfg),
+    read from the module built on the meta device (no memory, no kernels)."""
+    import torch
+    from ..archs.gfpganv1_ocr_arch import GFPGANv1OCR
+    with torch.device('meta'):
+        net = GFPGANv1OCR(**cfg)
+    return [(k, tuple(v.shape)) for k, v in net.state_dict().items()]
+
+
+def gfpgan_state_dict(seed=0, lr_mlp=0.01, **cfg):
+    """OrderedDict name -> np.float32 array for GFPGANv1OCR(**cfg): weights ~ N(0, 1) as initialised (the style MLP's / lr_mlp), the
+    noise buffers ~ N(0, 1), and — unlike the default initialisation, which zeroes the noise path and leaves the SFT scale at 1 —
+    noise strengths ~ U(0.05, 0.25), modulation and SFT-scale biases ~ 1 + U(+-0.2), every other bias ~ U(+-0.1)."""
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    for name, shape in gfpgan_param_shapes(lr_mlp=lr_mlp, **cfg):
+        leaf = name.rsplit('.', 1)[-1]
+        if '.noises.noise' in name:
+            v = rng.standard_normal(shape)
+        elif leaf == 'weight' and shape == (1,):
+            v = rng.uniform(0.05, 0.25, shape)
+        elif leaf == 'bias' and ('.modulation.' in name or (name.startswith('condition_scale.') and '.2.' in name)):
+            v = 1 + rng.uniform(-0.2, 0.2, shape)
+        elif leaf == 'bias':
+            v = rng.uniform(-0.1, 0.1, shape)
+        elif '.style_mlp.' in name:
+            v = rng.standard_normal(shape) / lr_mlp
+        else:
+            v = rng.standard_normal(shape)
+        sd[name] = np.asarray(v, np.float32)
+    return sd
