@@ -1,6 +1,7 @@
 """GFPGANv1OCR on the MI355X: every entry point of include/sr_hip_gfpgan.h against float64 on the CPU, the network against the
 reference's fixture (g_x_gfpgan, tools/make_golden_gfpgan.py) and against the float64 restatement (tests/gfpgan_restate.py) at the
-product configurations, random noise, checkpoints, the inference command line and determinism.
+product configurations at batch 2 and at the benchmark's batch 16, random noise, checkpoints, the inference command line and
+determinism.
 
 Bounds of the entry points are derived, in the conventions of tests/test_convd_ops_gpu.py.  EPS = 2^-24.  For every output
 element let A be the same operation on absolute values in float64 (|x s|, |W|, |d|, |noise|, |bias|, then sqrt(2) for the
@@ -301,22 +302,72 @@ def _product(cfg_hw, seed, cuda, n=2):
     return cfg, sd, x
 
 
+_PRODUCT_REF = {}
+
+
+def _product_ref(hw):
+    """(cfg, sd, x, r64, r32) of a product configuration at its two seeded images: the float64 and float32 CPU restatements are
+    computed once per module run and shared by the batch-2 and batch-16 tests."""
+    if hw not in _PRODUCT_REF:
+        cfg, sd, x = _product(hw, 900 + hw[1], None)
+        sd64 = {k: torch.from_numpy(v).double() for k, v in sd.items()}
+        sd32 = {k: torch.from_numpy(v) for k, v in sd.items()}
+        _PRODUCT_REF[hw] = (cfg, sd, x, R.forward(sd64, cfg, torch.from_numpy(x).double()), R.forward(sd32, cfg, torch.from_numpy(x)))
+    return _PRODUCT_REF[hw]
+
+
 @pytest.mark.parametrize('hw', [(256, 256), (256, 64)], ids=['256x256', '256x64'])
 def test_product_configs_match_the_float64_restatement(cuda, hw):
     """The product configurations at batch 2 with seeded weights: within 10x the float32 CPU restatement's distance from
     float64."""
-    cfg, sd, x = _product(hw, 900 + hw[1], cuda)
+    cfg, sd, x, r64, r32 = _product_ref(hw)
     net = _net(cfg, sd, cuda)
     img, rgbs = net(torch.from_numpy(x).to(cuda), randomize_noise=False)
-    sd64 = {k: torch.from_numpy(v).double() for k, v in sd.items()}
-    sd32 = {k: torch.from_numpy(v) for k, v in sd.items()}
-    r64 = R.forward(sd64, cfg, torch.from_numpy(x).double())
-    r32 = R.forward(sd32, cfg, torch.from_numpy(x))
     e32 = float((r32['image'].double() - r64['image']).abs().max())
     err = float((img.cpu().double() - r64['image']).abs().max())
     assert err < max(1e-5, 10 * e32), (err, e32)
     for a, b, c32 in zip(rgbs, r64['out_rgbs'], r32['out_rgbs']):
         assert float((a.cpu().double() - b).abs().max()) < max(1e-5, 10 * float((c32.double() - b).abs().max()))
+
+
+@pytest.mark.parametrize('hw', [(256, 256), (256, 64)], ids=['256x256', '256x64'])
+def test_product_configs_at_the_benchmarks_batch(cuda, hw):
+    """The product configurations at batch 16 (what the benchmark and inference.py at throughput run): the two seeded images
+    tiled eight times.  Every one of the 16 outputs and every out_rgbs level lies within the rule above of its source image's
+    float64 result (max over that image), and the eight replicas of an image are bit-identical.
+
+    Batch 16 runs other kernel instances than batch 2 (tests/test_gfpgan_plan_host.py::test_product_decoder_instances): at 256x256
+    nine of the thirteen decoder launches — the upsampling convs at 4, 8, 16, 32 and 64 rows (gfp_upconv_kernel<2,1> -> <2,2>, an
+    instance the square network never takes at batch 2) and the 3x3 convs at 16, 32, 64 and 128 rows (gfp_modconv_kernel<2,1> ->
+    <2,2>); at 256x64 the upsampling conv at 4 rows and the 3x3 conv at 16 rows.
+
+    Batch 16 equals batch 2 BIT FOR BIT, and this asserts it.  The decoder guarantees it (per output element every instance
+    accumulates in the order cin block, tap, MFMA k-slice: tests/test_gfpgan_ops_gpu.py).  So does the U-Net, from its dispatch:
+    sr_conv3x3_f32 chooses among tile shapes of one conv_tile_f32 body (8- or 4-row tiles, the 16- and 8-column tiles over the
+    stacked batch) whose chain per element is (cin block, tap, k-slice) in each; sr_conv4x4s2_f32 is four accumulating passes of
+    that body in a fixed order; sr_convd_f32 as the decoder; sr_linear_fwd_f32 runs one workgroup per (output, sample); the rest
+    (bilinear, axpby, pixel unshuffle, layout, channel scale, blur, ToRGB, style) is per element or per sample."""
+    cfg, sd, x, r64, r32 = _product_ref(hw)
+    net = _net(cfg, sd, cuda)
+    xd = torch.from_numpy(x).to(cuda)
+    img2, rgbs2 = net(xd, randomize_noise=False)
+    img, rgbs = net(xd.repeat(8, 1, 1, 1), randomize_noise=False)
+    assert img.shape[0] == 16 and len(rgbs) == len(r64['out_rgbs']) == len(rgbs2)
+    pairs = [(img, img2, r64['image'], r32['image'])] + list(zip(rgbs, rgbs2, r64['out_rgbs'], r32['out_rgbs']))
+    for lvl, (a, a2, b64, b32) in enumerate(pairs):
+        a = a.cpu()
+        tol = max(1e-5, 10 * float((b32.double() - b64).abs().max()))     # the rule of the batch-2 test, unchanged
+        for i in range(16):
+            err = float((a[i].double() - b64[i % 2]).abs().max())
+            assert err < tol, (lvl, i, err, tol)
+            assert torch.equal(a[i], a[i % 2]), (lvl, i)
+        assert torch.equal(a[:2], a2.cpu()), (lvl, float((a[:2] - a2.cpu()).abs().max()))
+        bad = a[:2].clone()
+        bad.view(-1).view(torch.int32)[-1] ^= 1            # negative controls: one flipped bit, one element off by twice the rule
+        assert not torch.equal(bad, a2.cpu())
+        bad = a[15].double().clone()
+        bad.view(-1)[0] += 2 * tol
+        assert not float((bad - b64[1]).abs().max()) < tol
 
 
 def test_random_noise_follows_the_documented_draws(cuda):

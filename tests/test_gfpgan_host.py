@@ -25,7 +25,7 @@ import gfpgan_restate as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'sr_hip_gfpgan.h')
-_GPU = 'tests/test_gfpgan_gpu.py::'
+_OPS = 'tests/test_gfpgan_ops_gpu.py::'
 
 # network_g of the reference's training_config/train_gfpgan_v4_*.yml (values copied; decoder_load_path is ~ in all four)
 _SQ = dict(type='GFPGANv1OCR', input_width=256, input_height=256, num_style_feat=256, channel_multiplier=0.5,
@@ -221,13 +221,14 @@ def test_inference_defaults_are_the_square_product_config():
 
 
 # ------------------------------------------------------------------------------------------ ledger of sr_hip_gfpgan.h
+# the strongest pin of each entry point: every kernel instance on its production dispatch path, at the edges of its contract
 PINNED = {
-    'sr_gfpgan_style_f32': _GPU + 'test_style_coefficients',
-    'sr_gfpgan_norm_style_f32': _GPU + 'test_norm_style',
-    'sr_gfpgan_modconv_f32': _GPU + 'test_modconv_forward',
-    'sr_gfpgan_upconv_f32': _GPU + 'test_upconv_blur_forward',
-    'sr_gfpgan_blur_up_f32': _GPU + 'test_upconv_blur_forward',
-    'sr_gfpgan_torgb_f32': _GPU + 'test_torgb',
+    'sr_gfpgan_style_f32': _OPS + 'test_style_shapes',
+    'sr_gfpgan_norm_style_f32': _OPS + 'test_norm_style_edges',
+    'sr_gfpgan_modconv_f32': _OPS + 'test_modconv_instances',
+    'sr_gfpgan_upconv_f32': _OPS + 'test_upconv_blur_instances',
+    'sr_gfpgan_blur_up_f32': _OPS + 'test_upconv_blur_instances',
+    'sr_gfpgan_torgb_f32': _OPS + 'test_torgb_edges',
 }
 
 
