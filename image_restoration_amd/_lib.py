@@ -1,4 +1,5 @@
-"""ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h and include/sr_hip_gfpgan.h).
+"""ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h and
+include/sr_hip_edsr.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -358,6 +359,17 @@ GFPGAN_SIGNATURES = {
                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/sr_hip_edsr.h declares
+EDSR_SIGNATURES = {
+    'sr_cb16_pixel_shuffle_bf16': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p]),
+    'sr_edsr_shift_in_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p]),
+    'sr_edsr_shift_in_bf16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p]),
+    'sr_edsr_shift_out_f32': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -370,7 +382,8 @@ def load():
         raise SrHipError(f'{LIB_PATH} is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                          '(or `make -C image_restoration_amd/csrc`). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
+            + list(EDSR_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1025,5 +1025,9 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "gfp_torgb_kernel", "gfp_norm_kernel"};
     return fnames[id - 91];
   }
+  if (id >= 98 && id < 101) {  // edsr_ops.hip (include/sr_hip_edsr.h); 97 stays unnamed
+    static const char* enames[3] = {"cb16_pixel_shuffle_kernel", "edsr_shift_in_kernel", "edsr_shift_out_kernel"};
+    return enames[id - 98];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

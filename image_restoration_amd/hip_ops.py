@@ -831,6 +831,50 @@ def conv3x3_wgrad_bf16(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=Fa
     return dw, db
 
 
+# ---- EDSR: the bf16 pixel shuffle and the image shifts at both ends (include/sr_hip_edsr.h) ----
+
+def pixel_shuffle_bf16(src, channels, r, out=None):
+    """nn.PixelShuffle(r) on CB16 (r in {2, 3}): ``src`` holds r*r*channels real channels -> CB16 of ``channels`` at r x the
+    size — sr_cb16_pixel_shuffle_bf16."""
+    lib = _lib.load()
+    assert src.channels >= channels * r * r
+    if out is None:
+        out = CB16.empty(src.n, channels, src.h * r, src.w * r, src.device)
+    assert (out.n, out.h, out.w) == (src.n, src.h * r, src.w * r) and out.channels >= channels
+    with torch.cuda.device(src.device):
+        _lib.check(lib.sr_cb16_pixel_shuffle_bf16(src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, src.h, src.w,
+                                                  r, _stream(src.device)), 'sr_cb16_pixel_shuffle_bf16')
+    return out
+
+
+def edsr_shift_in(x, mean, img_range, bf16=False):
+    """(x - mean[c]) * img_range of an NCHW fp32 image [N, 3, H, W] into a one-block CB8 (fp32) or CB16 (bf16) tensor, pad
+    channels zero — sr_edsr_shift_in_f32 / sr_edsr_shift_in_bf16.  ``mean``: three Python floats."""
+    _need_cuda(x, 'edsr_shift_in')
+    lib = _lib.load()
+    n, c, h, w = x.shape
+    assert c == 3 and x.is_contiguous() and x.dtype == torch.float32 and len(mean) == 3
+    out = (CB16 if bf16 else CB8).empty(n, 3, h, w, x.device)
+    m = (C.c_float * 3)(*mean)
+    fn, name = (lib.sr_edsr_shift_in_bf16, 'sr_edsr_shift_in_bf16') if bf16 else (lib.sr_edsr_shift_in_f32, 'sr_edsr_shift_in_f32')
+    with torch.cuda.device(x.device):
+        _lib.check(fn(x.data_ptr(), out.ptr, out.img_stride, m, float(img_range), n, h, w, _stream(x.device)), name)
+    return out
+
+
+def edsr_shift_out(y, mean, img_range):
+    """y = y / img_range + mean[c] in place on an NCHW fp32 image [N, 3, H, W] — sr_edsr_shift_out_f32."""
+    _need_cuda(y, 'edsr_shift_out')
+    lib = _lib.load()
+    n, c, h, w = y.shape
+    assert c == 3 and y.is_contiguous() and y.dtype == torch.float32 and len(mean) == 3
+    m = (C.c_float * 3)(*mean)
+    with torch.cuda.device(y.device):
+        _lib.check(lib.sr_edsr_shift_out_f32(y.data_ptr(), m, float(img_range), n, h, w, _stream(y.device)),
+                   'sr_edsr_shift_out_f32')
+    return y
+
+
 # ---- GFPGANv1OCR: style coefficients, modulated and upsampling convs, ToRGB (include/sr_hip_gfpgan.h) ----
 
 def bilinear2x(src, out=None):

@@ -326,3 +326,38 @@ def gfpgan_state_dict(seed=0, lr_mlp=0.01, **cfg):
             v = rng.standard_normal(shape)
         sd[name] = np.asarray(v, np.float32)
     return sd
+
+
+def edsr_param_shapes(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4, **_):
+    """(name, shape) in state_dict order of EDSR (edsr_arch.py:44-48): upscale 2^n or 3."""
+    out = []
+
+    def conv(name, ci, co):
+        out.append((f'{name}.weight', (co, ci, 3, 3)))
+        out.append((f'{name}.bias', (co,)))
+
+    conv('conv_first', num_in_ch, num_feat)
+    for b in range(num_block):
+        conv(f'body.{b}.conv1', num_feat, num_feat)
+        conv(f'body.{b}.conv2', num_feat, num_feat)
+    conv('conv_after_body', num_feat, num_feat)
+    if upscale == 3:
+        conv('upsample.0', num_feat, 9 * num_feat)
+    else:
+        for k in range(int(round(math.log2(upscale)))):
+            conv(f'upsample.{2 * k}', num_feat, 4 * num_feat)
+    conv('conv_last', num_feat, num_out_ch)
+    return out
+
+
+def edsr_state_dict(seed=0, **cfg):
+    """OrderedDict name -> np.float32 array for EDSR(**cfg): every conv ~ U(+-1/sqrt(fan_in)) (the reference builds its blocks
+    with pytorch_init=True, so no conv is scaled down), small non-zero biases."""
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    shapes = edsr_param_shapes(**cfg)
+    for i in range(0, len(shapes), 2):
+        (wn, ws), (bn, _) = shapes[i], shapes[i + 1]
+        w, b = conv_params(rng, ws, rdb_style=False)
+        sd[wn], sd[bn] = w, b
+    return sd
