@@ -1,5 +1,5 @@
-"""ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h and
-include/sr_hip_edsr.h).
+"""ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h,
+include/sr_hip_edsr.h and include/sr_hip_ca_bf16.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -370,6 +370,15 @@ EDSR_SIGNATURES = {
     'sr_edsr_shift_out_f32': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/sr_hip_ca_bf16.h declares
+CA_BF16_SIGNATURES = {
+    'sr_ca_workspace_bytes_bf16': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'sr_ca_squeeze_bf16': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sr_ca_excite_bf16': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_float, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -383,7 +392,7 @@ def load():
                          '(or `make -C image_restoration_amd/csrc`). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
-            + list(EDSR_SIGNATURES.items()):
+            + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -16,6 +16,15 @@ per-layer launches:
     conv_last, / img_range + mean   sr_conv3x3_f32 storing NCHW, then sr_channel_affine_f32
 
 Training goes through one autograd function for the whole network (rcan_autograd.py).
+
+``compute_dtype='bf16'`` (forward only) keeps every activation in CB16 bf16 between the input shift and conv_last:
+
+    (x - mean) * img_range          sr_edsr_shift_in_bf16 (the same arithmetic; NCHW fp32 -> one CB16 block)
+    conv_first, rcab.0, rcab.2      sr_conv3x3_bf16 (act_slope 0 for the ReLU)
+    channel attention               sr_ca_squeeze_bf16 (fp32 pool + MLP on the fp32 parameters), sr_ca_excite_bf16
+    body.{g}.conv, conv_after_body  sr_conv3x3_bf16 with res1, beta1 = 1
+    upsample                        per stage sr_conv3x3_bf16, then sr_cb16_pixel_shuffle_bf16
+    conv_last, / img_range + mean   sr_conv3x3_bf16 storing fp32 NCHW, then sr_edsr_shift_out_f32 in place
 """
 import torch
 from torch import nn
@@ -93,20 +102,26 @@ def _upscale_stages(upscale):
 @ARCH_REGISTRY.register()
 class RCAN(nn.Module):
     """RCAN(num_in_ch, num_out_ch, num_feat=64, num_group=10, num_block=16, squeeze_factor=16, upscale=4, res_scale=1,
-    img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040)).
+    img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040)[, compute_dtype='fp32']).
 
     forward(x [N, 3, H, W] fp32 on a HIP device) -> [N, 3, upscale*H, upscale*W].  ValueError for: ``upscale`` not 2^n (n >= 1)
     or 3; ``num_feat`` not a positive multiple of 8 (CB8 activations) or above 512; ``num_feat // squeeze_factor < 1``;
     ``num_in_ch`` or ``num_out_ch`` other than 3 (the reference's mean only broadcasts over 3 channels); ``num_group`` or
-    ``num_block`` below 1.  fp32 only.
+    ``num_block`` below 1; a ``compute_dtype`` other than 'fp32' / 'bf16'.  ``compute_dtype='bf16'`` (this project's own key) needs
+    ``num_feat`` to be a multiple of 16 (CB16 activations) and is forward only (eval mode or no_grad): bf16 activations and
+    weight images rounded from the fp32 parameters, fp32 accumulation, epilogues, attention MLP and output.
     """
 
     def __init__(self, num_in_ch, num_out_ch, num_feat=64, num_group=10, num_block=16, squeeze_factor=16, upscale=4,
-                 res_scale=1, img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040)):
+                 res_scale=1, img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040), compute_dtype='fp32'):
         super().__init__()
+        if compute_dtype not in ('fp32', 'bf16'):
+            raise ValueError(f"compute dtype must be 'fp32' or 'bf16', got {compute_dtype!r}")
         self.stages = _upscale_stages(upscale)
         if not isinstance(num_feat, int) or num_feat <= 0 or num_feat % 8 or num_feat > 512:
             raise ValueError(f'RCAN needs num_feat to be a positive multiple of 8 up to 512 (CB8 activations), got {num_feat!r}')
+        if compute_dtype == 'bf16' and num_feat % 16:
+            raise ValueError(f'RCAN in bf16 needs num_feat to be a multiple of 16 (CB16 activations), got {num_feat!r}')
         if not isinstance(squeeze_factor, int) or squeeze_factor <= 0 or num_feat // squeeze_factor < 1:
             raise ValueError(f'RCAN needs num_feat // squeeze_factor >= 1, got {num_feat!r} // {squeeze_factor!r}')
         if num_in_ch != 3 or num_out_ch != 3:
@@ -119,6 +134,7 @@ class RCAN(nn.Module):
         self.num_in_ch, self.num_out_ch, self.num_feat = num_in_ch, num_out_ch, num_feat
         self.num_group, self.num_block, self.squeeze_factor = num_group, num_block, squeeze_factor
         self.res_scale = res_scale
+        self.compute_dtype = compute_dtype
         self.rgb_mean = tuple(float(v) for v in rgb_mean)
         self.mean = torch.Tensor(rgb_mean).view(1, 3, 1, 1)   # a plain attribute, as in the reference: not in the state_dict
 
@@ -153,18 +169,20 @@ class RCAN(nn.Module):
         """Call after parameter memory was written behind torch's version counters (fused Adam, EMA, a broadcast)."""
         self._pack_gen += 1
 
-    def packed(self, conv, mode=0):
-        """Weight image of ``conv`` (mode 0: forward, 1: data gradient), rebuilt when the parameter storage, its version,
-        the FlatAdam epoch of the parameter or this net's generation (invalidate_packed) changed."""
+    def packed(self, conv, mode=0, bf16=False):
+        """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter),
+        rebuilt when the parameter storage, its version, the FlatAdam epoch of the parameter or this net's generation
+        (invalidate_packed) changed."""
         w, b = conv.weight, conv.bias
         sig = (w.data_ptr(), w._version, getattr(w, '_sr_epoch', (0,))[0], b.data_ptr(), b._version, self._pack_gen)
-        key = (id(conv), mode)
+        key = (id(conv), mode, bf16)
         hit = self._packs.get(key)
         if hit is not None and hit[0] == sig:
             return hit[1]
         if w.dtype != torch.float32 or b.dtype != torch.float32:
             raise _lib.SrHipError('RCAN parameters must be fp32')
-        pc = hip_ops.PackedConv(w, b if mode == 0 else None, mode=mode)
+        cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv
+        pc = cls(w, b if mode == 0 else None, mode=mode)
         self._packs[key] = (sig, pc)
         return pc
 
@@ -238,6 +256,39 @@ class RCAN(nn.Module):
             y = self._channel_affine(y, af['out_a'], af['out_b'])
         return y, saved
 
+    def run_forward_bf16(self, x):
+        """The bf16 forward: CB16 activations on sr_conv3x3_bf16 with fp32 epilogues; the attention pools and gates in fp32
+        from the fp32 parameters and rounds x + res_scale * u * s once; conv_last stores fp32 NCHW."""
+        n, _, h, w = x.shape
+        s, nf = self.upscale, self.num_feat
+
+        def pk(conv):
+            return self.packed(conv, 0, True)
+
+        with torch.cuda.device(x.device):
+            xc = hip_ops.edsr_shift_in(x, self.rgb_mean, self.img_range, bf16=True)
+            x0 = feat = hip_ops.conv3x3_bf16(xc, pk(self.conv_first))
+            for grp, rcabs in self.blocks():
+                g_in = feat
+                for blk in rcabs:
+                    ca = blk.ca
+                    t = hip_ops.conv3x3_bf16(feat, pk(blk.conv1), act_slope=0.0)
+                    u = hip_ops.conv3x3_bf16(t, pk(blk.conv2))
+                    sv = hip_ops.ca_squeeze_bf16(u, ca.fc1.weight, ca.fc1.bias, ca.fc2.weight, ca.fc2.bias)
+                    # in place except where feat is still the group's input, which body.{g}.conv adds back
+                    feat = hip_ops.ca_excite_bf16(feat, u, sv, float(blk.res_scale), out=None if feat is g_in else feat)
+                    del t, u
+                feat = hip_ops.conv3x3_bf16(feat, pk(grp.conv), res1=g_in, beta1=1.0)
+            feat = hip_ops.conv3x3_bf16(feat, pk(self.conv_after_body), res1=x0, beta1=1.0)
+            for conv, r in self.ups():
+                u = hip_ops.conv3x3_bf16(feat, pk(conv))
+                feat = hip_ops.pixel_shuffle_bf16(u, nf, r)
+                del u
+            y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=x.device)
+            hip_ops.conv3x3_bf16(feat, pk(self.conv_last), out_nchw=y)
+            hip_ops.edsr_shift_out(y, self.rgb_mean, self.img_range)
+        return y
+
     def forward(self, x):
         if not x.is_cuda:
             raise _lib.SrHipError('RCAN.forward runs only on a HIP device (no CPU fallback): move the module '
@@ -245,7 +296,13 @@ class RCAN(nn.Module):
         if x.dim() != 4 or x.size(1) != self.num_in_ch:
             raise ValueError(f'expected [N, {self.num_in_ch}, H, W], got {tuple(x.shape)}')
         x = x.contiguous().float()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list())):
+        needs_graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list()))
+        if self.compute_dtype == 'bf16':
+            if needs_graph and self.training:
+                raise NotImplementedError("RCAN with compute_dtype='bf16' is forward only (eval mode or torch.no_grad()); "
+                                          "train with compute_dtype='fp32'")
+            return self.run_forward_bf16(x)
+        if needs_graph:
             from .rcan_autograd import rcan_apply
             return rcan_apply(self, x)
         return self.run_forward(x)[0]

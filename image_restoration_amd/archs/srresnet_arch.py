@@ -11,6 +11,10 @@ checkpoints drop in.  The modules only hold parameters; the network is a composi
     conv_last           sr_conv3x3_f32 storing NCHW, then sr_bilinear_up_f32 adds the bilinear base into that output
 
 Training goes through one autograd function for the whole network (srresnet_autograd.py).
+
+``compute_dtype='bf16'`` (forward only): sr_nchw_to_cb16_bf16 on the input, the same layer list on sr_conv3x3_bf16 and
+sr_cb16_pixel_shuffle_bf16 (CB16 bf16 activations), conv_last storing fp32 NCHW, and the same sr_bilinear_up_f32 adding the
+bilinear base of the fp32 input.
 """
 import torch
 from torch import nn
@@ -24,23 +28,35 @@ LRELU = 0.1
 
 @ARCH_REGISTRY.register()
 class MSRResNet(nn.Module):
-    """MSRResNet(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4).
+    """MSRResNet(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4[, compute_dtype='fp32']).
 
     forward(x [N, num_in_ch, H, W] fp32 on a HIP device) -> [N, num_out_ch, upscale*H, upscale*W].
     ``upscale`` must be 2, 3 or 4 (ValueError otherwise; the reference silently builds a net without upsampling).
     ``num_feat`` must be a positive multiple of 8: every activation lives in whole 8-channel CB8 blocks, so no pad
     channel ever sits between two layers.  num_in_ch == num_out_ch (the bilinear base is added to the output).
+    ``compute_dtype='bf16'`` (this project's own key; ValueError for anything but 'fp32' / 'bf16') needs ``num_feat`` to be a
+    multiple of 16 (CB16 activations) and ``num_out_ch`` >= 1 (sr_conv3x3_bf16's fp32 NCHW store guards every output channel,
+    so it takes any positive count), and is forward only (eval mode or no_grad): bf16 activations and weight images rounded
+    from the fp32 parameters, fp32 accumulation, epilogues and output.
     """
 
-    def __init__(self, num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4):
+    def __init__(self, num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4, compute_dtype='fp32'):
         super().__init__()
+        if compute_dtype not in ('fp32', 'bf16'):
+            raise ValueError(f"compute dtype must be 'fp32' or 'bf16', got {compute_dtype!r}")
         if upscale not in (2, 3, 4):
             raise ValueError(f'MSRResNet supports upscale 2, 3 and 4, got {upscale!r}')
         if not isinstance(num_feat, int) or num_feat <= 0 or num_feat % 8:
             raise ValueError(f'MSRResNet needs num_feat to be a positive multiple of 8 (CB8 activations), got {num_feat!r}')
         if num_block < 0:
             raise ValueError(f'num_block must be >= 0, got {num_block!r}')
+        if compute_dtype == 'bf16':
+            if num_feat % 16:
+                raise ValueError(f'MSRResNet in bf16 needs num_feat to be a multiple of 16 (CB16 activations), got {num_feat!r}')
+            if not isinstance(num_out_ch, int) or num_out_ch < 1 or not isinstance(num_in_ch, int) or num_in_ch < 1:
+                raise ValueError(f'MSRResNet in bf16 needs num_in_ch >= 1 and num_out_ch >= 1, got {num_in_ch!r}, {num_out_ch!r}')
         self.upscale = upscale
+        self.compute_dtype = compute_dtype
         self.num_in_ch, self.num_out_ch, self.num_feat, self.num_block = num_in_ch, num_out_ch, num_feat, num_block
 
         self.conv_first = Conv3x3Params(num_in_ch, num_feat)
@@ -80,18 +96,20 @@ class MSRResNet(nn.Module):
         """Call after parameter memory was written behind torch's version counters (fused Adam, EMA, a broadcast)."""
         self._pack_gen += 1
 
-    def packed(self, conv, mode=0):
-        """Weight image of ``conv`` (mode 0: forward, 1: data gradient), rebuilt when the parameter storage, its version,
-        the FlatAdam epoch of the parameter or this net's generation (invalidate_packed) changed."""
+    def packed(self, conv, mode=0, bf16=False):
+        """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter),
+        rebuilt when the parameter storage, its version, the FlatAdam epoch of the parameter or this net's generation
+        (invalidate_packed) changed."""
         w, b = conv.weight, conv.bias
         sig = (w.data_ptr(), w._version, getattr(w, '_sr_epoch', (0,))[0], b.data_ptr(), b._version, self._pack_gen)
-        key = (id(conv), mode)
+        key = (id(conv), mode, bf16)
         hit = self._packs.get(key)
         if hit is not None and hit[0] == sig:
             return hit[1]
         if w.dtype != torch.float32 or b.dtype != torch.float32:
             raise _lib.SrHipError('MSRResNet parameters must be fp32')
-        pc = hip_ops.PackedConv(w, b if mode == 0 else None, mode=mode)
+        cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv
+        pc = cls(w, b if mode == 0 else None, mode=mode)
         self._packs[key] = (sig, pc)
         return pc
 
@@ -131,6 +149,31 @@ class MSRResNet(nn.Module):
             hip_ops.bilinear_up(x, s, out=y)   # out += F.interpolate(x, scale_factor=s, mode='bilinear')
         return y, saved
 
+    def run_forward_bf16(self, x):
+        """The bf16 forward: the layer list of run_forward on CB16 activations, every epilogue in fp32; conv_last stores fp32
+        NCHW and the bilinear base of the fp32 input is added into it."""
+        n, _, h, w = x.shape
+        s, nf = self.upscale, self.num_feat
+
+        def pk(conv):
+            return self.packed(conv, 0, True)
+
+        with torch.cuda.device(x.device):
+            xc = hip_ops.nchw_to_cb16(x)
+            feat = hip_ops.conv3x3_bf16(xc, pk(self.conv_first), act_slope=LRELU)
+            for blk in self.body:
+                t = hip_ops.conv3x3_bf16(feat, pk(blk.conv1), act_slope=0.0)
+                feat = hip_ops.conv3x3_bf16(t, pk(blk.conv2), alpha=float(blk.res_scale), res1=feat, beta1=1.0)
+            for conv, r in self.ups():
+                u = hip_ops.conv3x3_bf16(feat, pk(conv), act_slope=LRELU)
+                feat = hip_ops.pixel_shuffle_bf16(u, nf, r)
+                del u
+            hr = hip_ops.conv3x3_bf16(feat, pk(self.conv_hr), act_slope=LRELU)
+            y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=x.device)
+            hip_ops.conv3x3_bf16(hr, pk(self.conv_last), out_nchw=y)
+            hip_ops.bilinear_up(x, s, out=y)   # out += F.interpolate(x, scale_factor=s, mode='bilinear') of the fp32 input
+        return y
+
     def forward(self, x):
         if not x.is_cuda:
             raise _lib.SrHipError('MSRResNet.forward runs only on a HIP device (no CPU fallback): move the module '
@@ -140,7 +183,13 @@ class MSRResNet(nn.Module):
         if self.num_in_ch != self.num_out_ch:
             raise ValueError('MSRResNet adds the bilinear upsampled input to its output: num_in_ch must equal num_out_ch')
         x = x.contiguous().float()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list())):
+        needs_graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list()))
+        if self.compute_dtype == 'bf16':
+            if needs_graph and self.training:
+                raise NotImplementedError("MSRResNet with compute_dtype='bf16' is forward only (eval mode or torch.no_grad()); "
+                                          "train with compute_dtype='fp32'")
+            return self.run_forward_bf16(x)
+        if needs_graph:
             from .srresnet_autograd import msrresnet_apply
             return msrresnet_apply(self, x)
         return self.run_forward(x)[0]

@@ -1029,5 +1029,9 @@ extern "C" const char* sr_kernel_name(int id) {
     static const char* enames[3] = {"cb16_pixel_shuffle_kernel", "edsr_shift_in_kernel", "edsr_shift_out_kernel"};
     return enames[id - 98];
   }
+  if (id >= 102 && id < 105) {  // channel_attention_bf16.hip (include/sr_hip_ca_bf16.h); 101 stays unnamed
+    static const char* anames[3] = {"attn16_pool_kernel", "attn16_finish_kernel", "attn16_excite_kernel"};
+    return anames[id - 102];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

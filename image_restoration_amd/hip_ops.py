@@ -875,6 +875,40 @@ def edsr_shift_out(y, mean, img_range):
     return y
 
 
+# ---- RCAN in bf16: channel attention on CB16 tensors (include/sr_hip_ca_bf16.h) ----
+
+def ca_squeeze_bf16(u, w1, b1, w2, b2):
+    """RCAN channel attention, the squeeze, on the CB16 tensor ``u`` (all its channels): s = sigmoid(W2 relu(W1 mean_hw u + b1)
+    + b2) in fp32 on the fp32 parameters as stored (W1 [hid, nf, 1, 1], W2 [nf, hid, 1, 1]).  Returns s [N, nf] fp32 —
+    sr_ca_squeeze_bf16."""
+    lib = _lib.load()
+    n, nf, hid = u.n, u.channels, w1.shape[0]
+    assert tuple(w1.shape[:2]) == (hid, nf) and tuple(w2.shape[:2]) == (nf, hid)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (w1, b1, w2, b2))
+    dev = u.device
+    s = torch.empty((n, nf), dtype=torch.float32, device=dev)
+    nbytes = lib.sr_ca_workspace_bytes_bf16(n, nf, hid, u.h, u.w)
+    ws = scratch(dev, nbytes, 'ca16')
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_ca_squeeze_bf16(u.ptr, u.img_stride, n, nf, u.h, u.w, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                                          b2.data_ptr(), hid, None, None, s.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)),
+                   'sr_ca_squeeze_bf16')
+    return s
+
+
+def ca_excite_bf16(x, u, s, res_scale=1.0, out=None):
+    """out = bf16(x + res_scale * (u * s[n][c])) on CB16, evaluated in fp32 and rounded once (out allocated if None; may be x)
+    — sr_ca_excite_bf16."""
+    lib = _lib.load()
+    if out is None:
+        out = CB16.empty(u.n, u.channels, u.h, u.w, u.device)
+    assert x.channels == u.channels == out.channels and s.is_contiguous() and s.dtype == torch.float32
+    with torch.cuda.device(u.device):
+        _lib.check(lib.sr_ca_excite_bf16(x.ptr, x.img_stride, u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n,
+                                         u.channels, u.h, u.w, float(res_scale), _stream(u.device)), 'sr_ca_excite_bf16')
+    return out
+
+
 # ---- GFPGANv1OCR: style coefficients, modulated and upsampling convs, ToRGB (include/sr_hip_gfpgan.h) ----
 
 def bilinear2x(src, out=None):
