@@ -1033,5 +1033,9 @@ extern "C" const char* sr_kernel_name(int id) {
     static const char* anames[3] = {"attn16_pool_kernel", "attn16_finish_kernel", "attn16_excite_kernel"};
     return anames[id - 102];
   }
+  if (id >= 106 && id < 109) {  // conv_wino_f32.hip: NW = 4, 2, 1; 105 stays unnamed
+    static const char* wino[3] = {"conv_wino_f32_kernelILi4E", "conv_wino_f32_kernelILi2E", "conv_wino_f32_kernelILi1E"};
+    return wino[id - 106];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

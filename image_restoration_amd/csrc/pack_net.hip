@@ -63,6 +63,33 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const sr::PackEntry* __
     }
     return;
   }
+  if (e.kind == 3) {  // Winograd F(2x2,3x3) image (conv_wino_f32.hip): one thread per (cout, cin), U = G g G^T in float64, rounded once
+    if constexpr (CB == 8) {
+      const int ci = (int)(i % e.cin), co = (int)(i / e.cin);
+      int pos = ci;
+      if (ci >= e.first_seg) {
+        const int r = ci - e.first_seg;
+        pos = rup(e.first_seg, CB) + (r / e.seg) * rup(e.seg, CB) + r % e.seg;
+      }
+      double gg[4][3];  // G g, G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double g0 = e.w[0][i * 9 + c], g1 = e.w[0][i * 9 + 3 + c], g2 = e.w[0][i * 9 + 6 + c];
+        gg[0][c] = g0;
+        gg[1][c] = 0.5 * ((g0 + g2) + g1);
+        gg[2][c] = 0.5 * ((g0 + g2) - g1);
+        gg[3][c] = g2;
+      }
+      const long long base = ((long long)(co / 32) * (e.cin_pad / CB) + pos / CB) * 16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double u[4] = {gg[r][0], 0.5 * ((gg[r][0] + gg[r][2]) + gg[r][1]), 0.5 * ((gg[r][0] + gg[r][2]) - gg[r][1]), gg[r][2]};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out[((base + r * 4 + c) * 32 + co % 32) * CB + pos % CB] = cvt<T>((float)u[c]);
+      }
+    }
+    return;
+  }
   const long long nw = (long long)e.cout * e.cin * 9;
   if (i >= nw) {  // kind 0: packed bias (fp32, zero-padded)
     const int j = (int)(i - nw);
@@ -103,6 +130,8 @@ int pack_table_run(std::vector<PackEntry>& entries, void* blob, size_t image_byt
       long long total = 0;
       for (int k = 5; k > e.s; --k) total += (long long)(k == 5 ? e.nf : e.gc) * slice * 9;
       e.elems = total;
+    } else if (e.kind == 3) {
+      e.elems = (long long)e.cout * e.cin;
     } else {
       e.elems = (long long)e.cout * e.cin * 9 + (e.kind == 0 ? (long long)sr_conv3x3_packed_bias_floats(e.cout) : 0);
     }

@@ -29,13 +29,16 @@ struct ConvPlan {
   int cout, cin, first_seg, seg, cin_pad;
   size_t w_off, b_off;  // float offsets in the packed (forward) blob
   size_t dg_off;        // float offset in the packed data-gradient blob
+  size_t wino_off;      // float offset of the Winograd image in the packed (forward) blob; kNoWino = the conv has none
 };
+constexpr size_t kNoWino = ~(size_t)0;
 
 struct NetPlan {
   int nfp, gcp, cin0, cin0_pad, unshuffle;
   std::vector<ConvPlan> convs;  // state_dict order
   std::vector<size_t> rdb_dg;   // [rdb][step s = 0..4]: transposed-dense-block images in the data-gradient blob
   size_t packed_floats, dgrad_floats;
+  size_t pack_entries;  // rows of the forward pack table: one per conv + one per Winograd image
 };
 
 int r8(int v) { return (v + 7) / 8 * 8; }
@@ -62,6 +65,7 @@ bool make_plan(const sr_rrdbnet_cfg* c, NetPlan* P) {
     cp.b_off = off;
     off += sr::align_up(sr_conv3x3_packed_bias_floats(cout), 64);
     cp.dg_off = dg;
+    cp.wino_off = kNoWino;
     dg += sr::align_up(sr_conv3x3_packed_weight_floats(cp.cin_pad, r8(cout)), 64);
     P->convs.push_back(cp);
   };
@@ -84,6 +88,16 @@ bool make_plan(const sr_rrdbnet_cfg* c, NetPlan* P) {
   add(nf, nf, nf, 0);             // conv_up2
   add(nf, nf, nf, 0);             // conv_hr
   add(c->num_out_ch, nf, nf, 0);  // conv_last
+  // Winograd F(2x2,3x3) images of the inference forward (conv_wino_f32.hip), behind the direct images, whose offsets stay: every
+  // conv but conv_first and conv_last, where the widths allow it
+  P->pack_entries = P->convs.size();
+  for (size_t i = 1; i + 1 < P->convs.size(); ++i) {
+    ConvPlan& cp = P->convs[i];
+    if (!sr::wino_f32_weights_eligible(cp.cout, cp.cin)) continue;
+    cp.wino_off = off;
+    off += sr::align_up(sr::wino_f32_image_floats(cp.cout, cp.cin_pad), 64);
+    ++P->pack_entries;
+  }
   P->packed_floats = off;
   P->dgrad_floats = dg;
   return true;
@@ -166,6 +180,16 @@ int forward_body(const sr_rrdbnet_cfg* cfg, const NetPlan& P, const FwdSpace& W,
   if (rc) return rc;
 
   size_t ci = 0;
+  // Inference: an eligible conv takes the Winograd kernel (conv_wino_f32.hip); the choice depends on the conv's widths and on the
+  // size of ONE image only.  Training, and everything not eligible, keeps the direct kernels.
+  const bool wino = !train && sr::wino_f32_mode() != 0;
+  auto run = [&](const sr_conv3x3_desc& d, const ConvPlan& cp) -> int {
+    if (wino && cp.wino_off != kNoWino) {
+      const int rc = sr::conv3x3_wino_f32(&d, packed + cp.wino_off, stream, false);
+      if (rc != SR_WINO_NOT_ELIGIBLE) return rc;
+    }
+    return sr_conv3x3_f32(&d, stream);
+  };
   auto conv = [&](const float* in, long long in_ns, int ih, int iw, int ups, float* out, long long out_ns, float slope,
                   float alpha, const float* r1, long long r1_ns, float b1, const float* r2, long long r2_ns, float b2,
                   int out_nchw) -> int {
@@ -193,7 +217,7 @@ int forward_body(const sr_rrdbnet_cfg* cfg, const NetPlan& P, const FwdSpace& W,
     d.res2 = r2;
     d.res2_img_stride = r2_ns;
     d.beta2 = b2;
-    return sr_conv3x3_f32(&d, stream);
+    return run(d, cp);
   };
   auto cat = [&](int q) { return W.cat[train ? q : (q & 3)]; };
 
@@ -257,7 +281,13 @@ int forward_body(const sr_rrdbnet_cfg* cfg, const NetPlan& P, const FwdSpace& W,
         d[4] = desc(buf, nxt, 1.f, 0.2f, buf, 1.f, nullptr, 0.f);
       else  // (x5*0.2 + x)*0.2 + x_rrdb (:39, :63)
         d[4] = desc(buf, nxt, 1.f, 0.04f, buf, 0.2f, x_rrdb, 1.f);
-      rc = sr_conv3x3_chain_f32(d, 5, sync, chain_call++, stream);
+      if (wino && P.convs[ci - 1].wino_off != kNoWino && P.convs[ci - 5].wino_off != kNoWino) {
+        // conv by conv; sr_set_conv_chain_f32 governs the direct kernels only
+        for (int k = 0; k < 5 && !rc; ++k) rc = run(d[k], P.convs[ci - 5 + k]);
+        ++chain_call;
+      } else {
+        rc = sr_conv3x3_chain_f32(d, 5, sync, chain_call++, stream);
+      }
       if (rc) return rc;
     }
   }
@@ -373,7 +403,7 @@ extern "C" int sr_rrdbnet_num_params(const sr_rrdbnet_cfg* cfg) {
 extern "C" size_t sr_rrdbnet_packed_bytes(const sr_rrdbnet_cfg* cfg) {
   NetPlan P;
   if (!make_plan(cfg, &P)) return 0;
-  return P.packed_floats * sizeof(float) + sr::pack_table_bytes(P.convs.size());  // images + the pack table (pack_net.hip)
+  return P.packed_floats * sizeof(float) + sr::pack_table_bytes(P.pack_entries);  // images + the pack table (pack_net.hip)
 }
 
 extern "C" size_t sr_rrdbnet_packed_dgrad_bytes(const sr_rrdbnet_cfg* cfg) {
@@ -413,6 +443,16 @@ extern "C" int sr_rrdbnet_pack_f32(const sr_rrdbnet_cfg* cfg, const float* const
     e.first_seg = cp.first_seg;
     e.seg = cp.seg > 0 ? cp.seg : 1;
     e.cin_pad = cp.cin_pad;
+  }
+  for (size_t i = 0; i < P.convs.size(); ++i) {  // the Winograd images of the same weights
+    const ConvPlan& cp = P.convs[i];
+    if (cp.wino_off == kNoWino) continue;
+    sr::PackEntry e = tab[i];
+    e.kind = 3;
+    e.bias = nullptr;
+    e.bout = nullptr;
+    e.out = packed + cp.wino_off;
+    tab.push_back(e);
   }
   return sr::pack_table_run(tab, packed, P.packed_floats * sizeof(float), false, (hipStream_t)stream);
 }

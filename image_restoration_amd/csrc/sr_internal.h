@@ -49,7 +49,7 @@ struct PackEntry {
   const float* bias;  // kind 0
   void* out;          // image
   float* bout;        // kind 0: packed bias
-  int kind;           // 0 forward image + bias, 1 data-gradient image, 2 transposed-dense-block step
+  int kind;           // 0 forward image + bias, 1 data-gradient image, 2 transposed-dense-block step, 3 Winograd F(2x2,3x3) forward image
   int cout, cin, first_seg, seg, cin_pad;
   int nf, gc, s;
   float scale5;
@@ -57,6 +57,12 @@ struct PackEntry {
 };
 size_t pack_table_bytes(size_t entries);
 int pack_table_run(std::vector<PackEntry>& entries, void* blob, size_t image_bytes, bool bf16, hipStream_t stream);
+// conv_wino_f32.hip: Winograd F(2x2,3x3) twin of sr_conv3x3_f32 for the fp32 inference forward
+#define SR_WINO_NOT_ELIGIBLE 1  // conv3x3_wino_f32: nothing launched, the caller runs the direct kernels
+int wino_f32_mode();            // sr_dev_set_wino_f32 / SR_F32_WINOGRAD: 0 off, 1 on, 2.. on with a forced tile variant
+bool wino_f32_weights_eligible(int cout, int cin);
+size_t wino_f32_image_floats(int cout, int cin_pad);  // U[cout / 32][cin_pad / 8][16 points][32][8]
+int conv3x3_wino_f32(const sr_conv3x3_desc* d, const float* image, hipStream_t stream, bool any_size);
 // Device address of a 64-byte line of zeros (padding source of the LDS-DMA loaders).  Kernels take it as a parameter:
 // naming the __device__ symbol inside a loop makes hipcc re-load its address (s_getpc + s_load + wait) at every use.
 const void* zero_line();
