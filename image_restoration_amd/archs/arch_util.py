@@ -62,6 +62,16 @@ def make_layer(basic_block, num_basic_block, **kwarg):
     return nn.Sequential(*[basic_block(**kwarg) for _ in range(num_basic_block)])
 
 
+def upscale_stages(upscale):
+    """Pixel-shuffle factors of the reference's Upsample (arch_util.py:90-109): 2^n -> n stages of 2 (none for 1), 3 -> one
+    of 3; None for a scale it does not support (the caller raises in its own words)."""
+    if upscale == 3:
+        return [3]
+    if isinstance(upscale, int) and upscale >= 1 and upscale & (upscale - 1) == 0:
+        return [2] * (int(upscale).bit_length() - 1)
+    return None
+
+
 class ResidualBlockNoBN(nn.Module):
     """Parameters of ``x + res_scale * conv2(relu(conv1(x)))`` (reference arch_util.py:59-87): conv1 / conv2 are
     num_feat -> num_feat 3x3 convs with bias, initialised kaiming_normal * 0.1, bias 0 (``pytorch_init=False``) or like

@@ -13,14 +13,13 @@ The modules only hold parameters; the network is a composition of per-layer laun
 
 Training (fp32) goes through one autograd function for the whole network (edsr_autograd.py).
 """
-import math
-
 import torch
 from torch import nn
 
-from .. import _lib, hip_ops
+from .. import hip_ops
 from ..utils.registry import ARCH_REGISTRY
-from .arch_util import Conv3x3Params, ResidualBlockNoBN, make_layer
+from .arch_util import Conv3x3Params, ResidualBlockNoBN, make_layer, upscale_stages
+from .hip_generator import F32, HipGenerator, residual_block, upsample_stage
 
 
 class Upsample(nn.Sequential):
@@ -28,14 +27,12 @@ class Upsample(nn.Sequential):
     conv nf -> 9nf + PixelShuffle(3).  The PixelShuffle entries only keep the reference's ``upsample.{0,2,..}`` numbering."""
 
     def __init__(self, scale, num_feat):
-        m = []
-        if isinstance(scale, int) and scale >= 1 and (scale & (scale - 1)) == 0:
-            for _ in range(int(math.log2(scale))):
-                m += [Conv3x3Params(num_feat, 4 * num_feat), nn.PixelShuffle(2)]
-        elif scale == 3:
-            m += [Conv3x3Params(num_feat, 9 * num_feat), nn.PixelShuffle(3)]
-        else:
+        factors = upscale_stages(scale)
+        if factors is None:
             raise ValueError(f'scale {scale} is not supported. Supported scales: 2^n and 3.')
+        m = []
+        for r in factors:
+            m += [Conv3x3Params(num_feat, r * r * num_feat), nn.PixelShuffle(r)]
         super().__init__(*m)
 
     def stages(self):
@@ -48,7 +45,7 @@ class Upsample(nn.Sequential):
 
 
 @ARCH_REGISTRY.register()
-class EDSR(nn.Module):
+class EDSR(HipGenerator):
     """EDSR(num_in_ch, num_out_ch, num_feat=64, num_block=16, upscale=4, res_scale=1, img_range=255.,
     rgb_mean=(0.4488, 0.4371, 0.4040)[, compute_dtype='fp32']).
 
@@ -57,6 +54,8 @@ class EDSR(nn.Module):
     must be a positive multiple of 8 (fp32, CB8 activations) or of 16 (bf16, CB16), so that no pad channel sits between layers.
     ``compute_dtype='bf16'``: forward only (eval mode or no_grad): bf16 activations and weight images rounded from the fp32
     parameters, fp32 accumulation and epilogues, fp32 output."""
+
+    _in_channels = 3
 
     def __init__(self, num_in_ch, num_out_ch, num_feat=64, num_block=16, upscale=4, res_scale=1, img_range=255.,
                  rgb_mean=(0.4488, 0.4371, 0.4040), compute_dtype='fp32'):
@@ -86,118 +85,44 @@ class EDSR(nn.Module):
         self.conv_after_body = Conv3x3Params(num_feat, num_feat)
         self.upsample = Upsample(upscale, num_feat)
         self.conv_last = Conv3x3Params(num_feat, num_out_ch)
-        self._packs = {}
-        self._pack_gen = 0
-        self._grad_sink = None  # set by optim.FlatAdam: weight gradients are added straight into its arena
 
     # ------------------------------------------------------------------ HIP plumbing
     def ups(self):
         """(conv, r) of the upsampling stages, in forward order."""
         return self.upsample.stages()
 
-    def convs(self):
-        """Every conv in state_dict order."""
-        out = [self.conv_first]
-        for blk in self.body:
-            out += [blk.conv1, blk.conv2]
-        return out + [self.conv_after_body] + [c for c, _ in self.ups()] + [self.conv_last]
+    def _autograd_apply(self, x):
+        from .edsr_autograd import edsr_apply
+        return edsr_apply(self, x)
 
-    def _param_list(self):
-        """Parameters in state_dict order (weight, bias per conv)."""
-        return [t for c in self.convs() for t in (c.weight, c.bias)]
-
-    def invalidate_packed(self):
-        """Call after parameter memory was written behind torch's version counters (fused Adam, EMA, a broadcast)."""
-        self._pack_gen += 1
-
-    def packed(self, conv, mode=0, bf16=False):
-        """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter),
-        rebuilt when the parameter storage, its version, the FlatAdam epoch of the parameter or this net's generation
-        (invalidate_packed) changed."""
-        w, b = conv.weight, conv.bias
-        sig = (w.data_ptr(), w._version, getattr(w, '_sr_epoch', (0,))[0], b.data_ptr(), b._version, self._pack_gen)
-        key = (id(conv), mode, bf16)
-        hit = self._packs.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        if w.dtype != torch.float32 or b.dtype != torch.float32:
-            raise _lib.SrHipError('EDSR parameters must be fp32')
-        cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv
-        pc = cls(w, b if mode == 0 else None, mode=mode)
-        self._packs[key] = (sig, pc)
-        return pc
-
-    def _apply(self, fn, *args, **kwargs):
-        self._packs = {}
-        return super()._apply(fn, *args, **kwargs)
-
-    def run_forward(self, x, keep=False):
-        """The fp32 forward as per-layer launches on the current stream.  ``keep``: also return what the backward reads (CB8
+    def run_forward(self, x, keep=False, ops=F32):
+        """The forward as per-layer launches on the current stream, on CB8 fp32 (``F32``) or CB16 bf16 (``BF16``) activations
+        with every epilogue in fp32; conv_last stores fp32 NCHW.  ``keep`` (fp32 only): also return what the backward reads (CB8
         activations: the shifted input, conv_first output, per block the ReLU output and the block output, the trunk output,
         per upsampling stage the shuffled output)."""
+        assert not (keep and ops.bf16), 'the backward reads fp32 activations'
         n, _, h, w = x.shape
-        s, nf = self.upscale, self.num_feat
+        s = self.upscale
+
+        def pk(conv):
+            return self.packed(conv, 0, ops.bf16)
+
         with torch.cuda.device(x.device):
-            xc = hip_ops.edsr_shift_in(x, self._mean3, self.img_range)
-            feat0 = feat = hip_ops.conv3x3(xc, self.packed(self.conv_first))
+            xc = hip_ops.edsr_shift_in(x, self._mean3, self.img_range, bf16=ops.bf16)
+            feat0 = feat = ops.conv3x3(xc, pk(self.conv_first))
             saved = dict(x=xc, feat0=feat0, blocks=[], ups=[]) if keep else None
             for blk in self.body:
-                t = hip_ops.conv3x3(feat, self.packed(blk.conv1), act_slope=0.0)
-                feat = hip_ops.conv3x3(t, self.packed(blk.conv2), alpha=float(blk.res_scale), res1=feat, beta1=1.0)
+                t, feat = residual_block(self, feat, blk, ops)
                 if keep:
                     saved['blocks'].append((t, feat))
-            feat = hip_ops.conv3x3(feat, self.packed(self.conv_after_body), res1=feat0, beta1=1.0)
+            feat = ops.conv3x3(feat, pk(self.conv_after_body), res1=feat0, beta1=1.0)
             if keep:
                 saved['trunk'] = feat
             for conv, r in self.ups():
-                u = hip_ops.conv3x3(feat, self.packed(conv))
-                feat = hip_ops.pixel_shuffle(u, nf, r)
-                del u
+                feat = upsample_stage(self, feat, conv, r, ops)
                 if keep:
                     saved['ups'].append(feat)
             y = torch.empty((n, 3, h * s, w * s), dtype=torch.float32, device=x.device)
-            hip_ops.conv3x3(feat, self.packed(self.conv_last), out_nchw=y)
+            ops.conv3x3(feat, pk(self.conv_last), out_nchw=y)
             hip_ops.edsr_shift_out(y, self._mean3, self.img_range)
         return y, saved
-
-    def run_forward_bf16(self, x):
-        """The bf16 forward: CB16 activations on sr_conv3x3_bf16, every epilogue in fp32; conv_last stores fp32 NCHW."""
-        n, _, h, w = x.shape
-        s, nf = self.upscale, self.num_feat
-
-        def pk(conv):
-            return self.packed(conv, 0, True)
-
-        with torch.cuda.device(x.device):
-            xc = hip_ops.edsr_shift_in(x, self._mean3, self.img_range, bf16=True)
-            feat0 = feat = hip_ops.conv3x3_bf16(xc, pk(self.conv_first))
-            for blk in self.body:
-                t = hip_ops.conv3x3_bf16(feat, pk(blk.conv1), act_slope=0.0)
-                feat = hip_ops.conv3x3_bf16(t, pk(blk.conv2), alpha=float(blk.res_scale), res1=feat, beta1=1.0)
-            feat = hip_ops.conv3x3_bf16(feat, pk(self.conv_after_body), res1=feat0, beta1=1.0)
-            for conv, r in self.ups():
-                u = hip_ops.conv3x3_bf16(feat, pk(conv))
-                feat = hip_ops.pixel_shuffle_bf16(u, nf, r)
-                del u
-            y = torch.empty((n, 3, h * s, w * s), dtype=torch.float32, device=x.device)
-            hip_ops.conv3x3_bf16(feat, pk(self.conv_last), out_nchw=y)
-            hip_ops.edsr_shift_out(y, self._mean3, self.img_range)
-        return y
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise _lib.SrHipError('EDSR.forward runs only on a HIP device (no CPU fallback): move the module and input '
-                                  'with .to("cuda")')
-        if x.dim() != 4 or x.size(1) != 3:
-            raise ValueError(f'expected [N, 3, H, W], got {tuple(x.shape)}')
-        x = x.contiguous().float()
-        needs_graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list()))
-        if self.compute_dtype == 'bf16':
-            if needs_graph and self.training:
-                raise NotImplementedError("EDSR with compute_dtype='bf16' is forward only (eval mode or torch.no_grad()); "
-                                          "train with compute_dtype='fp32'")
-            return self.run_forward_bf16(x)
-        if needs_graph:
-            from .edsr_autograd import edsr_apply
-            return edsr_apply(self, x)
-        return self.run_forward(x)[0]

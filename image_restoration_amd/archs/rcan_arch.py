@@ -31,7 +31,8 @@ from torch import nn
 
 from .. import _lib, hip_ops
 from ..utils.registry import ARCH_REGISTRY
-from .arch_util import Conv3x3Params, make_layer
+from .arch_util import Conv3x3Params, make_layer, upscale_stages
+from .hip_generator import F32, HipGenerator, upsample_stage
 
 
 class ChannelAttentionParams(nn.Module):
@@ -89,18 +90,8 @@ class ResidualGroupParams(nn.Module):
         raise RuntimeError('ResidualGroupParams is a parameter container; RCAN launches the HIP kernels')
 
 
-def _upscale_stages(upscale):
-    """Pixel-shuffle factors of the reference's Upsample (arch_util.py Upsample): 2^n -> n stages of 2, 3 -> one of 3."""
-    if isinstance(upscale, int) and not isinstance(upscale, bool):
-        if upscale == 3:
-            return [3]
-        if upscale >= 2 and upscale & (upscale - 1) == 0:
-            return [2] * (upscale.bit_length() - 1)
-    raise ValueError(f'RCAN supports upscale 2^n (n >= 1) and 3, got {upscale!r}')
-
-
 @ARCH_REGISTRY.register()
-class RCAN(nn.Module):
+class RCAN(HipGenerator):
     """RCAN(num_in_ch, num_out_ch, num_feat=64, num_group=10, num_block=16, squeeze_factor=16, upscale=4, res_scale=1,
     img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040)[, compute_dtype='fp32']).
 
@@ -112,12 +103,16 @@ class RCAN(nn.Module):
     weight images rounded from the fp32 parameters, fp32 accumulation, epilogues, attention MLP and output.
     """
 
+    _in_channels = property(lambda self: self.num_in_ch)
+
     def __init__(self, num_in_ch, num_out_ch, num_feat=64, num_group=10, num_block=16, squeeze_factor=16, upscale=4,
                  res_scale=1, img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040), compute_dtype='fp32'):
         super().__init__()
         if compute_dtype not in ('fp32', 'bf16'):
             raise ValueError(f"compute dtype must be 'fp32' or 'bf16', got {compute_dtype!r}")
-        self.stages = _upscale_stages(upscale)
+        self.stages = upscale_stages(upscale) if isinstance(upscale, int) and not isinstance(upscale, bool) else None
+        if not self.stages:   # None, or no stage at all (upscale 1)
+            raise ValueError(f'RCAN supports upscale 2^n (n >= 1) and 3, got {upscale!r}')
         if not isinstance(num_feat, int) or num_feat <= 0 or num_feat % 8 or num_feat > 512:
             raise ValueError(f'RCAN needs num_feat to be a positive multiple of 8 up to 512 (CB8 activations), got {num_feat!r}')
         if compute_dtype == 'bf16' and num_feat % 16:
@@ -147,10 +142,7 @@ class RCAN(nn.Module):
             ups += [Conv3x3Params(num_feat, r * r * num_feat), nn.PixelShuffle(r)]
         self.upsample = nn.Sequential(*ups)
         self.conv_last = Conv3x3Params(num_feat, num_out_ch)
-        self._packs = {}
-        self._pack_gen = 0
         self._affine = {}
-        self._grad_sink = None  # set by optim.FlatAdam: weight gradients are added straight into its arena
 
     # ------------------------------------------------------------------ HIP plumbing
     def blocks(self):
@@ -161,35 +153,12 @@ class RCAN(nn.Module):
         """(conv, r) of the upsampling stages, in forward order."""
         return [(self.upsample[2 * i], r) for i, r in enumerate(self.stages)]
 
-    def _param_list(self):
-        """Parameters in state_dict (= named_parameters) order."""
-        return list(self.parameters())
-
-    def invalidate_packed(self):
-        """Call after parameter memory was written behind torch's version counters (fused Adam, EMA, a broadcast)."""
-        self._pack_gen += 1
-
-    def packed(self, conv, mode=0, bf16=False):
-        """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter),
-        rebuilt when the parameter storage, its version, the FlatAdam epoch of the parameter or this net's generation
-        (invalidate_packed) changed."""
-        w, b = conv.weight, conv.bias
-        sig = (w.data_ptr(), w._version, getattr(w, '_sr_epoch', (0,))[0], b.data_ptr(), b._version, self._pack_gen)
-        key = (id(conv), mode, bf16)
-        hit = self._packs.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        if w.dtype != torch.float32 or b.dtype != torch.float32:
-            raise _lib.SrHipError('RCAN parameters must be fp32')
-        cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv
-        pc = cls(w, b if mode == 0 else None, mode=mode)
-        self._packs[key] = (sig, pc)
-        return pc
-
-    def _apply(self, fn, *args, **kwargs):
-        self._packs = {}
+    def _drop_device_caches(self):
         self._affine = {}
-        return super()._apply(fn, *args, **kwargs)
+
+    def _autograd_apply(self, x):
+        from .rcan_autograd import rcan_apply
+        return rcan_apply(self, x)
 
     def affine(self, dev):
         """Per-channel (a, b) device constants of the mean shift: in (x * R - R*mean), out (y * (1/R) + mean), and their
@@ -212,97 +181,62 @@ class RCAN(nn.Module):
                                              h * w, hip_ops._stream(x.device)), 'sr_channel_affine_f32')
         return y
 
-    def run_forward(self, x, keep=False):
-        """The forward as per-layer launches on the current stream.  ``keep``: also return what the backward reads (the CB8
-        input, conv_first's output, per RCAB (conv 0 output t, conv 2 output u, p, h, s, block output), per group its input,
-        the body's output, the conv_after_body output and each shuffled upsampling output)."""
+    def run_forward(self, x, keep=False, ops=F32):
+        """The forward as per-layer launches on the current stream, on CB8 fp32 (``F32``) or CB16 bf16 (``BF16``) activations:
+        in bf16 every conv epilogue is fp32, the attention pools and gates in fp32 from the fp32 parameters and rounds
+        x + res_scale * u * s once, and conv_last stores fp32 NCHW.  ``keep`` (fp32 only): also return what the backward reads
+        (the CB8 input, conv_first's output, per RCAB (conv 0 output t, conv 2 output u, p, h, s, block output), per group its
+        input, the body's output, the conv_after_body output and each shuffled upsampling output)."""
+        assert not (keep and ops.bf16), 'the backward reads fp32 activations'
         n, _, h, w = x.shape
-        s, nf = self.upscale, self.num_feat
+        s = self.upscale
+
+        def pk(conv):
+            return self.packed(conv, 0, ops.bf16)
+
         with torch.cuda.device(x.device):
-            af = self.affine(x.device)
-            xc = hip_ops.nchw_to_cb8(self._channel_affine(x, af['in_a'], af['in_b']))
-            x0 = hip_ops.conv3x3(xc, self.packed(self.conv_first))
+            if ops.bf16:
+                xc = hip_ops.edsr_shift_in(x, self.rgb_mean, self.img_range, bf16=True)
+            else:   # x*R - R*mean: not the shift kernels' (x - mean)*R, whose rounding differs
+                af = self.affine(x.device)
+                xc = hip_ops.nchw_to_cb8(self._channel_affine(x, af['in_a'], af['in_b']))
+            x0 = feat = ops.conv3x3(xc, pk(self.conv_first))
             saved = dict(x=xc, x0=x0, groups=[], ups=[]) if keep else None
-            feat = x0
             for grp, rcabs in self.blocks():
                 g_in = feat
                 blocks = []
                 for blk in rcabs:
                     ca = blk.ca
-                    t = hip_ops.conv3x3(feat, self.packed(blk.conv1), act_slope=0.0)
-                    u = hip_ops.conv3x3(t, self.packed(blk.conv2))
-                    p, hb, sv = hip_ops.ca_squeeze(u, ca.fc1.weight, ca.fc1.bias, ca.fc2.weight, ca.fc2.bias)
-                    feat = hip_ops.ca_excite(feat, u, sv, float(blk.res_scale))
+                    mlp = (ca.fc1.weight, ca.fc1.bias, ca.fc2.weight, ca.fc2.bias)
+                    t = ops.conv3x3(feat, pk(blk.conv1), act_slope=0.0)
+                    u = ops.conv3x3(t, pk(blk.conv2))
+                    if ops.bf16:
+                        sv = hip_ops.ca_squeeze_bf16(u, *mlp)
+                        # in place except where feat is still the group's input, which body.{g}.conv adds back
+                        feat = hip_ops.ca_excite_bf16(feat, u, sv, float(blk.res_scale), out=None if feat is g_in else feat)
+                    else:
+                        p, hb, sv = hip_ops.ca_squeeze(u, *mlp)
+                        feat = hip_ops.ca_excite(feat, u, sv, float(blk.res_scale))
                     if keep:
                         blocks.append((t, u, p, hb, sv, feat))
                     else:
                         del t, u
-                feat = hip_ops.conv3x3(feat, self.packed(grp.conv), res1=g_in, beta1=1.0)
+                feat = ops.conv3x3(feat, pk(grp.conv), res1=g_in, beta1=1.0)
                 if keep:
                     saved['groups'].append((g_in, blocks))
             if keep:
                 saved['body'] = feat
-            feat = hip_ops.conv3x3(feat, self.packed(self.conv_after_body), res1=x0, beta1=1.0)
+            feat = ops.conv3x3(feat, pk(self.conv_after_body), res1=x0, beta1=1.0)
             if keep:
                 saved['res'] = feat
             for conv, r in self.ups():
-                u = hip_ops.conv3x3(feat, self.packed(conv))
-                feat = hip_ops.pixel_shuffle(u, nf, r)
-                del u
+                feat = upsample_stage(self, feat, conv, r, ops)
                 if keep:
                     saved['ups'].append(feat)
             y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=x.device)
-            hip_ops.conv3x3(feat, self.packed(self.conv_last), out_nchw=y)
-            y = self._channel_affine(y, af['out_a'], af['out_b'])
+            ops.conv3x3(feat, pk(self.conv_last), out_nchw=y)
+            if ops.bf16:
+                hip_ops.edsr_shift_out(y, self.rgb_mean, self.img_range)
+            else:
+                y = self._channel_affine(y, af['out_a'], af['out_b'])
         return y, saved
-
-    def run_forward_bf16(self, x):
-        """The bf16 forward: CB16 activations on sr_conv3x3_bf16 with fp32 epilogues; the attention pools and gates in fp32
-        from the fp32 parameters and rounds x + res_scale * u * s once; conv_last stores fp32 NCHW."""
-        n, _, h, w = x.shape
-        s, nf = self.upscale, self.num_feat
-
-        def pk(conv):
-            return self.packed(conv, 0, True)
-
-        with torch.cuda.device(x.device):
-            xc = hip_ops.edsr_shift_in(x, self.rgb_mean, self.img_range, bf16=True)
-            x0 = feat = hip_ops.conv3x3_bf16(xc, pk(self.conv_first))
-            for grp, rcabs in self.blocks():
-                g_in = feat
-                for blk in rcabs:
-                    ca = blk.ca
-                    t = hip_ops.conv3x3_bf16(feat, pk(blk.conv1), act_slope=0.0)
-                    u = hip_ops.conv3x3_bf16(t, pk(blk.conv2))
-                    sv = hip_ops.ca_squeeze_bf16(u, ca.fc1.weight, ca.fc1.bias, ca.fc2.weight, ca.fc2.bias)
-                    # in place except where feat is still the group's input, which body.{g}.conv adds back
-                    feat = hip_ops.ca_excite_bf16(feat, u, sv, float(blk.res_scale), out=None if feat is g_in else feat)
-                    del t, u
-                feat = hip_ops.conv3x3_bf16(feat, pk(grp.conv), res1=g_in, beta1=1.0)
-            feat = hip_ops.conv3x3_bf16(feat, pk(self.conv_after_body), res1=x0, beta1=1.0)
-            for conv, r in self.ups():
-                u = hip_ops.conv3x3_bf16(feat, pk(conv))
-                feat = hip_ops.pixel_shuffle_bf16(u, nf, r)
-                del u
-            y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=x.device)
-            hip_ops.conv3x3_bf16(feat, pk(self.conv_last), out_nchw=y)
-            hip_ops.edsr_shift_out(y, self.rgb_mean, self.img_range)
-        return y
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise _lib.SrHipError('RCAN.forward runs only on a HIP device (no CPU fallback): move the module '
-                                  'and input with .to("cuda")')
-        if x.dim() != 4 or x.size(1) != self.num_in_ch:
-            raise ValueError(f'expected [N, {self.num_in_ch}, H, W], got {tuple(x.shape)}')
-        x = x.contiguous().float()
-        needs_graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list()))
-        if self.compute_dtype == 'bf16':
-            if needs_graph and self.training:
-                raise NotImplementedError("RCAN with compute_dtype='bf16' is forward only (eval mode or torch.no_grad()); "
-                                          "train with compute_dtype='fp32'")
-            return self.run_forward_bf16(x)
-        if needs_graph:
-            from .rcan_autograd import rcan_apply
-            return rcan_apply(self, x)
-        return self.run_forward(x)[0]

@@ -10,113 +10,67 @@ backward -> per RCAB, last first: sr_ca_bwd_f32 (sum_hw g*u, the sigmoid / W2 / 
 This stands where the reference relies on autograd through nn.Conv2d / ReLU / AdaptiveAvgPool2d / Sigmoid / PixelShuffle
 (rcan_arch.py:8-135 under sr_model.py).  Parameter gradients are returned to autograd as ordinary tensors
 (``requires_grad_(False)`` toggling works), or, with an optim.FlatAdam arena attached (``net._grad_sink``), added straight into
-the arena.
+the arena (hip_generator.WholeNetFunction / GradRouter).
 """
-import torch
+from .. import hip_ops
+from .hip_generator import WholeNetFunction
 
-from .. import _lib, hip_ops
 
-
-class _RCANFunction(torch.autograd.Function):
-
-    @staticmethod
-    def forward(ctx, net, x, *params):
-        y, saved = net.run_forward(x, keep=True)
-        ctx.net, ctx.saved, ctx.params = net, saved, params
-        return y
+class _RCANFunction(WholeNetFunction):
 
     @staticmethod
-    def backward(ctx, dy):
-        net, sv, params = ctx.net, ctx.saved, ctx.params
-        dy = dy.contiguous().float()
-        dev = dy.device
-        need_x = ctx.needs_input_grad[1]
-        need_p = ctx.needs_input_grad[2:]
+    def run_backward(net, sv, dy, router, need_x):
         nf = net.num_feat
-        sink = getattr(net, '_grad_sink', None)
-        grads = [None] * len(params)
-        index = {id(p): i for i, p in enumerate(params)}
-        to_sink = sink is not None and any(need_p)
-        if to_sink and not all(need_p):
-            raise _lib.SrHipError('flat-arena mode needs every generator parameter to require grad')
-
-        def wgrad(conv, src, d):
-            """weight / bias gradient of a 3x3 conv from its source and its output gradient."""
-            iw, ib = index[id(conv.weight)], index[id(conv.bias)]
-            if to_sink:
-                hip_ops.conv3x3_wgrad(src, d, conv.out_channels, conv.in_channels, out=(sink.grad_ptrs[iw], sink.grad_ptrs[ib]))
-            elif need_p[iw] or need_p[ib]:
-                dw, db = hip_ops.conv3x3_wgrad(src, d, conv.out_channels, conv.in_channels)
-                grads[iw] = dw if need_p[iw] else None
-                grads[ib] = db if need_p[ib] else None
-
-        def ca_targets(ca):
-            """(dW1, db1, dW2, db2) destinations of a channel attention's parameters, and whether they accumulate."""
-            ps = (ca.fc1.weight, ca.fc1.bias, ca.fc2.weight, ca.fc2.bias)
-            idx = [index[id(p)] for p in ps]
-            if to_sink:
-                return tuple(sink.grad_ptrs[i] for i in idx), True
-            out = []
-            for p, i in zip(ps, idx):
-                if need_p[i]:
-                    grads[i] = torch.empty_like(p)
-                    out.append(grads[i].data_ptr())
-                else:
-                    out.append(None)
-            return tuple(out), False
-
-        with torch.cuda.device(dev):
-            af = net.affine(dev)
-            g = hip_ops.nchw_to_cb8(net._channel_affine(dy, af['out_a'], None))   # d(conv_last output) = dy / img_range
-            feat_last = sv['ups'][-1]
-            wgrad(net.conv_last, feat_last, g)
-            g = hip_ops.conv3x3(g, net.packed(net.conv_last, 1))
-            ups = net.ups()
-            for k in range(len(ups) - 1, -1, -1):
-                conv, r = ups[k]
-                g = hip_ops.pixel_unshuffle(g, nf, r)
-                src = sv['ups'][k - 1] if k > 0 else sv['res']
-                wgrad(conv, src, g)
-                g = hip_ops.conv3x3(g, net.packed(conv, 1))
-            g_res = g                                                   # dL/d(conv_after_body output + x0)
-            groups = net.blocks()
-            wgrad(net.conv_after_body, sv['body'], g_res)
-            g = hip_ops.conv3x3(g_res, net.packed(net.conv_after_body, 1))
-            for gi in range(len(groups) - 1, -1, -1):
-                grp, rcabs = groups[gi]
-                g_in, blocks = sv['groups'][gi]
-                g_grp = g                                               # dL/d(group output): also the group identity's gradient
-                wgrad(grp.conv, blocks[-1][5], g_grp)
-                g = hip_ops.conv3x3(g_grp, net.packed(grp.conv, 1))
-                for b in range(len(rcabs) - 1, -1, -1):
-                    blk = rcabs[b]
-                    t, u, p, hb, s, _ = blocks[b]
-                    f_in = blocks[b - 1][5] if b > 0 else g_in
-                    rs = float(blk.res_scale)
-                    ca = blk.ca
-                    targets, acc = ca_targets(ca)
-                    q = hip_ops.ca_bwd(g, u, rs, ca.fc1.weight, ca.fc2.weight, p, hb, s, grads=targets, accumulate=acc)
-                    du = hip_ops.ca_bwd_apply(g, s, q, rs)
-                    wgrad(blk.conv2, t, du)
-                    dt = hip_ops.conv3x3(du, net.packed(blk.conv2, 1), mask=t, mask_slope=0.0)
-                    del du
-                    wgrad(blk.conv1, f_in, dt)
-                    # d(block input) = conv 0's data gradient + the block identity (res1) [+ the group identity (res2)]
-                    if b > 0:
-                        g = hip_ops.conv3x3(dt, net.packed(blk.conv1, 1), res1=g, beta1=1.0)
-                    elif gi > 0:
-                        g = hip_ops.conv3x3(dt, net.packed(blk.conv1, 1), res1=g, beta1=1.0, res2=g_grp, beta2=1.0)
-                    else:   # group 0's input is conv_first's output, whose long skip to conv_after_body adds g_res as well
-                        g = hip_ops.conv3x3(dt, net.packed(blk.conv1, 1), out=g_res, accumulate=True, res1=g, beta1=1.0,
-                                            res2=g_grp, beta2=1.0)
-            wgrad(net.conv_first, sv['x'], g)
-            dx = None
-            if need_x:
-                dxs = hip_ops.cb8_to_nchw(hip_ops.conv3x3(g, net.packed(net.conv_first, 1)), net.num_in_ch)
-                dx = net._channel_affine(dxs, af['in_a'], None)          # d/dx of (x - mean) * img_range
-        ctx.saved = None
-        return (None, dx) + tuple(grads)
+        wgrad = router.wgrad
+        af = net.affine(dy.device)
+        g = hip_ops.nchw_to_cb8(net._channel_affine(dy, af['out_a'], None))   # d(conv_last output) = dy / img_range
+        feat_last = sv['ups'][-1]
+        wgrad(net.conv_last, feat_last, g)
+        g = hip_ops.conv3x3(g, net.packed(net.conv_last, 1))
+        ups = net.ups()
+        for k in range(len(ups) - 1, -1, -1):
+            conv, r = ups[k]
+            g = hip_ops.pixel_unshuffle(g, nf, r)
+            src = sv['ups'][k - 1] if k > 0 else sv['res']
+            wgrad(conv, src, g)
+            g = hip_ops.conv3x3(g, net.packed(conv, 1))
+        g_res = g                                                   # dL/d(conv_after_body output + x0)
+        groups = net.blocks()
+        wgrad(net.conv_after_body, sv['body'], g_res)
+        g = hip_ops.conv3x3(g_res, net.packed(net.conv_after_body, 1))
+        for gi in range(len(groups) - 1, -1, -1):
+            grp, rcabs = groups[gi]
+            g_in, blocks = sv['groups'][gi]
+            g_grp = g                                               # dL/d(group output): also the group identity's gradient
+            wgrad(grp.conv, blocks[-1][5], g_grp)
+            g = hip_ops.conv3x3(g_grp, net.packed(grp.conv, 1))
+            for b in range(len(rcabs) - 1, -1, -1):
+                blk = rcabs[b]
+                t, u, p, hb, s, _ = blocks[b]
+                f_in = blocks[b - 1][5] if b > 0 else g_in
+                rs = float(blk.res_scale)
+                ca = blk.ca
+                # (dW1, db1, dW2, db2) destinations of the channel attention's parameters, and whether they accumulate
+                targets, acc = router.targets((ca.fc1.weight, ca.fc1.bias, ca.fc2.weight, ca.fc2.bias))
+                q = hip_ops.ca_bwd(g, u, rs, ca.fc1.weight, ca.fc2.weight, p, hb, s, grads=targets, accumulate=acc)
+                du = hip_ops.ca_bwd_apply(g, s, q, rs)
+                wgrad(blk.conv2, t, du)
+                dt = hip_ops.conv3x3(du, net.packed(blk.conv2, 1), mask=t, mask_slope=0.0)
+                del du
+                wgrad(blk.conv1, f_in, dt)
+                # d(block input) = conv 0's data gradient + the block identity (res1) [+ the group identity (res2)]
+                if b > 0:
+                    g = hip_ops.conv3x3(dt, net.packed(blk.conv1, 1), res1=g, beta1=1.0)
+                elif gi > 0:
+                    g = hip_ops.conv3x3(dt, net.packed(blk.conv1, 1), res1=g, beta1=1.0, res2=g_grp, beta2=1.0)
+                else:   # group 0's input is conv_first's output, whose long skip to conv_after_body adds g_res as well
+                    g = hip_ops.conv3x3(dt, net.packed(blk.conv1, 1), out=g_res, accumulate=True, res1=g, beta1=1.0,
+                                        res2=g_grp, beta2=1.0)
+        wgrad(net.conv_first, sv['x'], g)
+        if not need_x:
+            return None
+        dxs = hip_ops.cb8_to_nchw(hip_ops.conv3x3(g, net.packed(net.conv_first, 1)), net.num_in_ch)
+        return net._channel_affine(dxs, af['in_a'], None)            # d/dx of (x - mean) * img_range
 
 
-def rcan_apply(net, x):
-    return _RCANFunction.apply(net, x, *net._param_list())
+rcan_apply = _RCANFunction.net_apply

@@ -26,9 +26,10 @@ Training goes through one autograd function for the whole network (ridnet_autogr
 import torch
 from torch import nn
 
-from .. import _lib, hip_ops
+from .. import hip_ops
 from ..utils.registry import ARCH_REGISTRY
 from .arch_util import Conv3x3Params, ResidualBlockNoBN, make_layer
+from .hip_generator import HipGenerator
 from .rcan_arch import ChannelAttentionParams
 
 
@@ -89,7 +90,7 @@ class EAMParams(nn.Module):
 
 
 @ARCH_REGISTRY.register()
-class RIDNet(nn.Module):
+class RIDNet(HipGenerator):
     """RIDNet(in_channels, mid_channels, out_channels, num_block=4, img_range=255., rgb_mean=(0.4488, 0.4371, 0.4040),
     rgb_std=(1.0, 1.0, 1.0)).
 
@@ -122,39 +123,13 @@ class RIDNet(nn.Module):
         self.head = Conv3x3Params(in_channels, mid_channels)
         self.body = make_layer(EAMParams, num_block, in_channels=mid_channels, mid_channels=mid_channels, out_channels=mid_channels)
         self.tail = Conv3x3Params(mid_channels, out_channels)
-        self._packs = {}
-        self._pack_gen = 0
-        self._grad_sink = None  # set by optim.FlatAdam: weight gradients are added straight into its arena
 
     # ------------------------------------------------------------------ HIP plumbing
-    def _param_list(self):
-        """Parameters in state_dict (= named_parameters) order."""
-        return list(self.parameters())
+    _in_channels = property(lambda self: self.in_channels)
 
-    def invalidate_packed(self):
-        """Call after parameter memory was written behind torch's version counters (fused Adam, EMA, a broadcast)."""
-        self._pack_gen += 1
-
-    def packed(self, conv, mode=0):
-        """Weight image of ``conv`` (mode 0: forward, 1: data gradient): sr_conv3x3_pack_f32 for 3x3 convs (every dilation),
-        sr_convk_pack_f32 for the 1x1; rebuilt when the parameter storage, its version, the FlatAdam epoch of the parameter or this
-        net's generation (invalidate_packed) changed."""
-        w, b = conv.weight, conv.bias
-        sig = (w.data_ptr(), w._version, getattr(w, '_sr_epoch', (0,))[0], b.data_ptr(), b._version, self._pack_gen)
-        key = (id(conv), mode)
-        hit = self._packs.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        if w.dtype != torch.float32 or b.dtype != torch.float32:
-            raise _lib.SrHipError('RIDNet parameters must be fp32')
-        bias = b if mode == 0 else None
-        pc = hip_ops.PackedConv(w, bias, mode=mode) if w.shape[2] == 3 else hip_ops.PackedConvK(w, bias, mode=mode)
-        self._packs[key] = (sig, pc)
-        return pc
-
-    def _apply(self, fn, *args, **kwargs):
-        self._packs = {}
-        return super()._apply(fn, *args, **kwargs)
+    def _autograd_apply(self, x):
+        from .ridnet_autograd import ridnet_apply
+        return ridnet_apply(self, x)
 
     def run_forward(self, x, keep=False):
         """The forward as per-layer launches on the current stream.  ``keep``: also return what the backward reads (the input,
@@ -193,15 +168,3 @@ class RIDNet(nn.Module):
                 saved['tail'] = tail
             y = hip_ops.ridnet_add_mean(x, tail, self.add_mean.weight, self.add_mean.bias)
         return y, saved
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise _lib.SrHipError('RIDNet.forward runs only on a HIP device (no CPU fallback): move the module '
-                                  'and input with .to("cuda")')
-        if x.dim() != 4 or x.size(1) != self.in_channels:
-            raise ValueError(f'expected [N, {self.in_channels}, H, W], got {tuple(x.shape)}')
-        x = x.contiguous().float()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list())):
-            from .ridnet_autograd import ridnet_apply
-            return ridnet_apply(self, x)
-        return self.run_forward(x)[0]

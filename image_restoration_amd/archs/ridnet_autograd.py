@@ -10,122 +10,71 @@ backward -> sr_ridnet_add_mean_bwd_f32 (add_mean's dW / db and the tail gradient
 
 This stands where the reference relies on autograd through nn.Conv2d / ReLU / cat / AdaptiveAvgPool2d / Sigmoid
 (ridnet_arch.py:8-180 under sr_model.py).  Parameter gradients go back to autograd as ordinary tensors (``requires_grad_(False)``
-toggling works) or, with an optim.FlatAdam arena attached (``net._grad_sink``), are added straight into the arena.
+toggling works) or, with an optim.FlatAdam arena attached (``net._grad_sink``), are added straight into the arena
+(hip_generator.WholeNetFunction / GradRouter).
 """
-import torch
+from .. import hip_ops
+from .hip_generator import WholeNetFunction
 
-from .. import _lib, hip_ops
 
-
-class _RIDNetFunction(torch.autograd.Function):
-
-    @staticmethod
-    def forward(ctx, net, x, *params):
-        y, saved = net.run_forward(x, keep=True)
-        ctx.net, ctx.saved, ctx.params = net, saved, params
-        return y
+class _RIDNetFunction(WholeNetFunction):
 
     @staticmethod
-    def backward(ctx, dy):
-        net, sv, params = ctx.net, ctx.saved, ctx.params
-        dy = dy.contiguous().float()
-        dev = dy.device
-        need_x = ctx.needs_input_grad[1]
-        need_p = ctx.needs_input_grad[2:]
+    def run_backward(net, sv, dy, router, need_x):
         mid = net.mid_channels
-        sink = getattr(net, '_grad_sink', None)
-        grads = [None] * len(params)
-        index = {id(p): i for i, p in enumerate(params)}
-        to_sink = sink is not None and any(need_p)
-        if to_sink and not all(need_p):
-            raise _lib.SrHipError('flat-arena mode needs every generator parameter to require grad')
-
-        def targets(ps):
-            """Device pointers (or None) the gradients of ``ps`` go to, and whether they accumulate (arena)."""
-            idx = [index[id(p)] for p in ps]
-            if to_sink:
-                return tuple(sink.grad_ptrs[i] for i in idx), True
-            out = []
-            for p, i in zip(ps, idx):
-                if need_p[i]:
-                    grads[i] = torch.empty_like(p)
-                    out.append(grads[i].data_ptr())
-                else:
-                    out.append(None)
-            return tuple(out), False
-
-        def wgrad(conv, src, d, dilation=None):
-            """weight / bias gradient of a conv from its source and its pre-activation output gradient: the dense 3x3 path of
-            sr_conv3x3_wgrad_f32, or sr_convd_wgrad_f32 for a dilated or 1x1 conv."""
-            iw, ib = index[id(conv.weight)], index[id(conv.bias)]
-            k = conv.weight.shape[2]
-            if not (to_sink or need_p[iw] or need_p[ib]):
-                return
-            out = (sink.grad_ptrs[iw], sink.grad_ptrs[ib]) if to_sink else None   # arena: added in place, nothing returned
-            if dilation is None and k == 3:
-                res = hip_ops.conv3x3_wgrad(src, d, conv.out_channels, conv.in_channels, out=out)
-            else:
-                res = hip_ops.convd_wgrad(src, d, conv.out_channels, conv.in_channels, k, dilation or 1, out=out)
-            if not to_sink:
-                grads[iw] = res[0] if need_p[iw] else None
-                grads[ib] = res[1] if need_p[ib] else None
-
-        with torch.cuda.device(dev):
-            (dwa, dba), acc = targets((net.add_mean.weight, net.add_mean.bias))
-            g_t = hip_ops.ridnet_add_mean_bwd(dy, sv['tail'], net.add_mean.weight, dwa, dba, acc)     # dL/d(tail output)
-            wgrad(net.tail, sv['feat'], g_t)
-            g = hip_ops.conv3x3(g_t, net.packed(net.tail, 1))                                          # dL/d(body output)
-            del g_t
-            eams = list(net.body)
-            for k in range(len(eams) - 1, -1, -1):
-                eam, e = eams[k], sv['eams'][k]
-                mg, b1p, b2p, ca = eam.merge, eam.block1, eam.block2, eam.ca
-                # channel attention out = b2 * s(b2); b2 = relu(conv1x1(u2) + b1)
-                (dw1, db1, dw2, db2), acc = targets((ca.fc1.weight, ca.fc1.bias, ca.fc2.weight, ca.fc2.bias))
-                q = hip_ops.ca_bwd(g, e['b2'], 1.0, ca.fc1.weight, ca.fc2.weight, e['p'], e['hb'], e['s'], grads=(dw1, db1, dw2, db2),
-                                   accumulate=acc)
-                g2 = hip_ops.ca_bwd_apply(g, e['s'], q, 1.0)
-                g2 = hip_ops.relu_mask(g2, e['b2'], out=g2)                      # dL/d(block2's pre-activation sum)
-                wgrad(b2p.body[4], e['u2'], g2)
-                gu2 = hip_ops.convd(g2, net.packed(b2p.body[4], 1), 1, mask=e['u2'], mask_slope=0.0)
-                wgrad(b2p.body[2], e['u1'], gu2)
-                gu1 = hip_ops.conv3x3(gu2, net.packed(b2p.body[2], 1), mask=e['u1'], mask_slope=0.0)
-                del gu2
-                wgrad(b2p.body[0], e['b1'], gu1)
-                # block1 output b1 = relu(conv2(t) + m) feeds block2's body and its identity
-                gb1 = hip_ops.conv3x3(gu1, net.packed(b2p.body[0], 1), res1=g2, beta1=1.0, mask=e['b1'], mask_slope=0.0)
-                del gu1, g2
-                wgrad(b1p.conv2, e['t'], gb1)
-                gt = hip_ops.conv3x3(gb1, net.packed(b1p.conv2, 1), mask=e['t'], mask_slope=0.0)
-                wgrad(b1p.conv1, e['m'], gt)
-                gm = hip_ops.conv3x3(gt, net.packed(b1p.conv1, 1), res1=gb1, beta1=1.0)   # dL/dm, m = relu(agg conv) + f_in
-                del gt, gb1
-                gagg = hip_ops.relu_mask(gm, e['agg'])
-                wgrad(mg.aggregation[0], e['cat'], gagg)
-                gcat = hip_ops.conv3x3(gagg, net.packed(mg.aggregation[0], 1), mask=e['cat'], mask_slope=0.0)
-                del gagg
-                g1b, g2b = gcat.slice(0, mid), gcat.slice(mid, mid)
-                wgrad(mg.dilation1[2], e['d1a'], g1b, dilation=2)
-                gd1a = hip_ops.convd(g1b, net.packed(mg.dilation1[2], 1), 2, mask=e['d1a'], mask_slope=0.0)
-                wgrad(mg.dilation2[2], e['d2a'], g2b, dilation=4)
-                gd2a = hip_ops.convd(g2b, net.packed(mg.dilation2[2], 1), 4, mask=e['d2a'], mask_slope=0.0)
-                del gcat, g1b, g2b
-                f_in = e['f_in']
-                wgrad(mg.dilation1[0], f_in, gd1a)
-                wgrad(mg.dilation2[0], f_in, gd2a, dilation=3)
-                # dL/d(EAM input) = identity (gm) + both branches; the first EAM's input is relu(head), masked here
-                g = hip_ops.conv3x3(gd1a, net.packed(mg.dilation1[0], 1), res1=gm, beta1=1.0)
-                hip_ops.convd(gd2a, net.packed(mg.dilation2[0], 1), 3, out=g, accumulate=True,
-                              mask=sv['head'] if k == 0 else None, mask_slope=0.0)
-                del gd1a, gd2a, gm
-            wgrad(net.head, sv['s'], g)
-            g_s = hip_ops.conv3x3(g, net.packed(net.head, 1))                                          # dL/d(sub_mean output)
-            (dws, dbs), acc = targets((net.sub_mean.weight, net.sub_mean.bias))
-            dx = hip_ops.ridnet_sub_mean_bwd(sv['x'], g_s, net.sub_mean.weight, dws, dbs, acc, want_dx=need_x,
-                                             dx_res=dy if need_x else None)
-        ctx.saved = None
-        return (None, dx) + tuple(grads)
+        wgrad, targets = router.wgrad, router.targets
+        (dwa, dba), acc = targets((net.add_mean.weight, net.add_mean.bias))
+        g_t = hip_ops.ridnet_add_mean_bwd(dy, sv['tail'], net.add_mean.weight, dwa, dba, acc)     # dL/d(tail output)
+        wgrad(net.tail, sv['feat'], g_t)
+        g = hip_ops.conv3x3(g_t, net.packed(net.tail, 1))                                          # dL/d(body output)
+        del g_t
+        eams = list(net.body)
+        for k in range(len(eams) - 1, -1, -1):
+            eam, e = eams[k], sv['eams'][k]
+            mg, b1p, b2p, ca = eam.merge, eam.block1, eam.block2, eam.ca
+            # channel attention out = b2 * s(b2); b2 = relu(conv1x1(u2) + b1)
+            (dw1, db1, dw2, db2), acc = targets((ca.fc1.weight, ca.fc1.bias, ca.fc2.weight, ca.fc2.bias))
+            q = hip_ops.ca_bwd(g, e['b2'], 1.0, ca.fc1.weight, ca.fc2.weight, e['p'], e['hb'], e['s'], grads=(dw1, db1, dw2, db2),
+                               accumulate=acc)
+            g2 = hip_ops.ca_bwd_apply(g, e['s'], q, 1.0)
+            g2 = hip_ops.relu_mask(g2, e['b2'], out=g2)                      # dL/d(block2's pre-activation sum)
+            wgrad(b2p.body[4], e['u2'], g2)
+            gu2 = hip_ops.convd(g2, net.packed(b2p.body[4], 1), 1, mask=e['u2'], mask_slope=0.0)
+            wgrad(b2p.body[2], e['u1'], gu2)
+            gu1 = hip_ops.conv3x3(gu2, net.packed(b2p.body[2], 1), mask=e['u1'], mask_slope=0.0)
+            del gu2
+            wgrad(b2p.body[0], e['b1'], gu1)
+            # block1 output b1 = relu(conv2(t) + m) feeds block2's body and its identity
+            gb1 = hip_ops.conv3x3(gu1, net.packed(b2p.body[0], 1), res1=g2, beta1=1.0, mask=e['b1'], mask_slope=0.0)
+            del gu1, g2
+            wgrad(b1p.conv2, e['t'], gb1)
+            gt = hip_ops.conv3x3(gb1, net.packed(b1p.conv2, 1), mask=e['t'], mask_slope=0.0)
+            wgrad(b1p.conv1, e['m'], gt)
+            gm = hip_ops.conv3x3(gt, net.packed(b1p.conv1, 1), res1=gb1, beta1=1.0)   # dL/dm, m = relu(agg conv) + f_in
+            del gt, gb1
+            gagg = hip_ops.relu_mask(gm, e['agg'])
+            wgrad(mg.aggregation[0], e['cat'], gagg)
+            gcat = hip_ops.conv3x3(gagg, net.packed(mg.aggregation[0], 1), mask=e['cat'], mask_slope=0.0)
+            del gagg
+            g1b, g2b = gcat.slice(0, mid), gcat.slice(mid, mid)
+            wgrad(mg.dilation1[2], e['d1a'], g1b, dilation=2)
+            gd1a = hip_ops.convd(g1b, net.packed(mg.dilation1[2], 1), 2, mask=e['d1a'], mask_slope=0.0)
+            wgrad(mg.dilation2[2], e['d2a'], g2b, dilation=4)
+            gd2a = hip_ops.convd(g2b, net.packed(mg.dilation2[2], 1), 4, mask=e['d2a'], mask_slope=0.0)
+            del gcat, g1b, g2b
+            f_in = e['f_in']
+            wgrad(mg.dilation1[0], f_in, gd1a)
+            wgrad(mg.dilation2[0], f_in, gd2a, dilation=3)
+            # dL/d(EAM input) = identity (gm) + both branches; the first EAM's input is relu(head), masked here
+            g = hip_ops.conv3x3(gd1a, net.packed(mg.dilation1[0], 1), res1=gm, beta1=1.0)
+            hip_ops.convd(gd2a, net.packed(mg.dilation2[0], 1), 3, out=g, accumulate=True,
+                          mask=sv['head'] if k == 0 else None, mask_slope=0.0)
+            del gd1a, gd2a, gm
+        wgrad(net.head, sv['s'], g)
+        g_s = hip_ops.conv3x3(g, net.packed(net.head, 1))                                          # dL/d(sub_mean output)
+        (dws, dbs), acc = targets((net.sub_mean.weight, net.sub_mean.bias))
+        return hip_ops.ridnet_sub_mean_bwd(sv['x'], g_s, net.sub_mean.weight, dws, dbs, acc, want_dx=need_x,
+                                           dx_res=dy if need_x else None)
 
 
-def ridnet_apply(net, x):
-    return _RIDNetFunction.apply(net, x, *net._param_list())
+ridnet_apply = _RIDNetFunction.net_apply

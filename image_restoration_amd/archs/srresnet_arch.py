@@ -17,17 +17,17 @@ sr_cb16_pixel_shuffle_bf16 (CB16 bf16 activations), conv_last storing fp32 NCHW,
 bilinear base of the fp32 input.
 """
 import torch
-from torch import nn
 
-from .. import _lib, hip_ops
+from .. import hip_ops
 from ..utils.registry import ARCH_REGISTRY
 from .arch_util import Conv3x3Params, ResidualBlockNoBN, default_init_weights, make_layer
+from .hip_generator import F32, HipGenerator, residual_block, upsample_stage
 
 LRELU = 0.1
 
 
 @ARCH_REGISTRY.register()
-class MSRResNet(nn.Module):
+class MSRResNet(HipGenerator):
     """MSRResNet(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=16, upscale=4[, compute_dtype='fp32']).
 
     forward(x [N, num_in_ch, H, W] fp32 on a HIP device) -> [N, num_out_ch, upscale*H, upscale*W].
@@ -72,124 +72,53 @@ class MSRResNet(nn.Module):
         default_init_weights([self.conv_first, self.upconv1, self.conv_hr, self.conv_last], 0.1)
         if upscale == 4:
             default_init_weights(self.upconv2, 0.1)
-        self._packs = {}
-        self._pack_gen = 0
-        self._grad_sink = None  # set by optim.FlatAdam: weight gradients are added straight into its arena
 
     # ------------------------------------------------------------------ HIP plumbing
     def ups(self):
         """(conv, r) of the upsampling stages, in forward order."""
         return [(self.upconv1, 2), (self.upconv2, 2)] if self.upscale == 4 else [(self.upconv1, self.upscale)]
 
-    def convs(self):
-        """Every conv in state_dict order."""
-        out = [self.conv_first]
-        for blk in self.body:
-            out += [blk.conv1, blk.conv2]
-        return out + [c for c, _ in self.ups()] + [self.conv_hr, self.conv_last]
+    _in_channels = property(lambda self: self.num_in_ch)
 
-    def _param_list(self):
-        """Parameters in state_dict order (weight, bias per conv)."""
-        return [t for c in self.convs() for t in (c.weight, c.bias)]
+    def _check_input(self, x):
+        if self.num_in_ch != self.num_out_ch:
+            raise ValueError('MSRResNet adds the bilinear upsampled input to its output: num_in_ch must equal num_out_ch')
 
-    def invalidate_packed(self):
-        """Call after parameter memory was written behind torch's version counters (fused Adam, EMA, a broadcast)."""
-        self._pack_gen += 1
+    def _autograd_apply(self, x):
+        from .srresnet_autograd import msrresnet_apply
+        return msrresnet_apply(self, x)
 
-    def packed(self, conv, mode=0, bf16=False):
-        """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter),
-        rebuilt when the parameter storage, its version, the FlatAdam epoch of the parameter or this net's generation
-        (invalidate_packed) changed."""
-        w, b = conv.weight, conv.bias
-        sig = (w.data_ptr(), w._version, getattr(w, '_sr_epoch', (0,))[0], b.data_ptr(), b._version, self._pack_gen)
-        key = (id(conv), mode, bf16)
-        hit = self._packs.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        if w.dtype != torch.float32 or b.dtype != torch.float32:
-            raise _lib.SrHipError('MSRResNet parameters must be fp32')
-        cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv
-        pc = cls(w, b if mode == 0 else None, mode=mode)
-        self._packs[key] = (sig, pc)
-        return pc
-
-    def _apply(self, fn, *args, **kwargs):
-        self._packs = {}
-        return super()._apply(fn, *args, **kwargs)
-
-    def run_forward(self, x, keep=False):
-        """The forward as per-layer launches on the current stream.  ``keep``: also return what the backward reads
-        (CB8 activations: input, conv_first output, per block the ReLU output and the block output, per upsampling stage
-        the shuffled output, conv_hr output)."""
+    def run_forward(self, x, keep=False, ops=F32):
+        """The forward as per-layer launches on the current stream, on CB8 fp32 (``F32``) or CB16 bf16 (``BF16``) activations
+        with every epilogue in fp32.  ``keep`` (fp32 only): also return what the backward reads (CB8 activations: input,
+        conv_first output, per block the ReLU output and the block output, per upsampling stage the shuffled output, conv_hr
+        output)."""
+        assert not (keep and ops.bf16), 'the backward reads fp32 activations'
         n, _, h, w = x.shape
-        s, nf = self.upscale, self.num_feat
+        s = self.upscale
+
+        def pk(conv):
+            return self.packed(conv, 0, ops.bf16)
+
         with torch.cuda.device(x.device):
-            xc = hip_ops.nchw_to_cb8(x)
-            feat = hip_ops.conv3x3(xc, self.packed(self.conv_first), act_slope=LRELU)
+            xc = ops.to_cb(x)
+            feat = ops.conv3x3(xc, pk(self.conv_first), act_slope=LRELU)
             saved = dict(x=xc, feat0=feat, blocks=[], ups=[]) if keep else None
             for blk in self.body:
-                t = hip_ops.conv3x3(feat, self.packed(blk.conv1), act_slope=0.0)
-                feat = hip_ops.conv3x3(t, self.packed(blk.conv2), alpha=float(blk.res_scale), res1=feat, beta1=1.0)
+                t, feat = residual_block(self, feat, blk, ops)
                 if keep:
                     saved['blocks'].append((t, feat))
             for conv, r in self.ups():
-                u = hip_ops.conv3x3(feat, self.packed(conv), act_slope=LRELU)
-                feat = hip_ops.pixel_shuffle(u, nf, r)
-                del u
+                feat = upsample_stage(self, feat, conv, r, ops, LRELU)
                 if keep:
                     saved['ups'].append(feat)
-            hr = hip_ops.conv3x3(feat, self.packed(self.conv_hr), act_slope=LRELU)
+            hr = ops.conv3x3(feat, pk(self.conv_hr), act_slope=LRELU)
             if keep:
                 saved['hr'] = hr
-            if self.num_out_ch <= 4:
+            if ops.bf16 or self.num_out_ch <= 4:   # sr_conv3x3_bf16's fp32 NCHW store takes any channel count
                 y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=x.device)
-                hip_ops.conv3x3(hr, self.packed(self.conv_last), out_nchw=y)
+                ops.conv3x3(hr, pk(self.conv_last), out_nchw=y)
             else:
-                y = hip_ops.cb8_to_nchw(hip_ops.conv3x3(hr, self.packed(self.conv_last)), self.num_out_ch)
-            hip_ops.bilinear_up(x, s, out=y)   # out += F.interpolate(x, scale_factor=s, mode='bilinear')
-        return y, saved
-
-    def run_forward_bf16(self, x):
-        """The bf16 forward: the layer list of run_forward on CB16 activations, every epilogue in fp32; conv_last stores fp32
-        NCHW and the bilinear base of the fp32 input is added into it."""
-        n, _, h, w = x.shape
-        s, nf = self.upscale, self.num_feat
-
-        def pk(conv):
-            return self.packed(conv, 0, True)
-
-        with torch.cuda.device(x.device):
-            xc = hip_ops.nchw_to_cb16(x)
-            feat = hip_ops.conv3x3_bf16(xc, pk(self.conv_first), act_slope=LRELU)
-            for blk in self.body:
-                t = hip_ops.conv3x3_bf16(feat, pk(blk.conv1), act_slope=0.0)
-                feat = hip_ops.conv3x3_bf16(t, pk(blk.conv2), alpha=float(blk.res_scale), res1=feat, beta1=1.0)
-            for conv, r in self.ups():
-                u = hip_ops.conv3x3_bf16(feat, pk(conv), act_slope=LRELU)
-                feat = hip_ops.pixel_shuffle_bf16(u, nf, r)
-                del u
-            hr = hip_ops.conv3x3_bf16(feat, pk(self.conv_hr), act_slope=LRELU)
-            y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=x.device)
-            hip_ops.conv3x3_bf16(hr, pk(self.conv_last), out_nchw=y)
+                y = hip_ops.cb8_to_nchw(ops.conv3x3(hr, pk(self.conv_last)), self.num_out_ch)
             hip_ops.bilinear_up(x, s, out=y)   # out += F.interpolate(x, scale_factor=s, mode='bilinear') of the fp32 input
-        return y
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise _lib.SrHipError('MSRResNet.forward runs only on a HIP device (no CPU fallback): move the module '
-                                  'and input with .to("cuda")')
-        if x.dim() != 4 or x.size(1) != self.num_in_ch:
-            raise ValueError(f'expected [N, {self.num_in_ch}, H, W], got {tuple(x.shape)}')
-        if self.num_in_ch != self.num_out_ch:
-            raise ValueError('MSRResNet adds the bilinear upsampled input to its output: num_in_ch must equal num_out_ch')
-        x = x.contiguous().float()
-        needs_graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._param_list()))
-        if self.compute_dtype == 'bf16':
-            if needs_graph and self.training:
-                raise NotImplementedError("MSRResNet with compute_dtype='bf16' is forward only (eval mode or torch.no_grad()); "
-                                          "train with compute_dtype='fp32'")
-            return self.run_forward_bf16(x)
-        if needs_graph:
-            from .srresnet_autograd import msrresnet_apply
-            return msrresnet_apply(self, x)
-        return self.run_forward(x)[0]
+        return y, saved
