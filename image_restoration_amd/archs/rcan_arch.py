@@ -29,7 +29,7 @@ Training goes through one autograd function for the whole network (rcan_autograd
 import torch
 from torch import nn
 
-from .. import _lib, hip_ops
+from .. import hip_ops
 from ..utils.registry import ARCH_REGISTRY
 from .arch_util import Conv3x3Params, make_layer, upscale_stages
 from .hip_generator import F32, HipGenerator, upsample_stage
@@ -174,11 +174,10 @@ class RCAN(HipGenerator):
         return hit
 
     def _channel_affine(self, x, a, b):
-        lib = _lib.load()
         n, c, h, w = x.shape
         y = torch.empty_like(x)
-        _lib.check(lib.sr_channel_affine_f32(x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr() if b is not None else None, n, c,
-                                             h * w, hip_ops._stream(x.device)), 'sr_channel_affine_f32')
+        hip_ops.launch('sr_channel_affine_f32', x.device, x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr() if b is not None else None,
+                       n, c, h * w)
         return y
 
     def run_forward(self, x, keep=False, ops=F32):

@@ -2,25 +2,37 @@
 
 Activations travel between these Functions as plain fp32 tensors shaped [N, C/8, H, W, 8]
 (the CB8 layout of include/sr_hip.h); every forward/backward below is libsr_hip.so launches
-only.  The generator does not use this file: it is one fused Function
+only, each made through hip_ops.launch.  The generator does not use this file: it is one fused Function
 (archs/rrdbnet_autograd.py).
-"""
-import ctypes as C
 
+BNLReLUFn, MaxPool2x2Fn and LReLUFn also serve bf16 CB16 tensors [N, C/16, H, W, 16] (hip_autograd_bf16 exports them under
+their ...Fn16 names): the body takes the entry point's suffix from the tensor's dtype and the block width from x.size(4).
+"""
 import torch
 
 from . import _lib
 from . import hip_ops as H
 
-scratch = H.scratch
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
 
 def _cb8(t):
     return H.CB8(t)
+
+
+def _window(t):
+    """The whole-tensor window of a channel-blocked activation, CB8 or CB16 by its block width."""
+    return (H.CB16 if t.size(4) == 16 else H.CB8)(t)
+
+
+def _sfx(t):
+    """Entry-point suffix of an activation's dtype."""
+    return '_bf16' if t.dtype == torch.bfloat16 else '_f32'
+
+
+def _lrelu_bwd(gy, y, slope):
+    """dz = gy * LeakyReLU'(slope) by the sign of the saved output ``y`` (contiguous, one dtype) — sr_lrelu_bwd_f32 / _bf16."""
+    dz = torch.empty_like(gy)
+    H.launch('sr_lrelu_bwd' + _sfx(gy), gy.device, gy.data_ptr(), y.data_ptr(), dz.data_ptr(), slope, gy.numel())
+    return dz
 
 
 class ToCB8(torch.autograd.Function):
@@ -33,7 +45,7 @@ class ToCB8(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return H.cb8_to_nchw(_cb8(g.contiguous()), ctx.c)
+        return H.cb_to_nchw(_window(g.contiguous()), ctx.c)
 
 
 class FromCB8(torch.autograd.Function):
@@ -79,16 +91,8 @@ class ConvFn(torch.autograd.Function):
         k = ctx.k
         cout, cin = weight.shape[:2]
         gy = gy.contiguous()
-        dev = gy.device
         # dL/d(pre-activation): LeakyReLU backward against the saved output
-        if y is not None:
-            lib = _lib.load()
-            dz = torch.empty_like(gy)
-            with torch.cuda.device(dev):
-                _lib.check(lib.sr_lrelu_bwd_f32(gy.data_ptr(), y.data_ptr(), dz.data_ptr(), ctx.act_slope, gy.numel(),
-                                                _stream(dev)), 'sr_lrelu_bwd_f32')
-        else:
-            dz = gy
+        dz = _lrelu_bwd(gy, y, ctx.act_slope) if y is not None else gy
         dzc, src = _cb8(dz), _cb8(x)
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         dx = dw = db = None
@@ -109,49 +113,43 @@ class ConvFn(torch.autograd.Function):
 
 
 class BNLReLUFn(torch.autograd.Function):
-    """nn.BatchNorm2d + LeakyReLU on CB8 (sr_bn_lrelu_fwd_f32 / sr_bn_lrelu_bwd_f32)."""
+    """nn.BatchNorm2d + LeakyReLU on CB8 or CB16 (sr_bn_lrelu_fwd_f32 / sr_bn_lrelu_bwd_f32, or their _bf16 twins); parameters,
+    statistics and running buffers fp32."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, train, momentum, eps, slope):
-        lib = _lib.load()
-        n, cb, h, w, _ = x.shape
+        x = x.contiguous()
+        n, cb, h, w, blk = x.shape
         c = gamma.numel()
         dev = x.device
         y = torch.empty_like(x)
         mean = torch.empty(c, dtype=torch.float32, device=dev)
         invstd = torch.empty(c, dtype=torch.float32, device=dev)
-        wsb = lib.sr_reduce_workspace_bytes(c)
-        ws = scratch(dev, wsb)
-        ns = cb * h * w * 8
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_bn_lrelu_fwd_f32(x.data_ptr(), ns, y.data_ptr(), ns, n, c, h, w, gamma.data_ptr(),
-                                               beta.data_ptr(), running_mean.data_ptr() if running_mean is not None else None,
-                                               running_var.data_ptr() if running_var is not None else None, int(train),
-                                               momentum, eps, slope, mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(),
-                                               wsb, _stream(dev)), 'sr_bn_lrelu_fwd_f32')
+        ws, wsb = H.reduce_ws(dev, c)
+        ns = cb * h * w * blk
+        H.launch('sr_bn_lrelu_fwd' + _sfx(x), dev, x.data_ptr(), ns, y.data_ptr(), ns, n, c, h, w, gamma.data_ptr(),
+                 beta.data_ptr(), running_mean.data_ptr() if running_mean is not None else None,
+                 running_var.data_ptr() if running_var is not None else None, int(train), momentum, eps, slope, mean.data_ptr(),
+                 invstd.data_ptr(), ws.data_ptr(), wsb)
         ctx.save_for_backward(x, y, gamma, mean, invstd)
         ctx.train, ctx.slope = bool(train), slope
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         x, y, gamma, mean, invstd = ctx.saved_tensors
-        n, cb, h, w, _ = x.shape
+        n, cb, h, w, blk = x.shape
         c = gamma.numel()
         dev = x.device
         gy = gy.contiguous()
         dx = torch.empty_like(x)
         dgamma = torch.empty_like(gamma)
         dbeta = torch.empty_like(gamma)
-        wsb = lib.sr_reduce_workspace_bytes(c)
-        ws = scratch(dev, wsb)
-        ns = cb * h * w * 8
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_bn_lrelu_bwd_f32(x.data_ptr(), ns, gy.data_ptr(), ns, y.data_ptr(), ns, dx.data_ptr(), ns, n, c,
-                                               h, w, gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(), int(ctx.train),
-                                               ctx.slope, dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), wsb,
-                                               _stream(dev)), 'sr_bn_lrelu_bwd_f32')
+        ws, wsb = H.reduce_ws(dev, c)
+        ns = cb * h * w * blk
+        H.launch('sr_bn_lrelu_bwd' + _sfx(x), dev, x.data_ptr(), ns, gy.data_ptr(), ns, y.data_ptr(), ns, dx.data_ptr(), ns, n, c,
+                 h, w, gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(), int(ctx.train), ctx.slope, dgamma.data_ptr(),
+                 dbeta.data_ptr(), ws.data_ptr(), wsb)
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -160,21 +158,18 @@ class LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, act_slope):
-        lib = _lib.load()
         x = x.contiguous()
         n, nin = x.shape
         nout = weight.size(0)
         y = torch.empty((n, nout), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_linear_fwd_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                             y.data_ptr(), n, nin, nout, act_slope, _stream(x.device)), 'sr_linear_fwd_f32')
+        H.launch('sr_linear_fwd_f32', x.device, x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
+                 y.data_ptr(), n, nin, nout, act_slope)
         ctx.save_for_backward(x, weight, y)
         ctx.act_slope, ctx.has_bias = act_slope, bias is not None
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         x, weight, y = ctx.saved_tensors
         n, nin = x.shape
         nout = weight.size(0)
@@ -186,11 +181,9 @@ class LinearFn(torch.autograd.Function):
         db = torch.empty(nout, dtype=torch.float32, device=dev) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         if db is not None and dw is None:
             dw = torch.empty_like(weight)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_linear_bwd_f32(x.data_ptr(), weight.data_ptr(), y.data_ptr(), gy.data_ptr(), n, nin, nout,
-                                             ctx.act_slope, dz.data_ptr(), dx.data_ptr() if dx is not None else None,
-                                             dw.data_ptr() if dw is not None else None,
-                                             db.data_ptr() if db is not None else None, _stream(dev)), 'sr_linear_bwd_f32')
+        H.launch('sr_linear_bwd_f32', dev, x.data_ptr(), weight.data_ptr(), y.data_ptr(), gy.data_ptr(), n, nin, nout,
+                 ctx.act_slope, dz.data_ptr(), dx.data_ptr() if dx is not None else None,
+                 dw.data_ptr() if dw is not None else None, db.data_ptr() if db is not None else None)
         return dx, (dw if ctx.needs_input_grad[1] else None), db, None
 
 
@@ -200,30 +193,25 @@ class L1LossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, weight):
-        lib = _lib.load()
         ctx.dtype = pred.dtype
         pred, target = pred.contiguous().float(), target.contiguous().float()
         dev = pred.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        wsb = lib.sr_reduce_workspace_bytes(8)
-        ws = scratch(dev, wsb)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_l1_loss_fwd_f32(pred.data_ptr(), target.data_ptr(), pred.numel(), weight, loss.data_ptr(),
-                                              ws.data_ptr(), wsb, _stream(dev)), 'sr_l1_loss_fwd_f32')
+        ws, wsb = H.reduce_ws(dev)
+        H.launch('sr_l1_loss_fwd_f32', dev, pred.data_ptr(), target.data_ptr(), pred.numel(), weight, loss.data_ptr(),
+                 ws.data_ptr(), wsb)
         ctx.save_for_backward(pred, target)
         ctx.weight = weight
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         pred, target = ctx.saved_tensors
         dev = pred.device
         g = g.contiguous().float()
         dp = torch.empty_like(pred)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_l1_loss_bwd_f32(pred.data_ptr(), target.data_ptr(), pred.numel(), ctx.weight, g.data_ptr(),
-                                              dp.data_ptr(), _stream(dev)), 'sr_l1_loss_bwd_f32')
+        H.launch('sr_l1_loss_bwd_f32', dev, pred.data_ptr(), target.data_ptr(), pred.numel(), ctx.weight, g.data_ptr(),
+                 dp.data_ptr())
         return dp.to(ctx.dtype), None, None
 
 
@@ -233,26 +221,22 @@ class GramFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        lib = _lib.load()
         x = x.contiguous().float()
         n, c, h, w = x.shape
         dev = x.device
         g = torch.empty((n, c, c), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_gram_fwd_f32(x.data_ptr(), n, c, h * w, 1.0 / (c * h * w), g.data_ptr(), _stream(dev)), 'sr_gram_fwd_f32')
+        H.launch('sr_gram_fwd_f32', dev, x.data_ptr(), n, c, h * w, 1.0 / (c * h * w), g.data_ptr())
         ctx.save_for_backward(x)
         return g
 
     @staticmethod
     def backward(ctx, dg):
-        lib = _lib.load()
         x, = ctx.saved_tensors
         n, c, h, w = x.shape
         dev = x.device
         dx = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_gram_bwd_f32(x.data_ptr(), dg.contiguous().float().data_ptr(), n, c, h * w, 1.0 / (c * h * w), dx.data_ptr(),
-                                           _stream(dev)), 'sr_gram_bwd_f32')
+        H.launch('sr_gram_bwd_f32', dev, x.data_ptr(), dg.contiguous().float().data_ptr(), n, c, h * w, 1.0 / (c * h * w),
+                 dx.data_ptr())
         return dx
 
 
@@ -262,31 +246,25 @@ class PixelLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, weight, kind, eps):
-        lib = _lib.load()
         ctx.dtype = pred.dtype
         pred, target = pred.contiguous().float(), target.contiguous().float()
         dev = pred.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        wsb = lib.sr_reduce_workspace_bytes(8)
-        ws = scratch(dev, wsb)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_pixel_loss_fwd_f32(pred.data_ptr(), target.data_ptr(), pred.numel(), kind, eps, weight,
-                                                 loss.data_ptr(), ws.data_ptr(), wsb, _stream(dev)), 'sr_pixel_loss_fwd_f32')
+        ws, wsb = H.reduce_ws(dev)
+        H.launch('sr_pixel_loss_fwd_f32', dev, pred.data_ptr(), target.data_ptr(), pred.numel(), kind, eps, weight,
+                 loss.data_ptr(), ws.data_ptr(), wsb)
         ctx.save_for_backward(pred, target)
         ctx.args = (weight, kind, eps)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         pred, target = ctx.saved_tensors
         weight, kind, eps = ctx.args
         dev = pred.device
         dp = torch.empty_like(pred)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_pixel_loss_bwd_f32(pred.data_ptr(), target.data_ptr(), pred.numel(), kind, eps, weight,
-                                                 g.contiguous().float().data_ptr(), dp.data_ptr(), _stream(dev)),
-                       'sr_pixel_loss_bwd_f32')
+        H.launch('sr_pixel_loss_bwd_f32', dev, pred.data_ptr(), target.data_ptr(), pred.numel(), kind, eps, weight,
+                 g.contiguous().float().data_ptr(), dp.data_ptr())
         return dp.to(ctx.dtype), None, None, None, None
 
 
@@ -295,29 +273,23 @@ class GanPointLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, kind, c, weight):
-        lib = _lib.load()
         ctx.dtype = x.dtype
         x = x.contiguous().float()
         dev = x.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        wsb = lib.sr_reduce_workspace_bytes(8)
-        ws = scratch(dev, wsb)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_gan_point_loss_fwd_f32(x.data_ptr(), x.numel(), kind, c, weight, loss.data_ptr(), ws.data_ptr(), wsb,
-                                                     _stream(dev)), 'sr_gan_point_loss_fwd_f32')
+        ws, wsb = H.reduce_ws(dev)
+        H.launch('sr_gan_point_loss_fwd_f32', dev, x.data_ptr(), x.numel(), kind, c, weight, loss.data_ptr(), ws.data_ptr(), wsb)
         ctx.save_for_backward(x)
         ctx.args = (kind, c, weight)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         (x,) = ctx.saved_tensors
         kind, c, weight = ctx.args
         dx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_gan_point_loss_bwd_f32(x.data_ptr(), x.numel(), kind, c, weight, g.contiguous().float().data_ptr(),
-                                                     dx.data_ptr(), _stream(x.device)), 'sr_gan_point_loss_bwd_f32')
+        H.launch('sr_gan_point_loss_bwd_f32', x.device, x.data_ptr(), x.numel(), kind, c, weight,
+                 g.contiguous().float().data_ptr(), dx.data_ptr())
         return dx.to(ctx.dtype), None, None, None
 
 
@@ -329,25 +301,19 @@ class BCELogitsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, other, target_is_real, weight):
-        lib = _lib.load()
         ctx.dtypes = (x.dtype, other.dtype if other is not None else None)
         x = x.contiguous().float()
         dev = x.device
-        wsb = lib.sr_reduce_workspace_bytes(8)
-        ws = scratch(dev, wsb)
+        ws, wsb = H.reduce_ws(dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         shift = dsum = None
-        with torch.cuda.device(dev):
-            if other is not None:
-                other = other.contiguous().float()
-                shift = torch.empty((), dtype=torch.float32, device=dev)
-                dsum = torch.empty((), dtype=torch.float32, device=dev)
-                _lib.check(lib.sr_mean_f32(other.data_ptr(), other.numel(), shift.data_ptr(), ws.data_ptr(), wsb, _stream(dev)),
-                           'sr_mean_f32')
-            _lib.check(lib.sr_bce_logits_fwd_f32(x.data_ptr(), shift.data_ptr() if shift is not None else None, x.numel(),
-                                                 int(target_is_real), weight, loss.data_ptr(),
-                                                 dsum.data_ptr() if dsum is not None else None, ws.data_ptr(), wsb,
-                                                 _stream(dev)), 'sr_bce_logits_fwd_f32')
+        if other is not None:
+            other = other.contiguous().float()
+            shift = torch.empty((), dtype=torch.float32, device=dev)
+            dsum = torch.empty((), dtype=torch.float32, device=dev)
+            H.launch('sr_mean_f32', dev, other.data_ptr(), other.numel(), shift.data_ptr(), ws.data_ptr(), wsb)
+        H.launch('sr_bce_logits_fwd_f32', dev, x.data_ptr(), shift.data_ptr() if shift is not None else None, x.numel(),
+                 int(target_is_real), weight, loss.data_ptr(), dsum.data_ptr() if dsum is not None else None, ws.data_ptr(), wsb)
         ctx.save_for_backward(x, shift, dsum)
         ctx.target_is_real, ctx.weight = bool(target_is_real), weight
         ctx.other_shape = tuple(other.shape) if other is not None else None
@@ -355,21 +321,18 @@ class BCELogitsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         x, shift, dsum = ctx.saved_tensors
         dev = x.device
         g = g.contiguous().float()
         dx = dother = None
-        with torch.cuda.device(dev):
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _lib.check(lib.sr_bce_logits_bwd_f32(x.data_ptr(), shift.data_ptr() if shift is not None else None,
-                                                     x.numel(), int(ctx.target_is_real), ctx.weight, g.data_ptr(),
-                                                     dx.data_ptr(), _stream(dev)), 'sr_bce_logits_bwd_f32')
-            if ctx.other_shape is not None and ctx.needs_input_grad[1]:
-                dother = torch.empty(ctx.other_shape, dtype=torch.float32, device=dev)
-                _lib.check(lib.sr_fill_scaled_f32(g.data_ptr(), dsum.data_ptr(), -1.0 / dother.numel(), dother.data_ptr(),
-                                                  dother.numel(), _stream(dev)), 'sr_fill_scaled_f32')
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            H.launch('sr_bce_logits_bwd_f32', dev, x.data_ptr(), shift.data_ptr() if shift is not None else None, x.numel(),
+                     int(ctx.target_is_real), ctx.weight, g.data_ptr(), dx.data_ptr())
+        if ctx.other_shape is not None and ctx.needs_input_grad[1]:
+            dother = torch.empty(ctx.other_shape, dtype=torch.float32, device=dev)
+            H.launch('sr_fill_scaled_f32', dev, g.data_ptr(), dsum.data_ptr(), -1.0 / dother.numel(), dother.data_ptr(),
+                     dother.numel())
         if dx is not None:
             dx = dx.to(ctx.dtypes[0])
         if dother is not None:
@@ -380,14 +343,11 @@ class BCELogitsFn(torch.autograd.Function):
 def mean(x):
     """torch.mean(x.detach()) as one HIP reduction (logging of out_d_real / out_d_fake, esrgan_model.py:77-78); fp32 result for
     any floating input."""
-    lib = _lib.load()
     x = x.detach().contiguous().float()
     dev = x.device
     out = torch.empty((), dtype=torch.float32, device=dev)
-    wsb = lib.sr_reduce_workspace_bytes(8)
-    ws = scratch(dev, wsb)
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_mean_f32(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), wsb, _stream(dev)), 'sr_mean_f32')
+    ws, wsb = H.reduce_ws(dev)
+    H.launch('sr_mean_f32', dev, x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), wsb)
     return out
 
 
@@ -396,24 +356,18 @@ class Bilinear2xFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        lib = _lib.load()
         n, cb, h, w, _ = x.shape
         y = torch.empty((n, cb, 2 * h, 2 * w, 8), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_bilinear2x_fwd_f32(x.data_ptr(), cb * h * w * 8, y.data_ptr(), cb * h * w * 32, n, cb, h, w,
-                                                 _stream(x.device)), 'sr_bilinear2x_fwd_f32')
+        H.launch('sr_bilinear2x_fwd_f32', x.device, x.data_ptr(), cb * h * w * 8, y.data_ptr(), cb * h * w * 32, n, cb, h, w)
         ctx.shape = (n, cb, h, w)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         n, cb, h, w = ctx.shape
         g = g.contiguous()
         gx = torch.empty((n, cb, h, w, 8), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.check(lib.sr_bilinear2x_bwd_f32(g.data_ptr(), cb * h * w * 32, gx.data_ptr(), cb * h * w * 8, n, cb, h, w,
-                                                 _stream(g.device)), 'sr_bilinear2x_bwd_f32')
+        H.launch('sr_bilinear2x_bwd_f32', g.device, g.data_ptr(), cb * h * w * 32, gx.data_ptr(), cb * h * w * 8, n, cb, h, w)
         return gx
 
 
@@ -422,16 +376,27 @@ class AddFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b):
-        lib = _lib.load()
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty_like(a)
-        with torch.cuda.device(a.device):
-            _lib.check(lib.sr_add_f32(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _stream(a.device)), 'sr_add_f32')
+        H.launch('sr_add_f32', a.device, a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel())
         return out
 
     @staticmethod
     def backward(ctx, g):
         return g, g
+
+
+def _sn_bwd(g, w_sn, u, v, sigma_ptr, rows, cols):
+    """Gradient of one spectrally normalised weight w.r.t. weight_orig, given this forward's u, v and sigma —
+    sr_spectral_norm_bwd_f32."""
+    dev = g.device
+    g = g.contiguous()
+    gw = torch.empty_like(g)
+    wsb = max((rows + cols) * 4, _lib.load().sr_reduce_workspace_bytes(8) + 64)
+    ws = H.scratch(dev, wsb)
+    H.launch('sr_spectral_norm_bwd_f32', dev, g.data_ptr(), w_sn.data_ptr(), u.data_ptr(), v.data_ptr(), sigma_ptr, rows, cols,
+             gw.data_ptr(), ws.data_ptr(), wsb)
+    return gw
 
 
 class SpectralNormFn(torch.autograd.Function):
@@ -448,30 +413,17 @@ class SpectralNormFn(torch.autograd.Function):
         w_sn = torch.empty_like(w)
         sigma = torch.empty((), dtype=torch.float32, device=dev)
         wsb = max((rows + 16 * cols) * 4, lib.sr_reduce_workspace_bytes(8) + 64)
-        ws = scratch(dev, wsb)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_spectral_norm_fwd_f32(w.data_ptr(), u.data_ptr(), v.data_ptr(), rows, cols, int(update), eps,
-                                                    w_sn.data_ptr(), sigma.data_ptr(), ws.data_ptr(), wsb, _stream(dev)),
-                       'sr_spectral_norm_fwd_f32')
+        ws = H.scratch(dev, wsb)
+        H.launch('sr_spectral_norm_fwd_f32', dev, w.data_ptr(), u.data_ptr(), v.data_ptr(), rows, cols, int(update), eps,
+                 w_sn.data_ptr(), sigma.data_ptr(), ws.data_ptr(), wsb)
         ctx.save_for_backward(w_sn, u.clone(), v.clone(), sigma)
         ctx.dims = (rows, cols)
         return w_sn
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         w_sn, u, v, sigma = ctx.saved_tensors
-        rows, cols = ctx.dims
-        dev = g.device
-        g = g.contiguous()
-        gw = torch.empty_like(g)
-        wsb = max((rows + cols) * 4, lib.sr_reduce_workspace_bytes(8) + 64)
-        ws = scratch(dev, wsb)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_spectral_norm_bwd_f32(g.data_ptr(), w_sn.data_ptr(), u.data_ptr(), v.data_ptr(), sigma.data_ptr(),
-                                                    rows, cols, gw.data_ptr(), ws.data_ptr(), wsb, _stream(dev)),
-                       'sr_spectral_norm_bwd_f32')
-        return gw, None, None, None, None
+        return _sn_bwd(g, w_sn, u, v, sigma.data_ptr(), *ctx.dims), None, None, None, None
 
 
 class SpectralNormBatchFn(torch.autograd.Function):
@@ -481,7 +433,6 @@ class SpectralNormBatchFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, update, eps, *wuv):
-        lib = _lib.load()
         nl = len(wuv) // 3
         ws_, us, vs = [w.contiguous() for w in wuv[0::3]], wuv[1::3], wuv[2::3]
         dev = ws_[0].device
@@ -498,10 +449,8 @@ class SpectralNormBatchFn(torch.autograd.Function):
             table[i].rows, table[i].cols = rows, cols
             table[i].w_sn, table[i].sigma = outs[i].data_ptr(), sigmas.data_ptr() + 4 * i
             need += ((rows + 16 * cols) * 4 + 255) // 256 * 256
-        ws = scratch(dev, need + 256)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_spectral_norm_fwd_batch_f32(table, nl, int(update), eps, ws.data_ptr(), need + 256, _stream(dev)),
-                       'sr_spectral_norm_fwd_batch_f32')
+        ws = H.scratch(dev, need + 256)
+        H.launch('sr_spectral_norm_fwd_batch_f32', dev, table, nl, int(update), eps, ws.data_ptr(), need + 256)
         if any(ctx.needs_input_grad[2::3]):   # u, v are updated in place by the next forward: the backward needs this forward's
             ctx.save_for_backward(sigmas, *outs, *[u.clone() for u in us], *[v.clone() for v in vs])
         ctx.dims = dims
@@ -509,7 +458,6 @@ class SpectralNormBatchFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gs):
-        lib = _lib.load()
         saved = ctx.saved_tensors
         nl = len(ctx.dims)
         sigmas, outs, us, vs = saved[0], saved[1:1 + nl], saved[1 + nl:1 + 2 * nl], saved[1 + 2 * nl:1 + 3 * nl]
@@ -518,44 +466,30 @@ class SpectralNormBatchFn(torch.autograd.Function):
             if g is None:
                 grads += [None, None, None]
                 continue
-            rows, cols = ctx.dims[i]
-            dev = g.device
-            g = g.contiguous()
-            gw = torch.empty_like(g)
-            wsb = max((rows + cols) * 4, lib.sr_reduce_workspace_bytes(8) + 64)
-            ws = scratch(dev, wsb)
-            with torch.cuda.device(dev):
-                _lib.check(lib.sr_spectral_norm_bwd_f32(g.data_ptr(), outs[i].data_ptr(), us[i].data_ptr(), vs[i].data_ptr(),
-                                                        sigmas.data_ptr() + 4 * i, rows, cols, gw.data_ptr(), ws.data_ptr(), wsb,
-                                                        _stream(dev)), 'sr_spectral_norm_bwd_f32')
+            gw = _sn_bwd(g, outs[i], us[i], vs[i], sigmas.data_ptr() + 4 * i, *ctx.dims[i])
             grads += [gw, None, None]
         return tuple(grads)
 
 
 class MaxPool2x2Fn(torch.autograd.Function):
-    """nn.MaxPool2d(kernel_size=2, stride=2) on CB8 (sr_maxpool2x2_fwd_f32 / sr_maxpool2x2_bwd_f32)."""
+    """nn.MaxPool2d(kernel_size=2, stride=2) on CB8 or CB16 (sr_maxpool2x2_fwd_f32 / sr_maxpool2x2_bwd_f32, or their _bf16 twins)."""
 
     @staticmethod
     def forward(ctx, x):
-        lib = _lib.load()
         x = x.contiguous()
-        n, cb, h, w, _ = x.shape
-        y = torch.empty((n, cb, h // 2, w // 2, 8), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_maxpool2x2_fwd_f32(x.data_ptr(), y.data_ptr(), n, cb, h, w, _stream(x.device)), 'sr_maxpool2x2_fwd_f32')
+        n, cb, h, w, blk = x.shape
+        y = torch.empty((n, cb, h // 2, w // 2, blk), dtype=x.dtype, device=x.device)
+        H.launch('sr_maxpool2x2_fwd' + _sfx(x), x.device, x.data_ptr(), y.data_ptr(), n, cb, h, w)
         ctx.save_for_backward(x)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         x, = ctx.saved_tensors
         n, cb, h, w, _ = x.shape
         dx = torch.empty_like(x)
         gy = gy.contiguous()
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_maxpool2x2_bwd_f32(x.data_ptr(), gy.data_ptr(), dx.data_ptr(), n, cb, h, w, _stream(x.device)),
-                       'sr_maxpool2x2_bwd_f32')
+        H.launch('sr_maxpool2x2_bwd' + _sfx(x), x.device, x.data_ptr(), gy.data_ptr(), dx.data_ptr(), n, cb, h, w)
         return dx
 
 
@@ -564,50 +498,37 @@ class ChannelAffineFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, a, b):
-        lib = _lib.load()
         x = x.contiguous().float()
         n, c, h, w = x.shape
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_channel_affine_f32(x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), n, c, h * w, _stream(x.device)),
-                       'sr_channel_affine_f32')
+        H.launch('sr_channel_affine_f32', x.device, x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), n, c, h * w)
         ctx.save_for_backward(a)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         a, = ctx.saved_tensors
         gy = gy.contiguous()
         n, c, h, w = gy.shape
         dx = torch.empty_like(gy)
-        with torch.cuda.device(gy.device):
-            _lib.check(lib.sr_channel_affine_f32(gy.data_ptr(), dx.data_ptr(), a.data_ptr(), None, n, c, h * w, _stream(gy.device)),
-                       'sr_channel_affine_f32')
+        H.launch('sr_channel_affine_f32', gy.device, gy.data_ptr(), dx.data_ptr(), a.data_ptr(), None, n, c, h * w)
         return dx, None, None
 
 
 class LReLUFn(torch.autograd.Function):
-    """Stand-alone LeakyReLU(slope) / ReLU (slope 0) on any contiguous fp32 tensor (sr_lrelu_fwd_f32 / sr_lrelu_bwd_f32)."""
+    """Stand-alone LeakyReLU(slope) / ReLU (slope 0) on any contiguous fp32 or bf16 tensor (sr_lrelu_fwd_f32 / sr_lrelu_bwd_f32, or
+    their _bf16 twins)."""
 
     @staticmethod
     def forward(ctx, x, slope):
-        lib = _lib.load()
         x = x.contiguous()
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_lrelu_fwd_f32(x.data_ptr(), y.data_ptr(), slope, x.numel(), _stream(x.device)), 'sr_lrelu_fwd_f32')
+        H.launch('sr_lrelu_fwd' + _sfx(x), x.device, x.data_ptr(), y.data_ptr(), slope, x.numel())
         ctx.save_for_backward(y)
         ctx.slope = slope
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         y, = ctx.saved_tensors
-        gy = gy.contiguous()
-        dx = torch.empty_like(gy)
-        with torch.cuda.device(gy.device):
-            _lib.check(lib.sr_lrelu_bwd_f32(gy.data_ptr(), y.data_ptr(), dx.data_ptr(), ctx.slope, gy.numel(), _stream(gy.device)),
-                       'sr_lrelu_bwd_f32')
-        return dx, None
+        return _lrelu_bwd(gy.contiguous(), y, ctx.slope), None

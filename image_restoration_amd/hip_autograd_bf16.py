@@ -2,25 +2,22 @@
 
 Activations travel between these Functions as torch.bfloat16 tensors shaped [N, C/16, H, W, 16] (the CB16 layout of
 include/sr_hip.h); weights, biases and their gradients stay fp32 (the master copies the optimiser updates); every
-forward / backward below is libsr_hip.so launches only.  Twin of hip_autograd.py (fp32, CB8).
+forward / backward below is libsr_hip.so launches only, each made through hip_ops.launch.  Twin of hip_autograd.py (fp32, CB8):
+what differs from it only in the entry point's suffix and the block width is that module's code under its ...Fn16 name (BN +
+LeakyReLU, max-pool, LeakyReLU, the backward of ToCB16); the Functions below differ in substance.
 """
-import ctypes as C
-
 import torch
 
-from . import _lib
+from . import hip_autograd as A
 from . import hip_ops as H
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
+from .hip_autograd import BNLReLUFn as BNLReLUFn16, LReLUFn as LReLUFn16, MaxPool2x2Fn as MaxPool2x2Fn16  # noqa: F401
 
 
 def _cb16(t):
     return H.CB16(t)
 
 
-class ToCB16(torch.autograd.Function):
+class ToCB16(A.ToCB8):
     """NCHW fp32 -> CB16 bf16 (sr_nchw_to_cb16_bf16); backward CB16 -> NCHW fp32."""
 
     @staticmethod
@@ -28,14 +25,9 @@ class ToCB16(torch.autograd.Function):
         ctx.c = x.size(1)
         return H.nchw_to_cb16(x).buf
 
-    @staticmethod
-    def backward(ctx, g):
-        return H.cb16_to_nchw(_cb16(g.contiguous()), ctx.c)
-
 
 def _unshuffle2(t, inverse=False):
     """CB16 [N, C/16, 2h, 2w, 16] <-> [N, 4C/16, h, w, 16] (parity-major channels) — sr_cb16_unshuffle2_bf16."""
-    lib = _lib.load()
     n, cb, hh, ww, _ = t.shape
     if inverse:
         cblocks, h, w = cb // 4, hh, ww
@@ -43,28 +35,21 @@ def _unshuffle2(t, inverse=False):
     else:
         cblocks, h, w = cb, hh // 2, ww // 2
         out = torch.empty((n, 4 * cblocks, h, w, 16), dtype=torch.bfloat16, device=t.device)
-    with torch.cuda.device(t.device):
-        _lib.check(lib.sr_cb16_unshuffle2_bf16(t.data_ptr(), t[0].numel(), out.data_ptr(), out[0].numel(), n, cblocks, h, w,
-                                               int(inverse), _stream(t.device)), 'sr_cb16_unshuffle2_bf16')
+    H.launch('sr_cb16_unshuffle2_bf16', t.device, t.data_ptr(), t[0].numel(), out.data_ptr(), out[0].numel(), n, cblocks, h, w,
+             int(inverse))
     return out
 
 
 def _w4_as_w3(w4):
-    lib = _lib.load()
     cout, cin = w4.shape[:2]
     w3 = torch.empty((cout, 4 * cin, 3, 3), dtype=torch.float32, device=w4.device)
-    with torch.cuda.device(w4.device):
-        _lib.check(lib.sr_conv4x4s2_weight_as_3x3_f32(w4.data_ptr(), w3.data_ptr(), cout, cin, 0, _stream(w4.device)),
-                   'sr_conv4x4s2_weight_as_3x3_f32')
+    H.launch('sr_conv4x4s2_weight_as_3x3_f32', w4.device, w4.data_ptr(), w3.data_ptr(), cout, cin, 0)
     return w3
 
 
 def _dw3_to_dw4(dw3, cout, cin):
-    lib = _lib.load()
     dw4 = torch.empty((cout, cin, 4, 4), dtype=torch.float32, device=dw3.device)
-    with torch.cuda.device(dw3.device):
-        _lib.check(lib.sr_conv4x4s2_weight_as_3x3_f32(dw4.data_ptr(), dw3.data_ptr(), cout, cin, 1, _stream(dw3.device)),
-                   'sr_conv4x4s2_weight_as_3x3_f32')
+    H.launch('sr_conv4x4s2_weight_as_3x3_f32', dw3.device, dw4.data_ptr(), dw3.data_ptr(), cout, cin, 1)
     return dw4
 
 
@@ -142,7 +127,6 @@ class ConvFn16(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         xs, w3, y, skip_u2 = ctx.saved_tensors
         src = _cb16(xs)
         dev = gy.device
@@ -157,14 +141,10 @@ class ConvFn16(torch.autograd.Function):
             if skip_u2 is not None:     # y = activation + skip (sign-keeping rounding): mask = sign(y - skip)
                 dz = torch.empty_like(gy)
                 n_, cb_, h2_, w2_, _ = gy.shape
-                with torch.cuda.device(dev):
-                    _lib.check(lib.sr_lrelu_bwd_diff_u2_bf16(gy.data_ptr(), y.data_ptr(), skip_u2.data_ptr(), dz.data_ptr(), ctx.act_slope,
-                                                             n_, cb_, h2_ // 2, w2_ // 2, _stream(dev)), 'sr_lrelu_bwd_diff_u2_bf16')
+                H.launch('sr_lrelu_bwd_diff_u2_bf16', dev, gy.data_ptr(), y.data_ptr(), skip_u2.data_ptr(), dz.data_ptr(),
+                         ctx.act_slope, n_, cb_, h2_ // 2, w2_ // 2)
             elif y is not None and not ctx.grad_premasked:
-                dz = torch.empty_like(gy)
-                with torch.cuda.device(dev):
-                    _lib.check(lib.sr_lrelu_bwd_bf16(gy.data_ptr(), y.data_ptr(), dz.data_ptr(), ctx.act_slope, gy.numel(),
-                                                     _stream(dev)), 'sr_lrelu_bwd_bf16')
+                dz = A._lrelu_bwd(gy, y, ctx.act_slope)
             else:
                 dz = gy
             dzc = _cb16(dz)
@@ -203,17 +183,14 @@ class SkipForkFn16(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_skip, g_u):
-        lib = _lib.load()
         (x,) = ctx.saved_tensors
         if g_u is None:  # the strided conv took no gradient (frozen network input): plain LeakyReLU backward of the skip
             g_u = torch.zeros((x.size(0), 4 * x.size(1), x.size(2) // 2, x.size(3) // 2, 16), dtype=x.dtype, device=x.device)
         n, cb, hh, ww, _ = x.shape
         dz = torch.empty_like(x)
         g_skip = g_skip.contiguous() if g_skip is not None else None
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_cb16_fork_bwd_bf16(g_skip.data_ptr() if g_skip is not None else None, g_u.contiguous().data_ptr(),
-                                                 x.data_ptr(), dz.data_ptr(), ctx.slope, n, cb, hh // 2, ww // 2, _stream(x.device)),
-                       'sr_cb16_fork_bwd_bf16')
+        H.launch('sr_cb16_fork_bwd_bf16', x.device, g_skip.data_ptr() if g_skip is not None else None,
+                 g_u.contiguous().data_ptr(), x.data_ptr(), dz.data_ptr(), ctx.slope, n, cb, hh // 2, ww // 2)
         return dz, None
 
 
@@ -234,17 +211,14 @@ class ForkU2Fn16(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_skip, g_u):
-        lib = _lib.load()
         (u,) = ctx.saved_tensors
         n, cb4, h, w, _ = u.shape
         if g_u is None:
             g_u = torch.zeros_like(u)
         dz = torch.empty_like(u)   # plain layout [n, cb4 / 4, 2h, 2w, 16] under u's shape
         g_skip = g_skip.contiguous() if g_skip is not None else None
-        with torch.cuda.device(u.device):
-            _lib.check(lib.sr_cb16_fork_bwd_u2_bf16(g_skip.data_ptr() if g_skip is not None else None, g_u.contiguous().data_ptr(),
-                                                    u.data_ptr(), dz.data_ptr(), ctx.slope, n, cb4 // 4, h, w, _stream(u.device)),
-                       'sr_cb16_fork_bwd_u2_bf16')
+        H.launch('sr_cb16_fork_bwd_u2_bf16', u.device, g_skip.data_ptr() if g_skip is not None else None,
+                 g_u.contiguous().data_ptr(), u.data_ptr(), dz.data_ptr(), ctx.slope, n, cb4 // 4, h, w)
         return dz, None
 
 
@@ -260,21 +234,19 @@ class Bilinear2xFn16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, skip=None, input_slope=1.0, skip_u2=False):
-        lib = _lib.load()
         x = x.contiguous()
         n, cb, h, w, _ = x.shape
         y = torch.empty((n, cb, 2 * h, 2 * w, 16), dtype=torch.bfloat16, device=x.device)
         if skip is not None:
             skip = skip.contiguous()
             assert skip.shape == ((n, 4 * cb, h // 2, w // 2, 16) if skip_u2 else x.shape)
-        with torch.cuda.device(x.device):
-            if skip is not None and skip_u2:
-                _lib.check(lib.sr_bilinear2x_fwd_u2_bf16(x.data_ptr(), x[0].numel(), skip.data_ptr(), skip[0].numel(), y.data_ptr(),
-                                                         y[0].numel(), n, cb, h, w, _stream(x.device)), 'sr_bilinear2x_fwd_u2_bf16')
-            else:
-                _lib.check(lib.sr_bilinear2x_fwd_bf16(x.data_ptr(), x[0].numel(), skip.data_ptr() if skip is not None else None,
-                                                      skip[0].numel() if skip is not None else 0, y.data_ptr(), y[0].numel(), n, cb, h,
-                                                      w, _stream(x.device)), 'sr_bilinear2x_fwd_bf16')
+        if skip is not None and skip_u2:
+            H.launch('sr_bilinear2x_fwd_u2_bf16', x.device, x.data_ptr(), x[0].numel(), skip.data_ptr(), skip[0].numel(),
+                     y.data_ptr(), y[0].numel(), n, cb, h, w)
+        else:
+            H.launch('sr_bilinear2x_fwd_bf16', x.device, x.data_ptr(), x[0].numel(),
+                     skip.data_ptr() if skip is not None else None, skip[0].numel() if skip is not None else 0, y.data_ptr(),
+                     y[0].numel(), n, cb, h, w)
         ctx.has_skip = skip is not None
         ctx.skip_shape = tuple(skip.shape) if skip is not None else None
         ctx.input_slope = input_slope
@@ -284,7 +256,6 @@ class Bilinear2xFn16(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         g = g.contiguous()
         n, cb, h2, w2, _ = g.shape
         gx = torch.empty((n, cb, h2 // 2, w2 // 2, 16), dtype=torch.bfloat16, device=g.device)
@@ -292,15 +263,12 @@ class Bilinear2xFn16(torch.autograd.Function):
             (x,) = ctx.saved_tensors
             want_plain = ctx.has_skip and ctx.needs_input_grad[1]
             gplain = torch.empty_like(gx) if want_plain else None
-            with torch.cuda.device(g.device):
-                _lib.check(lib.sr_bilinear2x_bwd_lrelu_bf16(g.data_ptr(), g[0].numel(), gx.data_ptr(), gx[0].numel(), x.data_ptr(),
-                                                            x[0].numel(), ctx.input_slope, gplain.data_ptr() if want_plain else None,
-                                                            gplain[0].numel() if want_plain else 0, n, cb, h2 // 2, w2 // 2,
-                                                            _stream(g.device)), 'sr_bilinear2x_bwd_lrelu_bf16')
+            H.launch('sr_bilinear2x_bwd_lrelu_bf16', g.device, g.data_ptr(), g[0].numel(), gx.data_ptr(), gx[0].numel(),
+                     x.data_ptr(), x[0].numel(), ctx.input_slope, gplain.data_ptr() if want_plain else None,
+                     gplain[0].numel() if want_plain else 0, n, cb, h2 // 2, w2 // 2)
             return gx, (gplain.view(ctx.skip_shape) if want_plain else None), None, None
-        with torch.cuda.device(g.device):
-            _lib.check(lib.sr_bilinear2x_bwd_bf16(g.data_ptr(), g[0].numel(), gx.data_ptr(), gx[0].numel(), n, cb, h2 // 2, w2 // 2,
-                                                  _stream(g.device)), 'sr_bilinear2x_bwd_bf16')
+        H.launch('sr_bilinear2x_bwd_bf16', g.device, g.data_ptr(), g[0].numel(), gx.data_ptr(), gx[0].numel(), n, cb, h2 // 2,
+                 w2 // 2)
         return gx, (gx.view(ctx.skip_shape) if ctx.has_skip else None), None, None
 
 
@@ -310,77 +278,21 @@ class AddFn16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b, b_u2=False):
-        lib = _lib.load()
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty_like(a)
         ctx.b_shape = tuple(b.shape)
-        with torch.cuda.device(a.device):
-            if b_u2:
-                n, cb, h2, w2, _ = a.shape
-                assert b.shape == (n, 4 * cb, h2 // 2, w2 // 2, 16)
-                _lib.check(lib.sr_cb16_add_u2_bf16(a.data_ptr(), b.data_ptr(), out.data_ptr(), n, cb, h2 // 2, w2 // 2, _stream(a.device)),
-                           'sr_cb16_add_u2_bf16')
-            else:
-                assert a.shape == b.shape
-                _lib.check(lib.sr_cb16_add_bf16(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _stream(a.device)),
-                           'sr_cb16_add_bf16')
+        if b_u2:
+            n, cb, h2, w2, _ = a.shape
+            assert b.shape == (n, 4 * cb, h2 // 2, w2 // 2, 16)
+            H.launch('sr_cb16_add_u2_bf16', a.device, a.data_ptr(), b.data_ptr(), out.data_ptr(), n, cb, h2 // 2, w2 // 2)
+        else:
+            assert a.shape == b.shape
+            H.launch('sr_cb16_add_bf16', a.device, a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel())
         return out
 
     @staticmethod
     def backward(ctx, g):
         return g, g.view(ctx.b_shape), None
-
-
-class MaxPool2x2Fn16(torch.autograd.Function):
-    """nn.MaxPool2d(kernel_size=2, stride=2) on CB16 (sr_maxpool2x2_{fwd,bwd}_bf16)."""
-
-    @staticmethod
-    def forward(ctx, x):
-        lib = _lib.load()
-        x = x.contiguous()
-        n, cb, h, w, _ = x.shape
-        y = torch.empty((n, cb, h // 2, w // 2, 16), dtype=torch.bfloat16, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_maxpool2x2_fwd_bf16(x.data_ptr(), y.data_ptr(), n, cb, h, w, _stream(x.device)), 'sr_maxpool2x2_fwd_bf16')
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        (x,) = ctx.saved_tensors
-        n, cb, h, w, _ = x.shape
-        dx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_maxpool2x2_bwd_bf16(x.data_ptr(), g.contiguous().data_ptr(), dx.data_ptr(), n, cb, h, w,
-                                                  _stream(x.device)), 'sr_maxpool2x2_bwd_bf16')
-        return dx
-
-
-class LReLUFn16(torch.autograd.Function):
-    """Stand-alone LeakyReLU / ReLU on CB16 (sr_lrelu_fwd_bf16 / sr_lrelu_bwd_bf16)."""
-
-    @staticmethod
-    def forward(ctx, x, slope):
-        lib = _lib.load()
-        x = x.contiguous()
-        y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sr_lrelu_fwd_bf16(x.data_ptr(), y.data_ptr(), slope, x.numel(), _stream(x.device)), 'sr_lrelu_fwd_bf16')
-        ctx.save_for_backward(y)
-        ctx.slope = slope
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        (y,) = ctx.saved_tensors
-        g = g.contiguous()
-        dz = torch.empty_like(g)
-        with torch.cuda.device(g.device):
-            _lib.check(lib.sr_lrelu_bwd_bf16(g.data_ptr(), y.data_ptr(), dz.data_ptr(), ctx.slope, g.numel(), _stream(g.device)),
-                       'sr_lrelu_bwd_bf16')
-        return dz, None
 
 
 class FromCB16(torch.autograd.Function):
@@ -396,52 +308,3 @@ class FromCB16(torch.autograd.Function):
         out = H.nchw_to_cb16(g.contiguous().float())
         assert out.buf.size(1) == ctx.cb
         return out.buf, None
-
-
-class BNLReLUFn16(torch.autograd.Function):
-    """nn.BatchNorm2d + LeakyReLU on CB16 (sr_bn_lrelu_fwd_bf16 / sr_bn_lrelu_bwd_bf16); parameters, statistics and running
-    buffers fp32."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, train, momentum, eps, slope):
-        lib = _lib.load()
-        x = x.contiguous()
-        n, cb, h, w, _ = x.shape
-        c = gamma.numel()
-        dev = x.device
-        y = torch.empty_like(x)
-        mean = torch.empty(c, dtype=torch.float32, device=dev)
-        invstd = torch.empty(c, dtype=torch.float32, device=dev)
-        wsb = lib.sr_reduce_workspace_bytes(c)
-        ws = H.scratch(dev, wsb)
-        ns = cb * h * w * 16
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_bn_lrelu_fwd_bf16(x.data_ptr(), ns, y.data_ptr(), ns, n, c, h, w, gamma.data_ptr(), beta.data_ptr(),
-                                                running_mean.data_ptr() if running_mean is not None else None,
-                                                running_var.data_ptr() if running_var is not None else None, int(train), momentum,
-                                                eps, slope, mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), wsb, _stream(dev)),
-                       'sr_bn_lrelu_fwd_bf16')
-        ctx.save_for_backward(x, y, gamma, mean, invstd)
-        ctx.train, ctx.slope = bool(train), slope
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        lib = _lib.load()
-        x, y, gamma, mean, invstd = ctx.saved_tensors
-        n, cb, h, w, _ = x.shape
-        c = gamma.numel()
-        dev = x.device
-        gy = gy.contiguous()
-        dx = torch.empty_like(x)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(gamma)
-        wsb = lib.sr_reduce_workspace_bytes(c)
-        ws = H.scratch(dev, wsb)
-        ns = cb * h * w * 16
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_bn_lrelu_bwd_bf16(x.data_ptr(), ns, gy.data_ptr(), ns, y.data_ptr(), ns, dx.data_ptr(), ns, n, c, h, w,
-                                                gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(), int(ctx.train), ctx.slope,
-                                                dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), wsb, _stream(dev)),
-                       'sr_bn_lrelu_bwd_bf16')
-        return dx, dgamma, dbeta, None, None, None, None, None, None

@@ -1,8 +1,12 @@
-"""Thin torch-tensor wrappers over the C ABI (include/sr_hip.h).
+"""Thin torch-tensor wrappers over the C ABI (include/sr_hip.h and its per-network companions).
 
-Tensors only provide device memory and the current HIP stream; every op below is one
-libsr_hip.so call.  Activations between ops are in the CB8 layout
-``[N][C/8][H][W][8]`` (class ``CB8``); channel slices are views (pointer + parent stride).
+Tensors only provide device memory and the current HIP stream; every op below is one libsr_hip.so call, made through
+``launch`` (device guard, the device's current stream as the last argument, the status check that names the symbol).
+Activations between ops are channel-blocked: fp32 ``[N][C/8][H][W][8]`` (class ``CB8``) or bf16 ``[N][C/16][H][W][16]``
+(class ``CB16``); channel slices are views (pointer + parent stride).  What the conv wrappers share is written once:
+``_PackedWeights`` (the four weight-image classes), ``_conv_desc`` (struct sr_conv3x3_desc for both dtypes) and
+``_wgrad_targets`` / ``_wgrad_desc`` (struct sr_conv3x3_wgrad_desc).  A wrapper is its assertions, its allocations and one
+``launch`` line.
 """
 import ctypes as C
 import weakref
@@ -14,6 +18,15 @@ from . import _lib
 
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+def launch(name, dev, *args):
+    """The one way a stream-ordered entry point is called: ``lib.<name>(*args, stream)`` under ``dev``'s device guard, with
+    ``dev``'s current stream looked up inside the guard, and a non-zero status raised as SrHipError naming ``name``.  ``args``
+    are what ctypes takes: device pointers as ints (``t.data_ptr()``, a CB window's ``.ptr``), None for NULL, scalars, byref."""
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
 
 
 _scratch = {}
@@ -64,117 +77,165 @@ def scratch(dev, nbytes, tag='ws'):
     return buf
 
 
+def reduce_ws(dev, c=8):
+    """(workspace, its size in bytes) of the two-stage reductions over ``c`` channels (sr_reduce_workspace_bytes)."""
+    nbytes = _lib.load().sr_reduce_workspace_bytes(c)
+    return scratch(dev, nbytes), nbytes
+
+
 def _need_cuda(t, what):
     if not t.is_cuda:
         raise _lib.SrHipError(f'{what}: tensor is on {t.device}; the HIP path has no CPU fallback')
 
 
-class CB8:
-    """A channel-blocked fp32 activation: storage ``buf`` [N, CB, H, W, 8] plus a channel-block window."""
+class _CBWindow:
+    """A channel-blocked activation: storage ``buf`` [N, CB, H, W, block] plus a channel-block window [cb0, cb0 + cbn)."""
+    block = dtype = esize = None   # channels per block, element type, bytes per element
 
     def __init__(self, buf, cb0=0, cbn=None):
-        assert buf.dim() == 5 and buf.size(4) == 8 and buf.dtype == torch.float32 and buf.is_contiguous()
+        assert buf.dim() == 5 and buf.size(4) == self.block and buf.dtype == self.dtype and buf.is_contiguous()
         self.buf, self.cb0 = buf, cb0
         self.cbn = buf.size(1) - cb0 if cbn is None else cbn
         assert 0 <= cb0 and cb0 + self.cbn <= buf.size(1)
 
-    @staticmethod
-    def empty(n, channels, h, w, device):
-        return CB8(torch.empty((n, (channels + 7) // 8, h, w, 8), dtype=torch.float32, device=device))
+    @classmethod
+    def empty(cls, n, channels, h, w, device):
+        return cls(torch.empty((n, (channels + cls.block - 1) // cls.block, h, w, cls.block), dtype=cls.dtype, device=device))
 
-    @staticmethod
-    def zeros(n, channels, h, w, device):
-        return CB8(torch.zeros((n, (channels + 7) // 8, h, w, 8), dtype=torch.float32, device=device))
+    @classmethod
+    def zeros(cls, n, channels, h, w, device):
+        return cls(torch.zeros((n, (channels + cls.block - 1) // cls.block, h, w, cls.block), dtype=cls.dtype, device=device))
 
     n = property(lambda s: s.buf.size(0))
     h = property(lambda s: s.buf.size(2))
     w = property(lambda s: s.buf.size(3))
-    channels = property(lambda s: s.cbn * 8)
-    img_stride = property(lambda s: s.buf.size(1) * s.buf.size(2) * s.buf.size(3) * 8)
+    channels = property(lambda s: s.cbn * s.block)
+    img_stride = property(lambda s: s.buf.size(1) * s.buf.size(2) * s.buf.size(3) * s.block)
     device = property(lambda s: s.buf.device)
 
     @property
     def ptr(self):
-        return self.buf.data_ptr() + self.cb0 * self.h * self.w * 8 * 4
+        return self.buf.data_ptr() + self.cb0 * self.h * self.w * self.block * self.esize
 
     def slice(self, c0, c):
-        assert c0 % 8 == 0 and c % 8 == 0
-        return CB8(self.buf, self.cb0 + c0 // 8, c // 8)
+        assert c0 % self.block == 0 and c % self.block == 0
+        return type(self)(self.buf, self.cb0 + c0 // self.block, c // self.block)
+
+
+class CB8(_CBWindow):
+    """A channel-blocked fp32 activation: storage ``buf`` [N, CB, H, W, 8] plus a channel-block window."""
+    block, dtype, esize = 8, torch.float32, 4
+
+
+class CB16(_CBWindow):
+    """A channel-blocked bf16 activation: storage ``buf`` [N, CB, H, W, 16] plus a channel-block window."""
+    block, dtype, esize = 16, torch.bfloat16, 2
 
 
 def nchw_to_cb8(x, unshuffle=1, out=None):
     _need_cuda(x, 'nchw_to_cb8')
-    lib = _lib.load()
     x = x.contiguous().float()
     n, c, hh, ww = x.shape
     h, w = hh // unshuffle, ww // unshuffle
     cu = c * unshuffle * unshuffle
     if out is None:
         out = CB8.empty(n, cu, h, w, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sr_nchw_to_cb8_f32(x.data_ptr(), out.ptr, n, c, h, w, unshuffle, out.cbn, out.img_stride,
-                                          _stream(x.device)), 'sr_nchw_to_cb8_f32')
+    launch('sr_nchw_to_cb8_f32', x.device, x.data_ptr(), out.ptr, n, c, h, w, unshuffle, out.cbn, out.img_stride)
     return out
 
 
-def cb8_to_nchw(t, channels):
-    lib = _lib.load()
+def cb_to_nchw(t, channels):
+    """CB8 or CB16 window -> NCHW fp32 with ``channels`` real channels — sr_cb8_to_nchw_f32 / sr_cb16_to_nchw_f32."""
     y = torch.empty((t.n, channels, t.h, t.w), dtype=torch.float32, device=t.device)
-    with torch.cuda.device(t.device):
-        _lib.check(lib.sr_cb8_to_nchw_f32(t.ptr, t.img_stride, y.data_ptr(), t.n, channels, t.h, t.w, 1,
-                                          _stream(t.device)), 'sr_cb8_to_nchw_f32')
+    launch(f'sr_cb{t.block}_to_nchw_f32', t.device, t.ptr, t.img_stride, y.data_ptr(), t.n, channels, t.h, t.w, 1)
     return y
 
 
-class PackedConv:
-    """MFMA operand image of one 3x3 conv (sr_conv3x3_pack_f32)."""
+cb8_to_nchw = cb16_to_nchw = cb_to_nchw
 
-    def __init__(self, weight, bias=None, first_seg=None, seg=0, mode=0):
-        _need_cuda(weight, 'PackedConv')
+
+class _PackedWeights:
+    """What the weight-image classes share: the device check, the fp32 copy of the weight, cout / src_channels by ``mode``
+    (0 = forward, 1 = data gradient: the image consumes dY and produces the padded source channels), the weight image, the bias
+    image (mode 0 with a bias only) and the one pack call.  A subclass states its kernel-size assertion and padding rule
+    (``_cin_pad``) and its size query and pack entry point (``_image``); every pack entry point takes (weight, bias,
+    *geometry, weight image, bias image, stream)."""
+    block, wdtype = 8, torch.float32   # channel block of the activations, element type of the weight image
+
+    def __init__(self, weight, bias, mode, first_seg=None, seg=0):
+        _need_cuda(weight, type(self).__name__)
         lib = _lib.load()
         weight = weight.detach().contiguous().float()
         cout, cin = weight.shape[:2]
-        assert weight.shape[2:] == (3, 3)
         first_seg = cin if first_seg is None else first_seg
-        self.cin_pad = lib.sr_conv3x3_cin_pad(cin, first_seg, seg)
-        if self.cin_pad <= 0:
-            raise ValueError(f'cin={cin} is not first_seg={first_seg} + k*seg={seg}')
+        cin_pad = self._cin_pad(lib, weight, first_seg, seg)
         self.mode = mode
         if mode == 0:
-            self.cout, self.src_channels = cout, self.cin_pad
-            nw = lib.sr_conv3x3_packed_weight_floats(cout, self.cin_pad)
+            self.cout, self.src_channels = cout, cin_pad
         else:
-            self.cout, self.src_channels = self.cin_pad, (cout + 7) // 8 * 8
-            nw = lib.sr_conv3x3_packed_weight_floats(self.cin_pad, self.src_channels)
+            self.cout, self.src_channels = cin_pad, (cout + self.block - 1) // self.block * self.block
+        nw, name, geometry = self._image(lib, cout, cin, first_seg, seg, mode)
         dev = weight.device
-        self.w = torch.empty(nw, dtype=torch.float32, device=dev)
+        self.w = torch.empty(nw, dtype=self.wdtype, device=dev)
         self.b = None
         if mode == 0 and bias is not None:
             bias = bias.detach().contiguous().float()
             self.b = torch.empty(lib.sr_conv3x3_packed_bias_floats(cout), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_conv3x3_pack_f32(weight.data_ptr(), bias.data_ptr() if self.b is not None else None,
-                                               cout, cin, first_seg, seg, mode, self.w.data_ptr(),
-                                               self.b.data_ptr() if self.b is not None else None, _stream(dev)),
-                       'sr_conv3x3_pack_f32')
+        launch(name, dev, weight.data_ptr(), bias.data_ptr() if self.b is not None else None, *geometry, self.w.data_ptr(),
+               self.b.data_ptr() if self.b is not None else None)
 
 
-def _conv_desc_f32(src, pc, out=None, *, upsample=False, act_slope=1.0, alpha=1.0, res1=None, beta1=0.0, res2=None,
-                   beta2=0.0, accumulate=False, mask=None, mask_cb0=0, mask_slope=0.2, out_nchw=None):
+class PackedConv(_PackedWeights):
+    """MFMA operand image of one 3x3 conv (sr_conv3x3_pack_f32)."""
+
+    def __init__(self, weight, bias=None, first_seg=None, seg=0, mode=0):
+        super().__init__(weight, bias, mode, first_seg, seg)
+
+    def _cin_pad(self, lib, weight, first_seg, seg):
+        cin = weight.shape[1]
+        assert weight.shape[2:] == (3, 3)
+        self.cin_pad = lib.sr_conv3x3_cin_pad(cin, first_seg, seg)
+        if self.cin_pad <= 0:
+            raise ValueError(f'cin={cin} is not first_seg={first_seg} + k*seg={seg}')
+        return self.cin_pad
+
+    def _image(self, lib, cout, cin, first_seg, seg, mode):
+        return (lib.sr_conv3x3_packed_weight_floats(self.cout, self.src_channels), 'sr_conv3x3_pack_f32',
+                (cout, cin, first_seg, seg, mode))
+
+
+def _conv_operands(d, src, pc, bias=True):
+    """The source and weight fields of a struct sr_conv3x3_desc."""
+    d.in_, d.in_img_stride, d.cin_pad, d.in_h, d.in_w = src.ptr, src.img_stride, pc.src_channels, src.h, src.w
+    d.wpacked, d.cout = pc.w.data_ptr(), pc.cout
+    if bias and pc.b is not None:
+        d.bpacked = pc.b.data_ptr()
+
+
+def _conv_desc(src, pc, out, upsample, act_slope, alpha, res1, beta1, res2, beta2, out_nchw, mask, mask_cb0, mask_slope,
+               out_unshuffle2=False):
+    """What sr_conv3x3_f32 and sr_conv3x3_bf16 (and the descriptors that embed theirs) share of a struct sr_conv3x3_desc:
+    operands, destination, epilogue scalars, residuals and mask; the windows are ``type(src)`` (CB8 or CB16).  Returns
+    (descriptor, what the conv returns)."""
     assert src.channels == pc.src_channels, (src.channels, pc.src_channels)
+    CB = type(src)
     H, W = (2 * src.h, 2 * src.w) if upsample else (src.h, src.w)
     d = _lib.ConvDesc()
-    d.in_, d.in_img_stride, d.cin_pad, d.in_h, d.in_w = src.ptr, src.img_stride, pc.src_channels, src.h, src.w
+    _conv_operands(d, src, pc)
     d.upsample = int(upsample)
-    d.wpacked, d.bpacked, d.cout = pc.w.data_ptr(), (pc.b.data_ptr() if pc.b is not None else None), pc.cout
     if out_nchw is not None:
         assert out_nchw.is_contiguous() and out_nchw.shape == (src.n, pc.cout, H, W)
         d.out, d.out_img_stride, d.out_nchw = out_nchw.data_ptr(), pc.cout * H * W, 1
         ret = out_nchw
+    elif out_unshuffle2:   # (bf16 only)
+        # the destination only exists pixel-unshuffled: [n][4 cout / 16][H / 2][W / 2][16] (sr_conv3x3_desc.out_unshuffle2)
+        assert out is None and pc.cout % 16 == 0 and H % 2 == 0 and W % 2 == 0
+        ret = CB.empty(src.n, 4 * pc.cout, H // 2, W // 2, src.device)
+        d.out, d.out_img_stride, d.out_nchw, d.out_unshuffle2 = ret.ptr, ret.img_stride, 0, 1
     else:
         if out is None:
-            out = CB8.empty(src.n, pc.cout, H, W, src.device)
-        assert (out.n, out.h, out.w) == (src.n, H, W) and out.channels >= (pc.cout + 7) // 8 * 8
+            out = CB.empty(src.n, pc.cout, H, W, src.device)  # every valid block is written (pad couts: zero weights)
+        assert (out.n, out.h, out.w) == (src.n, H, W) and out.channels >= (pc.cout + CB.block - 1) // CB.block * CB.block
         d.out, d.out_img_stride, d.out_nchw = out.ptr, out.img_stride, 0
         ret = out
     d.n, d.act_slope, d.alpha = src.n, act_slope, alpha
@@ -182,10 +243,19 @@ def _conv_desc_f32(src, pc, out=None, *, upsample=False, act_slope=1.0, alpha=1.
         d.res1, d.res1_img_stride, d.beta1 = res1.ptr, res1.img_stride, beta1
     if res2 is not None:
         d.res2, d.res2_img_stride, d.beta2 = res2.ptr, res2.img_stride, beta2
-    d.accumulate = int(accumulate)
     if mask is not None:
-        d.mask_src, d.mask_img_stride, d.mask_cb0, d.mask_cbn, d.mask_slope = (mask.ptr, mask.img_stride, mask_cb0,
-                                                                               mask.cbn, mask_slope)
+        _conv_mask(d, mask, mask_cb0, mask_slope)
+    return d, ret
+
+
+def _conv_mask(d, mask, mask_cb0, mask_slope):
+    d.mask_src, d.mask_img_stride, d.mask_cb0, d.mask_cbn, d.mask_slope = mask.ptr, mask.img_stride, mask_cb0, mask.cbn, mask_slope
+
+
+def _conv_desc_f32(src, pc, out=None, *, upsample=False, act_slope=1.0, alpha=1.0, res1=None, beta1=0.0, res2=None,
+                   beta2=0.0, accumulate=False, mask=None, mask_cb0=0, mask_slope=0.2, out_nchw=None):
+    d, ret = _conv_desc(src, pc, out, upsample, act_slope, alpha, res1, beta1, res2, beta2, out_nchw, mask, mask_cb0, mask_slope)
+    d.accumulate = int(accumulate)
     return d, ret
 
 
@@ -195,27 +265,48 @@ def conv3x3(src, pc, out=None, **kw):
     src: CB8 window of pc.src_channels channels.  out: CB8 window (allocated if None) or, with
     ``out_nchw`` = an NCHW tensor [N, cout<=4, H, W], a plain tensor.  Keywords: upsample, act_slope, alpha, res1/beta1,
     res2/beta2, accumulate, mask/mask_cb0/mask_slope, out_nchw."""
-    lib = _lib.load()
     d, ret = _conv_desc_f32(src, pc, out, **kw)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_conv3x3_f32(C.byref(d), _stream(src.device)), 'sr_conv3x3_f32')
+    launch('sr_conv3x3_f32', src.device, C.byref(d))
     return ret
+
+
+def _conv_chain(name, conv_desc, steps, sync, call_index):
+    src0 = steps[0][0]
+    if sync is None:
+        sync = torch.zeros(_lib.load().sr_conv3x3_chain_sync_ints(src0.n, src0.h, src0.w), dtype=torch.int32, device=src0.device)
+    descs = (_lib.ConvDesc * len(steps))()
+    outs = []
+    for i, (src, pc, out, kw) in enumerate(steps):
+        descs[i], ret = conv_desc(src, pc, out, **kw)
+        outs.append(ret)
+    launch(name, src0.device, descs, len(steps), sync.data_ptr(), call_index)
+    return outs, sync
 
 
 def conv3x3_chain(steps, sync=None, call_index=0):
     """fp32 twin of conv3x3_chain_bf16 — sr_conv3x3_chain_f32.  ``steps`` = [(src CB8, PackedConv, out CB8, kwargs of conv3x3)]."""
-    lib = _lib.load()
-    src0 = steps[0][0]
-    if sync is None:
-        sync = torch.zeros(lib.sr_conv3x3_chain_sync_ints(src0.n, src0.h, src0.w), dtype=torch.int32, device=src0.device)
-    descs = (_lib.ConvDesc * len(steps))()
-    outs = []
-    for i, (src, pc, out, kw) in enumerate(steps):
-        descs[i], ret = _conv_desc_f32(src, pc, out, **kw)
-        outs.append(ret)
-    with torch.cuda.device(src0.device):
-        _lib.check(lib.sr_conv3x3_chain_f32(descs, len(steps), sync.data_ptr(), call_index, _stream(src0.device)), 'sr_conv3x3_chain_f32')
-    return outs, sync
+    return _conv_chain('sr_conv3x3_chain_f32', _conv_desc_f32, steps, sync, call_index)
+
+
+def _wgrad_targets(out, shape, want_bias, dev, zeros=False):
+    """Where a weight gradient goes: (dw, db, (dweight pointer, dbias pointer, accumulate)).  ``out`` = the caller's
+    (dweight, dbias or None) device pointers the gradients are ADDED into (dw = db = None), else fresh fp32 tensors."""
+    if out is not None:
+        return None, None, (out[0], out[1], 1)
+    dw = (torch.zeros if zeros else torch.empty)(shape, dtype=torch.float32, device=dev)
+    db = torch.empty((shape[0],), dtype=torch.float32, device=dev) if want_bias else None
+    return dw, db, (dw.data_ptr(), db.data_ptr() if db is not None else None, 0)
+
+
+def _wgrad_desc(d, src, dy, cin_pad, upsample, cout, cin, first_seg, seg, scale, target, nbytes, tag='slab'):
+    """Fills a struct sr_conv3x3_wgrad_desc; the slab of ``nbytes`` is the per-device scratch buffer ``tag``."""
+    slab = scratch(src.device, nbytes, tag)
+    d.x, d.x_img_stride, d.cin_pad, d.in_h, d.in_w, d.upsample = src.ptr, src.img_stride, cin_pad, src.h, src.w, int(upsample)
+    d.dy, d.dy_img_stride = dy.ptr, dy.img_stride
+    d.cout, d.cin, d.first_seg, d.seg, d.n, d.scale = cout, cin, first_seg, seg, src.n, scale
+    d.dweight, d.dbias, d.accumulate = target
+    d.slab, d.slab_bytes = slab.data_ptr(), nbytes
+    return d
 
 
 def conv3x3_wgrad(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=False, scale=1.0, want_bias=True, out=None):
@@ -228,74 +319,47 @@ def conv3x3_wgrad(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=False, 
     assert src.channels == cin_pad, (src.channels, cin_pad)
     H, W = (2 * src.h, 2 * src.w) if upsample else (src.h, src.w)
     assert (dy.n, dy.h, dy.w) == (src.n, H, W) and dy.channels >= (cout + 7) // 8 * 8
-    dev = src.device
-    if out is not None:
-        return _wgrad_launch(lib, src, dy, cout, cin, first_seg, seg, cin_pad, upsample, scale, H, W, out[0], out[1], 1)
-    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=dev)
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_bias else None
-    _wgrad_launch(lib, src, dy, cout, cin, first_seg, seg, cin_pad, upsample, scale, H, W, dw.data_ptr(),
-                  db.data_ptr() if db is not None else None, 0)
-    return dw, db
-
-
-def _wgrad_launch(lib, src, dy, cout, cin, first_seg, seg, cin_pad, upsample, scale, H, W, dw_ptr, db_ptr, accumulate):
-    dev = src.device
-    nbytes = lib.sr_conv3x3_wgrad_slab_bytes(src.n, H, W)
-    slab = scratch(dev, nbytes, 'slab')
-    d = _lib.WgradDesc()
-    d.x, d.x_img_stride, d.cin_pad, d.in_h, d.in_w, d.upsample = src.ptr, src.img_stride, cin_pad, src.h, src.w, int(upsample)
-    d.dy, d.dy_img_stride = dy.ptr, dy.img_stride
-    d.cout, d.cin, d.first_seg, d.seg, d.n, d.scale = cout, cin, first_seg, seg, src.n, scale
-    d.dweight, d.dbias, d.accumulate = dw_ptr, db_ptr, accumulate
-    d.slab, d.slab_bytes = slab.data_ptr(), nbytes
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_conv3x3_wgrad_f32(C.byref(d), _stream(dev)), 'sr_conv3x3_wgrad_f32')
+    dw, db, target = _wgrad_targets(out, (cout, cin, 3, 3), want_bias, src.device)
+    d = _wgrad_desc(_lib.WgradDesc(), src, dy, cin_pad, upsample, cout, cin, first_seg, seg, scale, target,
+                    lib.sr_conv3x3_wgrad_slab_bytes(src.n, H, W))
+    launch('sr_conv3x3_wgrad_f32', src.device, C.byref(d))
+    return None if out is not None else (dw, db)
 
 
 def upsample2x_bwd(g, mask=None, mask_slope=0.2):
     """2x2-sum backward of the nearest upsample (+ optional LeakyReLU backward) — sr_upsample2x_bwd_f32."""
-    lib = _lib.load()
     assert g.h % 2 == 0 and g.w % 2 == 0
     out = CB8.empty(g.n, g.channels, g.h // 2, g.w // 2, g.device)
-    with torch.cuda.device(g.device):
-        _lib.check(lib.sr_upsample2x_bwd_f32(g.ptr, g.img_stride, out.ptr, out.img_stride,
-                                             mask.ptr if mask is not None else None,
-                                             mask.img_stride if mask is not None else 0, mask_slope, g.n, g.cbn,
-                                             out.h, out.w, _stream(g.device)), 'sr_upsample2x_bwd_f32')
+    launch('sr_upsample2x_bwd_f32', g.device, g.ptr, g.img_stride, out.ptr, out.img_stride,
+           mask.ptr if mask is not None else None, mask.img_stride if mask is not None else 0, mask_slope, g.n, g.cbn, out.h,
+           out.w)
     return out
 
 
 def cb8_axpby(dst, src, a=1.0, b=1.0):
     """dst = a*dst + b*src on CB8 windows — sr_cb8_axpby_f32."""
-    lib = _lib.load()
     assert (dst.n, dst.cbn, dst.h, dst.w) == (src.n, src.cbn, src.h, src.w)
-    with torch.cuda.device(dst.device):
-        _lib.check(lib.sr_cb8_axpby_f32(dst.ptr, dst.img_stride, src.ptr, src.img_stride, a, b, dst.n, dst.cbn, dst.h,
-                                        dst.w, _stream(dst.device)), 'sr_cb8_axpby_f32')
+    launch('sr_cb8_axpby_f32', dst.device, dst.ptr, dst.img_stride, src.ptr, src.img_stride, a, b, dst.n, dst.cbn, dst.h, dst.w)
     return dst
 
 
 def pixel_shuffle(src, channels, r):
     """nn.PixelShuffle(r) on CB8 (r in {2, 3}): ``src`` holds r*r*channels real channels -> CB8 of ``channels`` at r x the
     size — sr_cb8_pixel_shuffle_f32."""
-    lib = _lib.load()
     assert src.channels >= channels * r * r
     out = CB8.empty(src.n, channels, src.h * r, src.w * r, src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_cb8_pixel_shuffle_f32(src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, src.h, src.w, r,
-                                                _stream(src.device)), 'sr_cb8_pixel_shuffle_f32')
+    launch('sr_cb8_pixel_shuffle_f32', src.device, src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, src.h,
+           src.w, r)
     return out
 
 
 def pixel_unshuffle(src, channels, r):
     """nn.PixelUnshuffle(r) on CB8, the shuffle's backward: ``channels`` real channels of ``src`` -> CB8 of r*r*channels at
     1/r of the size — sr_cb8_pixel_unshuffle_f32."""
-    lib = _lib.load()
     assert src.channels >= channels and src.h % r == 0 and src.w % r == 0
     out = CB8.empty(src.n, channels * r * r, src.h // r, src.w // r, src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_cb8_pixel_unshuffle_f32(src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, out.h, out.w, r,
-                                                  _stream(src.device)), 'sr_cb8_pixel_unshuffle_f32')
+    launch('sr_cb8_pixel_unshuffle_f32', src.device, src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, out.h,
+           out.w, r)
     return out
 
 
@@ -303,16 +367,13 @@ def bilinear_up(x, s, out=None):
     """F.interpolate(x, scale_factor=s, mode='bilinear', align_corners=False) on NCHW fp32, s in {2, 3, 4} —
     sr_bilinear_up_f32.  ``out``: an NCHW tensor [N, C, s*H, s*W] the result is ADDED into (returned)."""
     _need_cuda(x, 'bilinear_up')
-    lib = _lib.load()
     x = x.contiguous().float()
     n, c, h, w = x.shape
     acc = out is not None
     if out is None:
         out = torch.empty((n, c, h * s, w * s), dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (n, c, h * s, w * s)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sr_bilinear_up_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, s, int(acc), _stream(x.device)),
-                   'sr_bilinear_up_f32')
+    launch('sr_bilinear_up_f32', x.device, x.data_ptr(), out.data_ptr(), n, c, h, w, s, int(acc))
     return out
 
 
@@ -320,7 +381,6 @@ def bilinear_up_bwd(g, s, out=None):
     """Adjoint of bilinear_up (gather form, bit-reproducible): g [N, C, s*H, s*W] -> [N, C, H, W] — sr_bilinear_up_bwd_f32.
     ``out``: an NCHW tensor the result is ADDED into (returned)."""
     _need_cuda(g, 'bilinear_up_bwd')
-    lib = _lib.load()
     g = g.contiguous().float()
     n, c, hh, ww = g.shape
     assert hh % s == 0 and ww % s == 0
@@ -329,9 +389,7 @@ def bilinear_up_bwd(g, s, out=None):
     if out is None:
         out = torch.empty((n, c, h, w), dtype=torch.float32, device=g.device)
     assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (n, c, h, w)
-    with torch.cuda.device(g.device):
-        _lib.check(lib.sr_bilinear_up_bwd_f32(g.data_ptr(), out.data_ptr(), n, c, h, w, s, int(acc), _stream(g.device)),
-                   'sr_bilinear_up_bwd_f32')
+    launch('sr_bilinear_up_bwd_f32', g.device, g.data_ptr(), out.data_ptr(), n, c, h, w, s, int(acc))
     return out
 
 
@@ -352,22 +410,18 @@ def ca_squeeze(u, w1, b1, w2, b2):
     hb = torch.empty((n, hid), dtype=torch.float32, device=dev)
     s = torch.empty((n, nf), dtype=torch.float32, device=dev)
     ws, nbytes = _ca_workspace(lib, dev, n, nf, hid, u.h, u.w)
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_ca_squeeze_f32(u.ptr, u.img_stride, n, nf, u.h, u.w, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                         b2.data_ptr(), hid, p.data_ptr(), hb.data_ptr(), s.data_ptr(), ws.data_ptr(), nbytes,
-                                         _stream(dev)), 'sr_ca_squeeze_f32')
+    launch('sr_ca_squeeze_f32', dev, u.ptr, u.img_stride, n, nf, u.h, u.w, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+           b2.data_ptr(), hid, p.data_ptr(), hb.data_ptr(), s.data_ptr(), ws.data_ptr(), nbytes)
     return p, hb, s
 
 
 def ca_excite(x, u, s, res_scale=1.0, out=None):
     """out = x + res_scale * (u * s[n][c]) on CB8 (out allocated if None; may be x) — sr_ca_excite_f32."""
-    lib = _lib.load()
     if out is None:
         out = CB8.empty(u.n, u.channels, u.h, u.w, u.device)
     assert x.channels == u.channels == out.channels and s.is_contiguous()
-    with torch.cuda.device(u.device):
-        _lib.check(lib.sr_ca_excite_f32(x.ptr, x.img_stride, u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n,
-                                        u.channels, u.h, u.w, float(res_scale), _stream(u.device)), 'sr_ca_excite_f32')
+    launch('sr_ca_excite_f32', u.device, x.ptr, x.img_stride, u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n,
+           u.channels, u.h, u.w, float(res_scale))
     return out
 
 
@@ -382,52 +436,38 @@ def ca_bwd(g, u, res_scale, w1, w2, p, hb, s, grads=None, accumulate=False):
     q = torch.empty((n, nf), dtype=torch.float32, device=dev)
     ws, nbytes = _ca_workspace(lib, dev, n, nf, hid, u.h, u.w)
     d = tuple(grads) if grads is not None else (None, None, None, None)
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_ca_bwd_f32(g.ptr, g.img_stride, u.ptr, u.img_stride, n, nf, u.h, u.w, float(res_scale), w1.data_ptr(),
-                                     w2.data_ptr(), hid, p.data_ptr(), hb.data_ptr(), s.data_ptr(), d[0], d[1], d[2], d[3],
-                                     int(accumulate), q.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)), 'sr_ca_bwd_f32')
+    launch('sr_ca_bwd_f32', dev, g.ptr, g.img_stride, u.ptr, u.img_stride, n, nf, u.h, u.w, float(res_scale), w1.data_ptr(),
+           w2.data_ptr(), hid, p.data_ptr(), hb.data_ptr(), s.data_ptr(), d[0], d[1], d[2], d[3], int(accumulate), q.data_ptr(),
+           ws.data_ptr(), nbytes)
     return q
 
 
 def ca_bwd_apply(g, s, q, res_scale=1.0, out=None):
     """du = (res_scale * g) * s[n][c] + q[n][c] on CB8 (out allocated if None; may be g) — sr_ca_bwd_apply_f32."""
-    lib = _lib.load()
     if out is None:
         out = CB8.empty(g.n, g.channels, g.h, g.w, g.device)
     assert out.channels == g.channels
-    with torch.cuda.device(g.device):
-        _lib.check(lib.sr_ca_bwd_apply_f32(g.ptr, g.img_stride, s.data_ptr(), q.data_ptr(), out.ptr, out.img_stride, g.n, g.channels,
-                                           g.h, g.w, float(res_scale), _stream(g.device)), 'sr_ca_bwd_apply_f32')
+    launch('sr_ca_bwd_apply_f32', g.device, g.ptr, g.img_stride, s.data_ptr(), q.data_ptr(), out.ptr, out.img_stride, g.n,
+           g.channels, g.h, g.w, float(res_scale))
     return out
 
 
 # ---- RIDNet: dilated 3x3 / 1x1 convolutions, the MeanShift ends, attention scale (include/sr_hip_ridnet.h) ----
 
-class PackedConvK:
+class PackedConvK(_PackedWeights):
     """MFMA operand image of a k x k conv, k in {1, 3}, dense cin (sr_convk_pack_f32); mode 1 = data gradient.  A 3x3 image
     serves every dilation."""
 
     def __init__(self, weight, bias=None, mode=0):
-        _need_cuda(weight, 'PackedConvK')
-        lib = _lib.load()
-        weight = weight.detach().contiguous().float()
-        cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+        super().__init__(weight, bias, mode)
+
+    def _cin_pad(self, lib, weight, first_seg, seg):
         assert weight.shape[2:] in ((1, 1), (3, 3)), weight.shape
-        self.ksize, self.mode = k, mode
-        if mode == 0:
-            self.cout, self.src_channels = cout, (cin + 7) // 8 * 8
-        else:
-            self.cout, self.src_channels = (cin + 7) // 8 * 8, (cout + 7) // 8 * 8
-        dev = weight.device
-        self.w = torch.empty(lib.sr_convk_packed_weight_floats(cout, cin, k, mode), dtype=torch.float32, device=dev)
-        self.b = None
-        if mode == 0 and bias is not None:
-            bias = bias.detach().contiguous().float()
-            self.b = torch.empty(lib.sr_conv3x3_packed_bias_floats(cout), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_convk_pack_f32(weight.data_ptr(), bias.data_ptr() if self.b is not None else None, cout, cin, k, mode,
-                                             self.w.data_ptr(), self.b.data_ptr() if self.b is not None else None, _stream(dev)),
-                       'sr_convk_pack_f32')
+        self.ksize = weight.shape[2]
+        return (weight.shape[1] + 7) // 8 * 8
+
+    def _image(self, lib, cout, cin, first_seg, seg, mode):
+        return lib.sr_convk_packed_weight_floats(cout, cin, self.ksize, mode), 'sr_convk_pack_f32', (cout, cin, self.ksize, mode)
 
 
 def convd(src, pc, dilation=1, out=None, *, post_act=False, out_pre=None, **kw):
@@ -435,15 +475,13 @@ def convd(src, pc, dilation=1, out=None, *, post_act=False, out_pre=None, **kw):
     post_act False: out = alpha*act(conv+bias) + beta1*res1 + beta2*res2 (conv3x3's epilogue); True: out = act(alpha*(conv+bias) +
     beta1*res1 + beta2*res2).  ``out_pre``: a CB8 window that also receives alpha*act(conv+bias) (post_act False).  Other keywords
     as conv3x3 (act_slope, alpha, res1/beta1, res2/beta2, accumulate, mask/mask_cb0/mask_slope)."""
-    lib = _lib.load()
     base, ret = _conv_desc_f32(src, pc, out, **kw)
     d = _lib.ConvdDesc()
     d.base, d.ksize, d.dilation, d.post_act = base, getattr(pc, 'ksize', 3), int(dilation), int(post_act)
     if out_pre is not None:
         assert (out_pre.n, out_pre.h, out_pre.w) == (ret.n, ret.h, ret.w) and out_pre.channels >= ret.channels
         d.out_pre, d.out_pre_img_stride = out_pre.ptr, out_pre.img_stride
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_convd_f32(C.byref(d), _stream(src.device)), 'sr_convd_f32')
+    launch('sr_convd_f32', src.device, C.byref(d))
     return ret
 
 
@@ -454,26 +492,12 @@ def convd_wgrad(src, dy, cout, cin, ksize=3, dilation=1, *, scale=1.0, want_bias
     cin_pad = (cin + 7) // 8 * 8
     assert src.channels == cin_pad, (src.channels, cin_pad)
     assert (dy.n, dy.h, dy.w) == (src.n, src.h, src.w) and dy.channels >= (cout + 7) // 8 * 8
-    dev = src.device
-    if out is not None:
-        dw_ptr, db_ptr, acc = out[0], out[1], 1
-        dw = db = None
-    else:
-        dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=dev)
-        db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_bias else None
-        dw_ptr, db_ptr, acc = dw.data_ptr(), (db.data_ptr() if db is not None else None), 0
-    nbytes = lib.sr_convd_wgrad_slab_bytes(src.n, src.h, src.w, cout, cin, ksize, dilation)
-    slab = scratch(dev, nbytes, 'slab')
+    dw, db, target = _wgrad_targets(out, (cout, cin, ksize, ksize), want_bias, src.device)
     d = _lib.ConvdWgradDesc()
-    b = d.base
-    b.x, b.x_img_stride, b.cin_pad, b.in_h, b.in_w, b.upsample = src.ptr, src.img_stride, cin_pad, src.h, src.w, 0
-    b.dy, b.dy_img_stride = dy.ptr, dy.img_stride
-    b.cout, b.cin, b.first_seg, b.seg, b.n, b.scale = cout, cin, cin, 0, src.n, scale
-    b.dweight, b.dbias, b.accumulate = dw_ptr, db_ptr, acc
-    b.slab, b.slab_bytes = slab.data_ptr(), nbytes
+    _wgrad_desc(d.base, src, dy, cin_pad, False, cout, cin, cin, 0, scale, target,
+                lib.sr_convd_wgrad_slab_bytes(src.n, src.h, src.w, cout, cin, ksize, dilation))
     d.ksize, d.dilation = ksize, dilation
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_convd_wgrad_f32(C.byref(d), _stream(dev)), 'sr_convd_wgrad_f32')
+    launch('sr_convd_wgrad_f32', src.device, C.byref(d))
     return dw, db
 
 
@@ -481,25 +505,20 @@ def ridnet_sub_mean(x, w, b):
     """s = W x + b (RIDNet's sub_mean, a trainable 3-channel 1x1 conv) from NCHW fp32 ``x`` [N, 3, H, W] into a one-block CB8
     tensor (channels 3..7 zero) — sr_ridnet_sub_mean_f32."""
     _need_cuda(x, 'ridnet_sub_mean')
-    lib = _lib.load()
     n, c, h, ww = x.shape
     assert c == 3 and x.is_contiguous()
     out = CB8.empty(n, 8, h, ww, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sr_ridnet_sub_mean_f32(x.data_ptr(), w.data_ptr(), b.data_ptr(), out.ptr, out.img_stride, n, h, ww,
-                                              _stream(x.device)), 'sr_ridnet_sub_mean_f32')
+    launch('sr_ridnet_sub_mean_f32', x.device, x.data_ptr(), w.data_ptr(), b.data_ptr(), out.ptr, out.img_stride, n, h, ww)
     return out
 
 
 def ridnet_add_mean(x, t, w, b):
     """y = x + W t + b (add_mean plus RIDNet's global residual): ``x`` NCHW [N, 3, H, W], ``t`` the tail conv's CB8 output —
     sr_ridnet_add_mean_f32."""
-    lib = _lib.load()
     n, _, h, ww = x.shape
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sr_ridnet_add_mean_f32(x.data_ptr(), t.ptr, t.img_stride, w.data_ptr(), b.data_ptr(), y.data_ptr(), n, h, ww,
-                                              _stream(x.device)), 'sr_ridnet_add_mean_f32')
+    launch('sr_ridnet_add_mean_f32', x.device, x.data_ptr(), t.ptr, t.img_stride, w.data_ptr(), b.data_ptr(), y.data_ptr(), n, h,
+           ww)
     return y
 
 
@@ -518,11 +537,9 @@ def ridnet_sub_mean_bwd(x, g, w, dw=None, db=None, accumulate=False, want_dx=Fal
     ws, nbytes = _mean_ws(lib, dev, n, h, ww)
     if dx_res is not None:
         assert dx_res.is_contiguous() and dx_res.shape == x.shape
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_ridnet_sub_mean_bwd_f32(x.data_ptr(), g.ptr, g.img_stride, w.data_ptr(), dw, db, int(accumulate),
-                                                  dx.data_ptr() if dx is not None else None,
-                                                  dx_res.data_ptr() if dx_res is not None else None, n, h, ww, ws.data_ptr(), nbytes,
-                                                  _stream(dev)), 'sr_ridnet_sub_mean_bwd_f32')
+    launch('sr_ridnet_sub_mean_bwd_f32', dev, x.data_ptr(), g.ptr, g.img_stride, w.data_ptr(), dw, db, int(accumulate),
+           dx.data_ptr() if dx is not None else None, dx_res.data_ptr() if dx_res is not None else None, n, h, ww, ws.data_ptr(),
+           nbytes)
     return dx
 
 
@@ -535,98 +552,71 @@ def ridnet_add_mean_bwd(g, t, w, dw=None, db=None, accumulate=False):
     dev = g.device
     dt = CB8.empty(n, 8, h, ww, dev)
     ws, nbytes = _mean_ws(lib, dev, n, h, ww)
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_ridnet_add_mean_bwd_f32(g.data_ptr(), t.ptr, t.img_stride, w.data_ptr(), dw, db, int(accumulate), dt.ptr,
-                                                  dt.img_stride, n, h, ww, ws.data_ptr(), nbytes, _stream(dev)),
-                   'sr_ridnet_add_mean_bwd_f32')
+    launch('sr_ridnet_add_mean_bwd_f32', dev, g.data_ptr(), t.ptr, t.img_stride, w.data_ptr(), dw, db, int(accumulate), dt.ptr,
+           dt.img_stride, n, h, ww, ws.data_ptr(), nbytes)
     return dt
 
 
 def ca_scale(u, s, out=None):
     """out = u * s[n][c] on CB8 (RIDNet's channel attention, no identity) — sr_ca_scale_f32."""
-    lib = _lib.load()
     if out is None:
         out = CB8.empty(u.n, u.channels, u.h, u.w, u.device)
     assert out.channels == u.channels and s.is_contiguous() and tuple(s.shape) == (u.n, u.channels)
-    with torch.cuda.device(u.device):
-        _lib.check(lib.sr_ca_scale_f32(u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n, u.channels, u.h, u.w,
-                                       _stream(u.device)), 'sr_ca_scale_f32')
+    launch('sr_ca_scale_f32', u.device, u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n, u.channels, u.h, u.w)
     return out
 
 
 def relu_mask(g, mask, slope=0.0, out=None):
     """out = mask > 0 ? g : slope * g on CB8 windows of equal shape — sr_cb8_relu_mask_f32."""
-    lib = _lib.load()
     if out is None:
         out = CB8.empty(g.n, g.channels, g.h, g.w, g.device)
     assert (mask.n, mask.cbn, mask.h, mask.w) == (g.n, g.cbn, g.h, g.w) and out.cbn == g.cbn
-    with torch.cuda.device(g.device):
-        _lib.check(lib.sr_cb8_relu_mask_f32(g.ptr, g.img_stride, mask.ptr, mask.img_stride, float(slope), out.ptr, out.img_stride, g.n,
-                                            g.cbn, g.h, g.w, _stream(g.device)), 'sr_cb8_relu_mask_f32')
+    launch('sr_cb8_relu_mask_f32', g.device, g.ptr, g.img_stride, mask.ptr, mask.img_stride, float(slope), out.ptr,
+           out.img_stride, g.n, g.cbn, g.h, g.w)
     return out
 
 
-class PackedConv4x4s2:
+class PackedConv4x4s2(_PackedWeights):
     """Parity-pass weight images of a 4x4 / stride 2 / pad 1 conv (sr_conv4x4s2_pack_f32); mode 1 = data gradient."""
 
     def __init__(self, weight, bias=None, mode=0):
-        _need_cuda(weight, 'PackedConv4x4s2')
-        lib = _lib.load()
-        weight = weight.detach().contiguous().float()
-        cout, cin = weight.shape[:2]
+        super().__init__(weight, bias, mode)
+
+    def _cin_pad(self, lib, weight, first_seg, seg):
         assert weight.shape[2:] == (4, 4)
-        self.mode, self.conv_cout, self.conv_cin = mode, cout, cin
-        cin_pad = (cin + 7) // 8 * 8
-        if mode == 0:
-            self.cout, self.src_channels = cout, cin_pad
-        else:
-            self.cout, self.src_channels = cin_pad, (cout + 7) // 8 * 8
-        dev = weight.device
-        self.w = torch.empty(lib.sr_conv4x4s2_packed_weight_floats(cout, cin, mode), dtype=torch.float32, device=dev)
-        self.b = None
-        if mode == 0 and bias is not None:
-            bias = bias.detach().contiguous().float()
-            self.b = torch.empty(lib.sr_conv3x3_packed_bias_floats(cout), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_conv4x4s2_pack_f32(weight.data_ptr(), bias.data_ptr() if self.b is not None else None,
-                                                 cout, cin, mode, self.w.data_ptr(),
-                                                 self.b.data_ptr() if self.b is not None else None, _stream(dev)),
-                       'sr_conv4x4s2_pack_f32')
+        self.conv_cout, self.conv_cin = weight.shape[:2]
+        return (self.conv_cin + 7) // 8 * 8
+
+    def _image(self, lib, cout, cin, first_seg, seg, mode):
+        return lib.sr_conv4x4s2_packed_weight_floats(cout, cin, mode), 'sr_conv4x4s2_pack_f32', (cout, cin, mode)
 
 
 def conv4x4s2(src, pc, out=None, *, act_slope=1.0, alpha=1.0):
     """Forward 4x4/s2/p1 conv (+bias, LeakyReLU): four accumulating parity passes of sr_conv4x4s2_f32."""
-    lib = _lib.load()
     assert pc.mode == 0 and src.channels == pc.src_channels
     H, W = (src.h - 2) // 2 + 1, (src.w - 2) // 2 + 1
     if out is None:
         out = CB8.empty(src.n, pc.cout, H, W, src.device)
     d = _lib.ConvDesc()
-    d.in_, d.in_img_stride, d.cin_pad, d.in_h, d.in_w = src.ptr, src.img_stride, pc.src_channels, src.h, src.w
-    d.wpacked, d.bpacked, d.cout = pc.w.data_ptr(), (pc.b.data_ptr() if pc.b is not None else None), pc.cout
+    _conv_operands(d, src, pc)
     d.out, d.out_img_stride, d.n, d.act_slope, d.alpha = out.ptr, out.img_stride, src.n, act_slope, alpha
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_conv4x4s2_f32(C.byref(d), _stream(src.device)), 'sr_conv4x4s2_f32')
+    launch('sr_conv4x4s2_f32', src.device, C.byref(d))
     return out
 
 
 def conv4x4s2_dgrad(dy, pc, out_h, out_w, out=None, *, alpha=1.0, accumulate=False, mask=None, mask_cb0=0,
                     mask_slope=0.2):
     """dX of the 4x4/s2 conv from dY (sr_conv4x4s2_dgrad_f32)."""
-    lib = _lib.load()
     assert pc.mode == 1 and dy.channels == pc.src_channels
     if out is None:
         out = CB8.empty(dy.n, pc.cout, out_h, out_w, dy.device)
     d = _lib.ConvDesc()
-    d.in_, d.in_img_stride, d.cin_pad, d.in_h, d.in_w = dy.ptr, dy.img_stride, pc.src_channels, dy.h, dy.w
-    d.wpacked, d.cout = pc.w.data_ptr(), pc.cout
+    _conv_operands(d, dy, pc, bias=False)
     d.out, d.out_img_stride, d.out_h, d.out_w = out.ptr, out.img_stride, out_h, out_w
     d.n, d.act_slope, d.alpha, d.accumulate = dy.n, 1.0, alpha, int(accumulate)
     if mask is not None:
-        d.mask_src, d.mask_img_stride, d.mask_cb0, d.mask_cbn, d.mask_slope = (mask.ptr, mask.img_stride, mask_cb0,
-                                                                               mask.cbn, mask_slope)
-    with torch.cuda.device(dy.device):
-        _lib.check(lib.sr_conv4x4s2_dgrad_f32(C.byref(d), _stream(dy.device)), 'sr_conv4x4s2_dgrad_f32')
+        _conv_mask(d, mask, mask_cb0, mask_slope)
+    launch('sr_conv4x4s2_dgrad_f32', dy.device, C.byref(d))
     return out
 
 
@@ -637,143 +627,53 @@ def conv4x4s2_wgrad(src, dy, cout, cin, *, scale=1.0, want_bias=False):
     assert src.channels == cin_pad
     H, W = (src.h - 2) // 2 + 1, (src.w - 2) // 2 + 1
     assert (dy.n, dy.h, dy.w) == (src.n, H, W)
-    dev = src.device
-    dw = torch.zeros((cout, cin, 4, 4), dtype=torch.float32, device=dev)
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_bias else None
-    nbytes = lib.sr_conv3x3_wgrad_slab_bytes(src.n, H, W)
-    slab = scratch(dev, nbytes, 'slab')
-    d = _lib.WgradDesc()
-    d.x, d.x_img_stride, d.cin_pad, d.in_h, d.in_w, d.upsample = src.ptr, src.img_stride, cin_pad, src.h, src.w, 0
-    d.dy, d.dy_img_stride = dy.ptr, dy.img_stride
-    d.cout, d.cin, d.first_seg, d.seg, d.n, d.scale = cout, cin, cin, 0, src.n, scale
-    d.dweight, d.dbias, d.accumulate = dw.data_ptr(), (db.data_ptr() if db is not None else None), 0
-    d.slab, d.slab_bytes = slab.data_ptr(), nbytes
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_conv4x4s2_wgrad_f32(C.byref(d), _stream(dev)), 'sr_conv4x4s2_wgrad_f32')
+    dw, db, target = _wgrad_targets(None, (cout, cin, 4, 4), want_bias, src.device, zeros=True)  # the passes add into dw
+    d = _wgrad_desc(_lib.WgradDesc(), src, dy, cin_pad, False, cout, cin, cin, 0, scale, target,
+                    lib.sr_conv3x3_wgrad_slab_bytes(src.n, H, W))
+    launch('sr_conv4x4s2_wgrad_f32', src.device, C.byref(d))
     return dw, db
 
 
 # ------------------------------------------------------------------ bf16 (CB16) inference ops
-class CB16:
-    """A channel-blocked bf16 activation: storage ``buf`` [N, CB, H, W, 16] plus a channel-block window."""
-
-    def __init__(self, buf, cb0=0, cbn=None):
-        assert buf.dim() == 5 and buf.size(4) == 16 and buf.dtype == torch.bfloat16 and buf.is_contiguous()
-        self.buf, self.cb0 = buf, cb0
-        self.cbn = buf.size(1) - cb0 if cbn is None else cbn
-        assert 0 <= cb0 and cb0 + self.cbn <= buf.size(1)
-
-    @staticmethod
-    def zeros(n, channels, h, w, device):
-        return CB16(torch.zeros((n, (channels + 15) // 16, h, w, 16), dtype=torch.bfloat16, device=device))
-
-    @staticmethod
-    def empty(n, channels, h, w, device):
-        return CB16(torch.empty((n, (channels + 15) // 16, h, w, 16), dtype=torch.bfloat16, device=device))
-
-    n = property(lambda s: s.buf.size(0))
-    h = property(lambda s: s.buf.size(2))
-    w = property(lambda s: s.buf.size(3))
-    channels = property(lambda s: s.cbn * 16)
-    img_stride = property(lambda s: s.buf.size(1) * s.buf.size(2) * s.buf.size(3) * 16)
-    device = property(lambda s: s.buf.device)
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.cb0 * self.h * self.w * 16 * 2
-
-    def slice(self, c0, c):
-        assert c0 % 16 == 0 and c % 16 == 0
-        return CB16(self.buf, self.cb0 + c0 // 16, c // 16)
-
-
 def nchw_to_cb16(x, unshuffle=1):
     """fp32 NCHW -> CB16 bf16 (round-to-nearest-even), pixel_unshuffle fused — sr_nchw_to_cb16_bf16."""
-    lib = _lib.load()
     _need_cuda(x, 'nchw_to_cb16')
     x = x.contiguous().float()
     n, c, sh, sw = x.shape
     h, w = sh // unshuffle, sw // unshuffle
     out = CB16.empty(n, c * unshuffle * unshuffle, h, w, x.device)  # the kernel writes every block, pad channels as zero
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sr_nchw_to_cb16_bf16(x.data_ptr(), out.ptr, n, c, h, w, unshuffle, out.cbn, out.img_stride,
-                                            _stream(x.device)), 'sr_nchw_to_cb16_bf16')
+    launch('sr_nchw_to_cb16_bf16', x.device, x.data_ptr(), out.ptr, n, c, h, w, unshuffle, out.cbn, out.img_stride)
     return out
 
 
-def cb16_to_nchw(t, channels):
-    lib = _lib.load()
-    y = torch.empty((t.n, channels, t.h, t.w), dtype=torch.float32, device=t.device)
-    with torch.cuda.device(t.device):
-        _lib.check(lib.sr_cb16_to_nchw_f32(t.ptr, t.img_stride, y.data_ptr(), t.n, channels, t.h, t.w, 1,
-                                           _stream(t.device)), 'sr_cb16_to_nchw_f32')
-    return y
-
-
-class PackedConvBF16:
+class PackedConvBF16(_PackedWeights):
     """bf16 MFMA weight image (+ fp32 bias) of one 3x3 conv — sr_conv3x3_pack_bf16."""
+    block, wdtype = 16, torch.bfloat16
 
     def __init__(self, weight, bias=None, first_seg=None, seg=0, mode=0):
-        lib = _lib.load()
-        _need_cuda(weight, 'PackedConvBF16')
-        weight = weight.detach().contiguous().float()
-        cout, cin = weight.shape[:2]
-        first_seg = cin if first_seg is None else first_seg
+        super().__init__(weight, bias, mode, first_seg, seg)
+
+    def _cin_pad(self, lib, weight, first_seg, seg):
+        cin = weight.shape[1]
         self.cin_pad = lib.sr_conv3x3_cin_pad16(cin, first_seg, seg)
         if self.cin_pad <= 0:
             raise ValueError(f'cin={cin} is not first_seg={first_seg} + k*seg={seg}')
-        if mode == 0:
-            self.cout, self.src_channels = cout, self.cin_pad
-        else:  # data-gradient image: consumes dY (cout channels, padded to 16), produces the cin_pad source channels
-            self.cout, self.src_channels = self.cin_pad, (cout + 15) // 16 * 16
-        dev = weight.device
-        self.w = torch.empty(lib.sr_conv3x3_packed_weight_elems_bf16(cout, cin, first_seg, seg, mode), dtype=torch.bfloat16,
-                             device=dev)
-        self.b = None
-        if mode == 0 and bias is not None:
-            bias = bias.detach().contiguous().float()
-            self.b = torch.empty(lib.sr_conv3x3_packed_bias_floats(cout), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_conv3x3_pack_bf16(weight.data_ptr(), bias.data_ptr() if self.b is not None else None, cout,
-                                                cin, first_seg, seg, mode, self.w.data_ptr(),
-                                                self.b.data_ptr() if self.b is not None else None, _stream(dev)),
-                       'sr_conv3x3_pack_bf16')
+        return self.cin_pad
+
+    def _image(self, lib, cout, cin, first_seg, seg, mode):
+        return (lib.sr_conv3x3_packed_weight_elems_bf16(cout, cin, first_seg, seg, mode), 'sr_conv3x3_pack_bf16',
+                (cout, cin, first_seg, seg, mode))
 
 
 def _conv_desc_bf16(src, pc, out=None, *, upsample=False, act_slope=1.0, alpha=1.0, res1=None, beta1=0.0, res2=None,
                     beta2=0.0, out_nchw=None, mask=None, mask_slope=0.2, s2_channels=0, s2_side=0, out_unshuffle2=False,
                     res1_u2=False, res1_keep_sign=False):
-    assert src.channels == pc.src_channels, (src.channels, pc.src_channels)
-    H, W = (2 * src.h, 2 * src.w) if upsample else (src.h, src.w)
-    d = _lib.ConvDesc()
-    d.in_, d.in_img_stride, d.cin_pad, d.in_h, d.in_w = src.ptr, src.img_stride, pc.src_channels, src.h, src.w
-    d.upsample = int(upsample)
-    d.wpacked, d.bpacked, d.cout = pc.w.data_ptr(), (pc.b.data_ptr() if pc.b is not None else None), pc.cout
+    assert out_nchw is None or out_nchw.dtype == torch.float32
+    d, ret = _conv_desc(src, pc, out, upsample, act_slope, alpha, res1, beta1, res2, beta2, out_nchw, mask, 0, mask_slope,
+                        out_unshuffle2)
     d.s2_channels, d.s2_side = s2_channels, s2_side
-    if out_nchw is not None:
-        assert out_nchw.is_contiguous() and out_nchw.dtype == torch.float32 and out_nchw.shape == (src.n, pc.cout, H, W)
-        d.out, d.out_img_stride, d.out_nchw = out_nchw.data_ptr(), pc.cout * H * W, 1
-        ret = out_nchw
-    elif out_unshuffle2:
-        # the destination only exists pixel-unshuffled: [n][4 cout / 16][H / 2][W / 2][16] (sr_conv3x3_desc.out_unshuffle2)
-        assert out is None and pc.cout % 16 == 0 and H % 2 == 0 and W % 2 == 0
-        out = CB16.empty(src.n, 4 * pc.cout, H // 2, W // 2, src.device)
-        d.out, d.out_img_stride, d.out_nchw, d.out_unshuffle2 = out.ptr, out.img_stride, 0, 1
-        ret = out
-    else:
-        if out is None:
-            out = CB16.empty(src.n, pc.cout, H, W, src.device)  # every valid block is written (pad couts: zero weights)
-        assert (out.n, out.h, out.w) == (src.n, H, W) and out.channels >= (pc.cout + 15) // 16 * 16
-        d.out, d.out_img_stride, d.out_nchw = out.ptr, out.img_stride, 0
-        ret = out
-    d.n, d.act_slope, d.alpha = src.n, act_slope, alpha
     if res1 is not None:
-        d.res1, d.res1_img_stride, d.beta1 = res1.ptr, res1.img_stride, beta1
         d.res1_u2, d.res1_keep_sign = int(res1_u2), int(res1_keep_sign)
-    if res2 is not None:
-        d.res2, d.res2_img_stride, d.beta2 = res2.ptr, res2.img_stride, beta2
-    if mask is not None:
-        d.mask_src, d.mask_img_stride, d.mask_cb0, d.mask_cbn, d.mask_slope = mask.ptr, mask.img_stride, 0, mask.cbn, mask_slope
     return d, ret
 
 
@@ -782,10 +682,8 @@ def conv3x3_bf16(src, pc, out=None, **kw):
     Keywords: upsample, act_slope, alpha, res1/beta1, res2/beta2, out_nchw, mask/mask_slope, s2_channels/s2_side
     (s2_channels = C marks a 4x4/s2 conv carried on a pixel-unshuffled operand of 4C channels: zero taps are skipped),
     out_unshuffle2 (the result is stored pixel-unshuffled only: [n][4 cout / 16][H / 2][W / 2][16])."""
-    lib = _lib.load()
     d, ret = _conv_desc_bf16(src, pc, out, **kw)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_conv3x3_bf16(C.byref(d), _stream(src.device)), 'sr_conv3x3_bf16')
+    launch('sr_conv3x3_bf16', src.device, C.byref(d))
     return ret
 
 
@@ -793,18 +691,7 @@ def conv3x3_chain_bf16(steps, sync=None, call_index=0):
     """A dependency chain of convs as one persistent launch — sr_conv3x3_chain_bf16.  ``steps`` = [(src, pc, out, kwargs), ...] in
     execution order (conv k reads what earlier convs wrote); ``sync`` = int32 tensor of sr_conv3x3_chain_sync_ints(n, h, w) zeros
     (created when None).  Returns (outputs, sync); sync[0] != 0 after a synchronisation means a dependency wait timed out."""
-    lib = _lib.load()
-    src0 = steps[0][0]
-    if sync is None:
-        sync = torch.zeros(lib.sr_conv3x3_chain_sync_ints(src0.n, src0.h, src0.w), dtype=torch.int32, device=src0.device)
-    descs = (_lib.ConvDesc * len(steps))()
-    outs = []
-    for i, (src, pc, out, kw) in enumerate(steps):
-        descs[i], ret = _conv_desc_bf16(src, pc, out, **kw)
-        outs.append(ret)
-    with torch.cuda.device(src0.device):
-        _lib.check(lib.sr_conv3x3_chain_bf16(descs, len(steps), sync.data_ptr(), call_index, _stream(src0.device)), 'sr_conv3x3_chain_bf16')
-    return outs, sync
+    return _conv_chain('sr_conv3x3_chain_bf16', _conv_desc_bf16, steps, sync, call_index)
 
 
 def conv3x3_wgrad_bf16(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=False, scale=1.0, want_bias=True):
@@ -815,19 +702,10 @@ def conv3x3_wgrad_bf16(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=Fa
     assert src.channels == cin_pad, (src.channels, cin_pad)
     H, W = (2 * src.h, 2 * src.w) if upsample else (src.h, src.w)
     assert (dy.n, dy.h, dy.w) == (src.n, H, W) and dy.channels >= (cout + 15) // 16 * 16
-    dev = src.device
-    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=dev)
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if want_bias else None
-    nbytes = lib.sr_conv3x3_wgrad_slab_bytes_bf16(src.n, H, W)
-    slab = scratch(dev, nbytes, 'slab16')
-    d = _lib.WgradDesc()
-    d.x, d.x_img_stride, d.cin_pad, d.in_h, d.in_w, d.upsample = src.ptr, src.img_stride, cin_pad, src.h, src.w, int(upsample)
-    d.dy, d.dy_img_stride = dy.ptr, dy.img_stride
-    d.cout, d.cin, d.first_seg, d.seg, d.n, d.scale = cout, cin, first_seg, seg, src.n, scale
-    d.dweight, d.dbias, d.accumulate = dw.data_ptr(), (db.data_ptr() if db is not None else None), 0
-    d.slab, d.slab_bytes = slab.data_ptr(), nbytes
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_conv3x3_wgrad_bf16(C.byref(d), _stream(dev)), 'sr_conv3x3_wgrad_bf16')
+    dw, db, target = _wgrad_targets(None, (cout, cin, 3, 3), want_bias, src.device)
+    d = _wgrad_desc(_lib.WgradDesc(), src, dy, cin_pad, upsample, cout, cin, first_seg, seg, scale, target,
+                    lib.sr_conv3x3_wgrad_slab_bytes_bf16(src.n, H, W), 'slab16')
+    launch('sr_conv3x3_wgrad_bf16', src.device, C.byref(d))
     return dw, db
 
 
@@ -836,14 +714,12 @@ def conv3x3_wgrad_bf16(src, dy, cout, cin, first_seg=None, seg=0, *, upsample=Fa
 def pixel_shuffle_bf16(src, channels, r, out=None):
     """nn.PixelShuffle(r) on CB16 (r in {2, 3}): ``src`` holds r*r*channels real channels -> CB16 of ``channels`` at r x the
     size — sr_cb16_pixel_shuffle_bf16."""
-    lib = _lib.load()
     assert src.channels >= channels * r * r
     if out is None:
         out = CB16.empty(src.n, channels, src.h * r, src.w * r, src.device)
     assert (out.n, out.h, out.w) == (src.n, src.h * r, src.w * r) and out.channels >= channels
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_cb16_pixel_shuffle_bf16(src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, src.h, src.w,
-                                                  r, _stream(src.device)), 'sr_cb16_pixel_shuffle_bf16')
+    launch('sr_cb16_pixel_shuffle_bf16', src.device, src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, channels, src.h,
+           src.w, r)
     return out
 
 
@@ -851,27 +727,22 @@ def edsr_shift_in(x, mean, img_range, bf16=False):
     """(x - mean[c]) * img_range of an NCHW fp32 image [N, 3, H, W] into a one-block CB8 (fp32) or CB16 (bf16) tensor, pad
     channels zero — sr_edsr_shift_in_f32 / sr_edsr_shift_in_bf16.  ``mean``: three Python floats."""
     _need_cuda(x, 'edsr_shift_in')
-    lib = _lib.load()
     n, c, h, w = x.shape
     assert c == 3 and x.is_contiguous() and x.dtype == torch.float32 and len(mean) == 3
     out = (CB16 if bf16 else CB8).empty(n, 3, h, w, x.device)
     m = (C.c_float * 3)(*mean)
-    fn, name = (lib.sr_edsr_shift_in_bf16, 'sr_edsr_shift_in_bf16') if bf16 else (lib.sr_edsr_shift_in_f32, 'sr_edsr_shift_in_f32')
-    with torch.cuda.device(x.device):
-        _lib.check(fn(x.data_ptr(), out.ptr, out.img_stride, m, float(img_range), n, h, w, _stream(x.device)), name)
+    launch('sr_edsr_shift_in_bf16' if bf16 else 'sr_edsr_shift_in_f32', x.device, x.data_ptr(), out.ptr, out.img_stride, m,
+           float(img_range), n, h, w)
     return out
 
 
 def edsr_shift_out(y, mean, img_range):
     """y = y / img_range + mean[c] in place on an NCHW fp32 image [N, 3, H, W] — sr_edsr_shift_out_f32."""
     _need_cuda(y, 'edsr_shift_out')
-    lib = _lib.load()
     n, c, h, w = y.shape
     assert c == 3 and y.is_contiguous() and y.dtype == torch.float32 and len(mean) == 3
     m = (C.c_float * 3)(*mean)
-    with torch.cuda.device(y.device):
-        _lib.check(lib.sr_edsr_shift_out_f32(y.data_ptr(), m, float(img_range), n, h, w, _stream(y.device)),
-                   'sr_edsr_shift_out_f32')
+    launch('sr_edsr_shift_out_f32', y.device, y.data_ptr(), m, float(img_range), n, h, w)
     return y
 
 
@@ -889,23 +760,19 @@ def ca_squeeze_bf16(u, w1, b1, w2, b2):
     s = torch.empty((n, nf), dtype=torch.float32, device=dev)
     nbytes = lib.sr_ca_workspace_bytes_bf16(n, nf, hid, u.h, u.w)
     ws = scratch(dev, nbytes, 'ca16')
-    with torch.cuda.device(dev):
-        _lib.check(lib.sr_ca_squeeze_bf16(u.ptr, u.img_stride, n, nf, u.h, u.w, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                          b2.data_ptr(), hid, None, None, s.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)),
-                   'sr_ca_squeeze_bf16')
+    launch('sr_ca_squeeze_bf16', dev, u.ptr, u.img_stride, n, nf, u.h, u.w, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+           b2.data_ptr(), hid, None, None, s.data_ptr(), ws.data_ptr(), nbytes)
     return s
 
 
 def ca_excite_bf16(x, u, s, res_scale=1.0, out=None):
     """out = bf16(x + res_scale * (u * s[n][c])) on CB16, evaluated in fp32 and rounded once (out allocated if None; may be x)
     — sr_ca_excite_bf16."""
-    lib = _lib.load()
     if out is None:
         out = CB16.empty(u.n, u.channels, u.h, u.w, u.device)
     assert x.channels == u.channels == out.channels and s.is_contiguous() and s.dtype == torch.float32
-    with torch.cuda.device(u.device):
-        _lib.check(lib.sr_ca_excite_bf16(x.ptr, x.img_stride, u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n,
-                                         u.channels, u.h, u.w, float(res_scale), _stream(u.device)), 'sr_ca_excite_bf16')
+    launch('sr_ca_excite_bf16', u.device, x.ptr, x.img_stride, u.ptr, u.img_stride, s.data_ptr(), out.ptr, out.img_stride, u.n,
+           u.channels, u.h, u.w, float(res_scale))
     return out
 
 
@@ -913,26 +780,21 @@ def ca_excite_bf16(x, u, s, res_scale=1.0, out=None):
 
 def bilinear2x(src, out=None):
     """F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) on a CB8 window — sr_bilinear2x_fwd_f32."""
-    lib = _lib.load()
     if out is None:
         out = CB8.empty(src.n, src.channels, 2 * src.h, 2 * src.w, src.device)
     assert (out.n, out.cbn, out.h, out.w) == (src.n, src.cbn, 2 * src.h, 2 * src.w)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_bilinear2x_fwd_f32(src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, src.cbn, src.h, src.w,
-                                             _stream(src.device)), 'sr_bilinear2x_fwd_f32')
+    launch('sr_bilinear2x_fwd_f32', src.device, src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, src.cbn, src.h, src.w)
     return out
 
 
 def cb8_channel_scale(u, s, n, out=None):
     """out[n] = u[n or 0] * s[n][c] (sr_ca_scale_f32): ``u`` with one image is repeated over the batch of ``n`` (image stride 0),
     as the decoder's constant input."""
-    lib = _lib.load()
     assert u.n in (1, n) and s.is_contiguous() and tuple(s.shape) == (n, u.channels)
     if out is None:
         out = CB8.empty(n, u.channels, u.h, u.w, u.device)
-    with torch.cuda.device(u.device):
-        _lib.check(lib.sr_ca_scale_f32(u.ptr, 0 if u.n == 1 else u.img_stride, s.data_ptr(), out.ptr, out.img_stride, n, u.channels,
-                                       u.h, u.w, _stream(u.device)), 'sr_ca_scale_f32')
+    launch('sr_ca_scale_f32', u.device, u.ptr, 0 if u.n == 1 else u.img_stride, s.data_ptr(), out.ptr, out.img_stride, n,
+           u.channels, u.h, u.w)
     return out
 
 
@@ -960,95 +822,76 @@ def gfpgan_tail(demod, noise=None, noise_strength=0.0, sft=None, sft_c0=0, s_nex
 def gfpgan_modconv(src, pc, tail, out=None, act_slope=0.2, alpha=2 ** 0.5):
     """One StyleConv at the source's size — sr_gfpgan_modconv_f32.  ``src``: CB8 x * s[n]; ``pc``: PackedConvK (3x3) of the
     shared weight with the StyleConv's activation bias; ``tail``: gfpgan_tail(...)."""
-    lib = _lib.load()
     base, ret = _conv_desc_f32(src, pc, out, act_slope=act_slope, alpha=alpha)
     d = _lib.GfpganModconvDesc()
     d.base, d.tail = base, tail
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_gfpgan_modconv_f32(C.byref(d), _stream(src.device)), 'sr_gfpgan_modconv_f32')
+    launch('sr_gfpgan_modconv_f32', src.device, C.byref(d))
     return ret
 
 
 def gfpgan_upconv(src, pc, out=None):
     """conv_transpose2d(src, W^T, stride 2) as four output parities -> the raw CB8 map of (2h+1) x (2w+1) —
     sr_gfpgan_upconv_f32."""
-    lib = _lib.load()
     assert src.channels == pc.src_channels and pc.ksize == 3
     if out is None:
         out = CB8.empty(src.n, pc.cout, 2 * src.h + 1, 2 * src.w + 1, src.device)
     assert (out.n, out.h, out.w) == (src.n, 2 * src.h + 1, 2 * src.w + 1) and out.channels >= pc.cout
     d = _lib.GfpganModconvDesc()
-    b = d.base
-    b.in_, b.in_img_stride, b.cin_pad, b.in_h, b.in_w = src.ptr, src.img_stride, pc.src_channels, src.h, src.w
-    b.wpacked, b.cout, b.out, b.out_img_stride, b.n = pc.w.data_ptr(), pc.cout, out.ptr, out.img_stride, src.n
-    with torch.cuda.device(src.device):
-        _lib.check(lib.sr_gfpgan_upconv_f32(C.byref(d), _stream(src.device)), 'sr_gfpgan_upconv_f32')
+    _conv_operands(d.base, src, pc, bias=False)
+    d.base.out, d.base.out_img_stride, d.base.n = out.ptr, out.img_stride, src.n
+    launch('sr_gfpgan_upconv_f32', src.device, C.byref(d))
     return out
 
 
 def gfpgan_blur_up(t, bias, tail, out=None, act_slope=0.2, alpha=2 ** 0.5):
     """The upsampling StyleConv's blur ([1,3,3,1]^2 / 64 * 4, pad 1) and tail: t (2h+1) x (2w+1) -> CB8 2h x 2w —
     sr_gfpgan_blur_up_f32.  ``bias``: the activation bias [cout] (contiguous fp32)."""
-    lib = _lib.load()
     h, w = (t.h - 1) // 2, (t.w - 1) // 2
     assert t.h == 2 * h + 1 and t.w == 2 * w + 1 and bias.is_contiguous()
     cout = bias.numel()
     if out is None:
         out = CB8.empty(t.n, cout, 2 * h, 2 * w, t.device)
     assert (out.n, out.h, out.w) == (t.n, 2 * h, 2 * w) and out.channels == cout == t.channels
-    with torch.cuda.device(t.device):
-        _lib.check(lib.sr_gfpgan_blur_up_f32(t.ptr, t.img_stride, out.ptr, out.img_stride, bias.data_ptr(), act_slope, alpha,
-                                             C.byref(tail), t.n, cout, h, w, _stream(t.device)), 'sr_gfpgan_blur_up_f32')
+    launch('sr_gfpgan_blur_up_f32', t.device, t.ptr, t.img_stride, out.ptr, out.img_stride, bias.data_ptr(), act_slope, alpha,
+           C.byref(tail), t.n, cout, h, w)
     return out
 
 
 def gfpgan_torgb(x, w, wscale, s, bias, skip=None, s_next=None):
     """ToRGB of the decoder: y [N, 3, H, W] (NCHW) = modulated 1x1 (no demodulation) + bias + upfirdn2d(skip, up 2); with
     ``s_next`` also x * s_next[n] (CB8), the next level's modulated input — sr_gfpgan_torgb_f32.  Returns (y, x_next or None)."""
-    lib = _lib.load()
     n, c = x.n, x.channels
     assert w.is_contiguous() and tuple(w.shape) == (3, c) and s.is_contiguous() and tuple(s.shape) == (n, c)
     y = torch.empty((n, 3, x.h, x.w), dtype=torch.float32, device=x.device)
     if skip is not None:
         assert skip.is_contiguous() and tuple(skip.shape) == (n, 3, x.h // 2, x.w // 2)
     xn = CB8.empty(n, c, x.h, x.w, x.device) if s_next is not None else None
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sr_gfpgan_torgb_f32(x.ptr, x.img_stride, w.data_ptr(), float(wscale), s.data_ptr(), bias.data_ptr(),
-                                           skip.data_ptr() if skip is not None else None, y.data_ptr(),
-                                           xn.ptr if xn is not None else None, xn.img_stride if xn is not None else 0,
-                                           s_next.data_ptr() if s_next is not None else None, n, c, x.h, x.w,
-                                           _stream(x.device)), 'sr_gfpgan_torgb_f32')
+    launch('sr_gfpgan_torgb_f32', x.device, x.ptr, x.img_stride, w.data_ptr(), float(wscale), s.data_ptr(), bias.data_ptr(),
+           skip.data_ptr() if skip is not None else None, y.data_ptr(), xn.ptr if xn is not None else None,
+           xn.img_stride if xn is not None else 0, s_next.data_ptr() if s_next is not None else None, n, c, x.h, x.w)
     return y, xn
 
 
 def gfpgan_style(latent, img_stride, row_stride, nsf, layers, n):
     """Every layer's modulation s and demodulation d in one sr_gfpgan_style_f32 launch.  ``layers``: a ctypes array of
     _lib.GfpganStyleLayer whose s / d pointers name the outputs."""
-    lib = _lib.load()
-    with torch.cuda.device(latent.device):
-        _lib.check(lib.sr_gfpgan_style_f32(latent.data_ptr(), img_stride, row_stride, nsf, layers, len(layers), n,
-                                           _stream(latent.device)), 'sr_gfpgan_style_f32')
+    launch('sr_gfpgan_style_f32', latent.device, latent.data_ptr(), img_stride, row_stride, nsf, layers, len(layers), n)
 
 
 def gfpgan_norm_style(x, out=None):
     """NormStyleCode on rows of a contiguous [N, nsf] tensor — sr_gfpgan_norm_style_f32."""
     _need_cuda(x, 'gfpgan_norm_style')
-    lib = _lib.load()
     assert x.is_contiguous() and x.dim() == 2 and x.dtype == torch.float32
     out = torch.empty_like(x) if out is None else out
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sr_gfpgan_norm_style_f32(x.data_ptr(), out.data_ptr(), x.size(0), x.size(1), _stream(x.device)),
-                   'sr_gfpgan_norm_style_f32')
+    launch('sr_gfpgan_norm_style_f32', x.device, x.data_ptr(), out.data_ptr(), x.size(0), x.size(1))
     return out
 
 
 def linear(x, w, b, act_slope=1.0, out=None):
     """y = lrelu(x w^T + b, act_slope) on contiguous fp32 rows — sr_linear_fwd_f32."""
-    lib = _lib.load()
     n, k = x.shape
     assert x.is_contiguous() and w.is_contiguous() and w.shape[1] == k
     y = torch.empty((n, w.shape[0]), dtype=torch.float32, device=x.device) if out is None else out
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sr_linear_fwd_f32(x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), n, k,
-                                         w.shape[0], float(act_slope), _stream(x.device)), 'sr_linear_fwd_f32')
+    launch('sr_linear_fwd_f32', x.device, x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), n, k,
+           w.shape[0], float(act_slope))
     return y

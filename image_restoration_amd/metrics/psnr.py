@@ -45,7 +45,7 @@ def psnr_device(sr, gt, crop_border=0):
     """PSNR per image of NCHW float tensors in [0, 1] on the HIP device, with tensor2img's quantisation."""
     import ctypes as C
     from .. import _lib
-    from ..hip_ops import scratch
+    from ..hip_ops import launch, scratch
     assert sr.shape == gt.shape and sr.dim() == 4 and sr.is_cuda
     lib = _lib.load()
     sr, gt = sr.contiguous().float(), gt.contiguous().float()
@@ -53,9 +53,7 @@ def psnr_device(sr, gt, crop_border=0):
     out = torch.empty(n, dtype=torch.float32, device=sr.device)
     wsb = lib.sr_reduce_workspace_bytes(8) * max(n, 1)
     ws = scratch(sr.device, wsb)
-    with torch.cuda.device(sr.device):
-        _lib.check(lib.sr_psnr_sse_f32(sr.data_ptr(), gt.data_ptr(), n, c, h, w, crop_border, out.data_ptr(), ws.data_ptr(), wsb,
-                                       torch.cuda.current_stream(sr.device).cuda_stream), 'sr_psnr_sse_f32')
+    launch('sr_psnr_sse_f32', sr.device, sr.data_ptr(), gt.data_ptr(), n, c, h, w, crop_border, out.data_ptr(), ws.data_ptr(), wsb)
     count = c * (h - 2 * crop_border) * (w - 2 * crop_border)
     mse = out.double().cpu().numpy() / count
     return [float('inf') if m == 0 else 20. * math.log10(255. / math.sqrt(m)) for m in mse]
@@ -106,7 +104,7 @@ def ssim_device(sr, gt, crop_border=0):
     does not matter: the channel mean is symmetric)."""
     import ctypes as C
     from .. import _lib
-    from ..hip_ops import scratch
+    from ..hip_ops import launch, scratch
     assert sr.shape == gt.shape and sr.dim() == 4 and sr.is_cuda
     lib = _lib.load()
     sr, gt = sr.contiguous().float(), gt.contiguous().float()
@@ -114,8 +112,6 @@ def ssim_device(sr, gt, crop_border=0):
     out = torch.empty(n, dtype=torch.float32, device=sr.device)
     wsb = lib.sr_reduce_workspace_bytes(8) * max(n, 1)
     ws = scratch(sr.device, wsb)
-    with torch.cuda.device(sr.device):
-        _lib.check(lib.sr_ssim_sum_f32(sr.data_ptr(), gt.data_ptr(), n, c, h, w, crop_border, out.data_ptr(), ws.data_ptr(), wsb,
-                                       torch.cuda.current_stream(sr.device).cuda_stream), 'sr_ssim_sum_f32')
+    launch('sr_ssim_sum_f32', sr.device, sr.data_ptr(), gt.data_ptr(), n, c, h, w, crop_border, out.data_ptr(), ws.data_ptr(), wsb)
     count = c * (h - 2 * crop_border - 10) * (w - 2 * crop_border - 10)
     return [float(v) / count for v in out.double().cpu().numpy()]
