@@ -19,6 +19,7 @@ from .. import _lib
 from .. import hip_autograd as A
 from ..utils.registry import ARCH_REGISTRY
 from .arch_util import Conv3x3Params
+from .hip_driver import HipDriverNet, grow_workspace, symbol
 
 
 class BatchNormParams(nn.Module):
@@ -67,7 +68,7 @@ class LinearParams(nn.Module):
 
 
 @ARCH_REGISTRY.register()
-class VGGStyleDiscriminator128(nn.Module):
+class VGGStyleDiscriminator128(HipDriverNet):
     """VGGStyleDiscriminator128(num_in_ch, num_feat): [N, num_in_ch, 128, 128] -> [N, 1] logits."""
 
     input_size = 128  # VGGStyleDiscriminator256 adds one 8nf -> 8nf stage (discriminator_arch.py:75-143)
@@ -94,85 +95,43 @@ class VGGStyleDiscriminator128(nn.Module):
             setattr(self, f'bn{i}_1', BatchNormParams(co))
         self.linear1 = LinearParams(nf * 8 * 4 * 4, 100)
         self.linear2 = LinearParams(100, 1)
-        self._packed = {}          # dtype -> (key, device blob of forward + data-gradient weight images)
-        self._grad_sink = None     # set by optim.FlatAdam: gradients accumulate straight into its arena
-        self._ws = None
-        self._pack_epoch = 0
+        self._bufptrs = None       # (buffer addresses, their C pointer array)
 
     # train-mode forwards are pure functions of (weights, input): models may run a repeated forward once (vgg_disc_autograd.py)
     repeatable_forward = True
 
-    # ------------------------------------------------------------------ HIP plumbing (mirrors RRDBNet's)
-    def invalidate_packed(self):
-        """Parameter memory was rewritten behind autograd's back (fused Adam writes the arena through raw pointers)."""
-        self._pack_epoch += 1
+    # ------------------------------------------------------------------ HIP plumbing (the caches: archs/hip_driver.py)
+    _num_params, _params_name = 'sr_vgg_num_params', 'discriminator'
 
     def _cfg(self):
         return _lib.VGGCfg(self.num_in_ch, self.num_feat, self.input_size)
 
-    def _param_list(self):
-        cached = self.__dict__.get('_plist')
-        if cached is not None and cached[0] is self.conv0_0.weight and cached[-1] is self.linear2.bias:
-            return cached
-        plist = [p for _, p in self.named_parameters()]
-        self.__dict__['_plist'] = plist
-        self.__dict__.pop('_bufptrs', None)
-        return plist
+    def _param_ends(self):
+        return self.conv0_0.weight, self.linear2.bias
 
-    def _apply(self, fn, *args, **kwargs):
-        self.__dict__.pop('_plist', None)
-        self.__dict__.pop('_bufptrs', None)
-        return super()._apply(fn, *args, **kwargs)
+    def _drop_device_caches(self):
+        self._bufptrs = None
 
     def _buffer_ptrs(self):
         """running_mean, running_var, num_batches_tracked of every BatchNorm in module order (sr_vgg_forward's host_buffers)."""
         bufs = [b for _, b in self.named_buffers()]
         key = tuple(b.data_ptr() for b in bufs)
-        cached = self.__dict__.get('_bufptrs')
+        cached = self._bufptrs
         if cached is None or cached[0] != key:
             lib = _lib.load()
             assert len(bufs) == 3 * lib.sr_vgg_num_batchnorm(C.byref(self._cfg())), len(bufs)
             for i, b in enumerate(bufs):
                 assert b.dtype == (torch.int64 if i % 3 == 2 else torch.float32) and b.is_contiguous()
-            cached = (key, (C.c_void_p * len(bufs))(*key))
-            self.__dict__['_bufptrs'] = cached
+            cached = self._bufptrs = (key, (C.c_void_p * len(bufs))(*key))
         return cached[1]
 
-    def _weights_key(self):
-        """Identity of the current weights: parameter storage + torch version counters + the epochs of writers torch cannot
-        see (FlatAdam's fused step, invalidate_packed, hip_ops.invalidate_packs)."""
-        from .. import hip_ops
-        params = self._param_list()
-        return (self._pack_epoch, hip_ops._pack_epoch[0], getattr(params[0], '_sr_epoch', (0,))[0],
-                tuple((p.data_ptr(), p._version) for p in params))
-
-    def _ensure_packed(self, lib, cfg, stream, bf16):
-        key = self._weights_key()
-        hit = self._packed.get(bf16)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        params = self._param_list()
-        n = lib.sr_vgg_num_params(C.byref(cfg))
-        if n != len(params):
-            raise _lib.SrHipError(f'parameter count {len(params)} != {n} expected by libsr_hip.so')
-        dev = params[0].device
-        for p in params:
-            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrHipError('discriminator parameters must be contiguous fp32 on one HIP device')
-        nbytes = (lib.sr_vgg_packed_bytes_bf16 if bf16 else lib.sr_vgg_packed_bytes)(C.byref(cfg))
-        blob = hit[1] if hit is not None and hit[1].numel() == nbytes and hit[1].device == dev else \
-            torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in params])
-        _lib.check((lib.sr_vgg_pack_bf16 if bf16 else lib.sr_vgg_pack_f32)(C.byref(cfg), ptrs, blob.data_ptr(), stream), 'sr_vgg_pack')
-        self._packed[bf16] = (key, blob)
-        return blob
+    def _packed(self, lib, cfg, stream, bf16):
+        """One blob of forward + data-gradient weight images per dtype."""
+        return self._blob(('fwd', bf16), lib, cfg, stream, 'sr_vgg_packed_bytes', 'sr_vgg_pack', short=True)
 
     def _workspace(self, lib, cfg, n, dev, bf16):
-        nbytes = (lib.sr_vgg_workspace_bytes_bf16 if bf16 else lib.sr_vgg_workspace_bytes)(C.byref(cfg), n)
-        ws = self._ws
-        if ws is None or ws.numel() < nbytes or ws.device != dev:
-            ws = self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return ws, nbytes
+        nbytes = symbol(lib, 'sr_vgg_workspace_bytes', bf16, query=True)[0](C.byref(cfg), n)
+        return grow_workspace(self, 'ws', nbytes, dev), nbytes
 
     def _check_input(self, x):
         sz = self.input_size

@@ -2,8 +2,9 @@
 (``HipGenerator``), the fp32 / bf16 ops table one layer list is written against (``F32``, ``BF16``) with the residual block and
 upsampling stage the networks have in common, and the autograd scaffold (``WholeNetFunction``, ``GradRouter``).
 
-A network built on this writes its parameters, ``run_forward(x, keep, ops)`` and the ``run_backward`` of its Function; RRDBNet,
-the discriminators and GFPGANv1OCR (whole-network C entry points, or one pack for the net) do not use it.
+A network built on this writes its parameters, ``run_forward(x, keep, ops)`` and the ``run_backward`` of its Function.  RRDBNet
+and the discriminators (whole-network C entry points) have their own base, hip_driver.py; GFPGANv1OCR (one Python-built pack for
+the net) uses neither.
 """
 from types import SimpleNamespace
 

@@ -15,6 +15,7 @@ import ctypes as C
 import torch
 
 from .. import _lib
+from .hip_driver import device_input, grad_targets, grow_workspace, symbol
 
 
 class _RRDBNetFunction(torch.autograd.Function):
@@ -22,17 +23,15 @@ class _RRDBNetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, x, *params):
         lib = _lib.load()
-        if not x.is_cuda:
-            raise _lib.SrHipError('RRDBNet runs only on a HIP device (no CPU fallback)')
-        x = x.contiguous().float()
+        x = device_input(x, 'RRDBNet')
         n, _, h, w = x.shape
         cfg = net._cfg()
         dev = x.device
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
             bf16 = net.compute_dtype == 'bf16'
-            packed = net._ensure_packed_bf16(lib, cfg, stream) if bf16 else net._ensure_packed(lib, cfg, stream)
-            nbytes = (lib.sr_rrdbnet_saved_bytes_bf16 if bf16 else lib.sr_rrdbnet_saved_bytes)(C.byref(cfg), n, h, w)
+            packed = net._packed(lib, cfg, stream, bf16)
+            nbytes = symbol(lib, 'sr_rrdbnet_saved_bytes', bf16, query=True)[0](C.byref(cfg), n, h, w)
             if nbytes == 0:
                 u = {4: 1, 2: 2, 1: 4}[cfg.scale]
                 assert h % u == 0 and w % u == 0, f'input {h}x{w} is not divisible by the pixel_unshuffle factor {u}'
@@ -40,12 +39,10 @@ class _RRDBNetFunction(torch.autograd.Function):
             saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             up = {4: 4, 2: 2, 1: 1}[cfg.scale]
             y = torch.empty((n, net.num_out_ch, h * up, w * up), dtype=torch.float32, device=dev)
-            fwd = lib.sr_rrdbnet_forward_train_bf16 if bf16 else lib.sr_rrdbnet_forward_train_f32
-            _lib.check(fwd(C.byref(cfg), packed.data_ptr(), x.data_ptr(), y.data_ptr(), n, h, w, saved.data_ptr(), nbytes,
-                           stream), 'sr_rrdbnet_forward_train_' + ('bf16' if bf16 else 'f32'))
+            fwd, name = symbol(lib, 'sr_rrdbnet_forward_train', bf16)
+            _lib.check(fwd(C.byref(cfg), packed.data_ptr(), x.data_ptr(), y.data_ptr(), n, h, w, saved.data_ptr(), nbytes, stream), name)
         ctx.net, ctx.cfg, ctx.saved, ctx.shape, ctx.bf16 = net, cfg, saved, (n, h, w), bf16
         ctx.x_shape = tuple(x.shape)
-        ctx.param_versions = tuple(p._version for p in params)
         ctx.params = params
         return y
 
@@ -53,46 +50,27 @@ class _RRDBNetFunction(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         net, cfg, (n, h, w), bf16 = ctx.net, ctx.cfg, ctx.shape, ctx.bf16
-        params = ctx.params
         dy = dy.contiguous().float()
         dev = dy.device
         need_x = ctx.needs_input_grad[1]
-        need_p = ctx.needs_input_grad[2:]
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
             # data-gradient weight images (transposed / flipped), cached per parameter version
-            packed_dg = net._ensure_packed_dgrad(lib, cfg, stream, bf16)
+            packed_dg = net._packed(lib, cfg, stream, bf16, dgrad=True)
             # deferred weight gradients (NetPack.defer_weight_gradients): the call returns with the lane still busy; whoever consumes
             # the gradient arena joins first (NetPack.update), and what the lane reads stays alive until then
-            defer = bool(bf16 and getattr(net, '_defer_wgrad', False) and getattr(net, '_grad_sink', None) is not None)
+            defer = bool(bf16 and getattr(net, '_defer_wgrad', False) and net._grad_sink is not None)
             if bf16:
                 lib.sr_set_backward_wgrad_deferred(int(getattr(net, '_defer_mode', 1)) if defer else 0)
-            wbytes = (lib.sr_rrdbnet_backward_workspace_bytes_bf16 if bf16 else
-                      lib.sr_rrdbnet_backward_workspace_bytes)(C.byref(cfg), n, h, w)
-            ws = net._bwd_workspace(wbytes, dev)
-            sink = getattr(net, '_grad_sink', None)
-            if sink is not None and any(need_p):
-                # Flat-arena mode (image_restoration_amd.optim.FlatAdam): gradients are ACCUMULATED straight into
-                # the arena that is all-reduced and consumed by the fused Adam kernel; autograd sees no grads.
-                if not all(need_p):
-                    raise _lib.SrHipError('flat-arena mode needs every generator parameter to require grad')
-                grads = [None] * len(params)
-                ptrs = (C.c_void_p * len(params))(*sink.grad_ptrs)
-                accumulate = 1
-            else:
-                grads = [torch.empty_like(p) if need else None for p, need in zip(params, need_p)]
-                # weight and bias of one conv travel together: a conv is skipped only when its weight needs no grad
-                ptrs = (C.c_void_p * len(params))(*[g.data_ptr() if g is not None else None for g in grads])
-                for i in range(0, len(params), 2):
-                    if grads[i] is None and grads[i + 1] is not None:
-                        raise _lib.SrHipError('bias.requires_grad without weight.requires_grad is not supported')
-                accumulate = 0
+            wbytes = symbol(lib, 'sr_rrdbnet_backward_workspace_bytes', bf16, query=True)[0](C.byref(cfg), n, h, w)
+            ws = grow_workspace(net, 'bwd', wbytes, dev)
+            grads, ptrs, accumulate = grad_targets(ctx.params, ctx.needs_input_grad[2:], net._grad_sink,
+                                                   'flat-arena mode needs every generator parameter to require grad', pairs=True)
             dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dev) if need_x else None
-            bwd = lib.sr_rrdbnet_backward_bf16 if bf16 else lib.sr_rrdbnet_backward_f32
+            bwd, name = symbol(lib, 'sr_rrdbnet_backward', bf16)
             try:
                 _lib.check(bwd(C.byref(cfg), packed_dg.data_ptr(), ctx.saved.data_ptr(), ctx.saved.numel(), dy.data_ptr(), n, h, w,
-                               ptrs, dx.data_ptr() if dx is not None else None, ws.data_ptr(), wbytes, accumulate, stream),
-                           'sr_rrdbnet_backward_' + ('bf16' if bf16 else 'f32'))
+                               ptrs, dx.data_ptr() if dx is not None else None, ws.data_ptr(), wbytes, accumulate, stream), name)
             finally:
                 if defer:
                     lib.sr_set_backward_wgrad_deferred(0)

@@ -12,6 +12,7 @@ import ctypes as C
 import torch
 
 from .. import _lib
+from .hip_driver import device_input, grad_targets, grow_workspace
 
 
 class _UNetFunction(torch.autograd.Function):
@@ -19,9 +20,7 @@ class _UNetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, x, *weights):
         lib = _lib.load()
-        if not x.is_cuda:
-            raise _lib.SrHipError('UNetDiscriminatorSN runs only on a HIP device (no CPU fallback)')
-        x = x.contiguous().float()
+        x = device_input(x, 'UNetDiscriminatorSN')
         n, _, h, w = x.shape
         cfg = net._cfg()
         dev = x.device
@@ -50,18 +49,12 @@ class _UNetFunction(torch.autograd.Function):
         dlogits = dlogits.contiguous().float()
         dev = dlogits.device
         need_x = ctx.needs_input_grad[1]
-        need_w = ctx.needs_input_grad[2:]
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
             wbytes = lib.sr_unet_workspace_bytes_bf16(C.byref(cfg), n, h, w)
-            ws = net._workspace(wbytes, dev)
-            grads = [None] * len(ctx.w_shapes)
-            dptrs = None
-            if any(need_w):
-                if not all(need_w):
-                    raise _lib.SrHipError('the whole-network U-Net backward needs all weights to require grad or none')
-                grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.w_shapes]
-                dptrs = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+            ws = grow_workspace(net, 'bwd', wbytes, dev)
+            grads, dptrs, _ = grad_targets(ctx.w_shapes, ctx.needs_input_grad[2:], None,
+                                           'the whole-network U-Net backward needs all weights to require grad or none', dev=dev)
             dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dev) if need_x else None
             _lib.check(lib.sr_unet_backward_bf16(C.byref(cfg), ctx.packed.data_ptr(), ctx.saved.data_ptr(), ctx.saved.numel(),
                                                  dlogits.data_ptr(), n, h, w, dptrs, dx.data_ptr() if dx is not None else None, ws.data_ptr(),

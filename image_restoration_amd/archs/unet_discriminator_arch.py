@@ -68,6 +68,7 @@ class UNetDiscriminatorSN(nn.Module):
         self.conv7 = SNConvParams(nf, nf, 3)
         self.conv8 = SNConvParams(nf, nf, 3)
         self.conv9 = Conv3x3Params(nf, 1, bias=True)
+        self._grown = {}    # hip_driver.grow_workspace: the driver backward's scratch
 
     def _sn_weights(self):
         """The normalised weights of conv1..conv8 for this forward: one power iteration each in train mode, all eight layers in one
@@ -114,12 +115,6 @@ class UNetDiscriminatorSN(nn.Module):
 
     def _cfg(self):
         return _lib.UNetCfg(self.num_in_ch, self.num_feat, int(bool(self.skip_connection)))
-
-    def _workspace(self, nbytes, dev):
-        ws = getattr(self, '_ws', None)
-        if ws is None or ws.numel() < nbytes or ws.device != dev:
-            ws = self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return ws
 
     def _forward_driver_bf16(self, x):
         """archs/unet_disc_autograd.py: sr_unet_forward_bf16 / sr_unet_backward_bf16 behind ONE autograd function; the spectral

@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from .. import _lib
+from .hip_driver import device_input, grad_targets, symbol
 
 
 class KeptForward:
@@ -32,18 +33,12 @@ def _x_key(x):
     return (x.data_ptr(), x._version, tuple(x.shape), str(x.device))
 
 
-def _fn(lib, name, bf16):
-    return getattr(lib, name + ('_bf16' if bf16 else '_f32'))
-
-
 class _VGGFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, x, kept, slot, *params):
         lib = _lib.load()
-        if not x.is_cuda:
-            raise _lib.SrHipError(f'{type(net).__name__} runs only on a HIP device (no CPU fallback)')
-        x = x.contiguous().float()
+        x = device_input(x, type(net).__name__)
         n = x.size(0)
         cfg = net._cfg()
         bf16 = net.compute_dtype == 'bf16'
@@ -55,11 +50,11 @@ class _VGGFunction(torch.autograd.Function):
             if kept is not None:
                 # a repeat of a forward that already ran on this input with these weights: only the statistics move
                 if train:
-                    _lib.check(_fn(lib, 'sr_vgg_apply_stats', bf16)(C.byref(cfg), kept.saved.data_ptr(), kept.saved.numel(), n, bufs, 1,
-                                                                    stream), 'sr_vgg_apply_stats')
+                    stats, name = symbol(lib, 'sr_vgg_apply_stats', bf16, short=True)
+                    _lib.check(stats(C.byref(cfg), kept.saved.data_ptr(), kept.saved.numel(), n, bufs, 1, stream), name)
             else:
-                packed = net._ensure_packed(lib, cfg, stream, bf16)
-                nbytes = (lib.sr_vgg_saved_bytes_bf16 if bf16 else lib.sr_vgg_saved_bytes)(C.byref(cfg), n)
+                packed = net._packed(lib, cfg, stream, bf16)
+                nbytes = symbol(lib, 'sr_vgg_saved_bytes', bf16, query=True)[0](C.byref(cfg), n)
                 if nbytes == 0:
                     raise _lib.SrHipError('sr_vgg_saved_bytes returned 0')
                 kept = KeptForward()
@@ -69,9 +64,9 @@ class _VGGFunction(torch.autograd.Function):
                 kept.x_key, kept.w_key = _x_key(x), net._weights_key()
                 ws, wbytes = net._workspace(lib, cfg, n, dev, bf16)
                 pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-                _lib.check(_fn(lib, 'sr_vgg_forward', bf16)(C.byref(cfg), packed.data_ptr(), pp, bufs, x.data_ptr(), kept.logits.data_ptr(),
-                                                            n, int(train), kept.saved.data_ptr(), nbytes, ws.data_ptr(), wbytes, stream),
-                           'sr_vgg_forward')
+                fwd, name = symbol(lib, 'sr_vgg_forward', bf16, short=True)
+                _lib.check(fwd(C.byref(cfg), packed.data_ptr(), pp, bufs, x.data_ptr(), kept.logits.data_ptr(), n, int(train),
+                               kept.saved.data_ptr(), nbytes, ws.data_ptr(), wbytes, stream), name)
             if slot is not None:
                 slot.append(kept)
         ctx.net, ctx.cfg, ctx.kept, ctx.params, ctx.x_shape = net, cfg, kept, params, tuple(x.shape)
@@ -85,32 +80,20 @@ class _VGGFunction(torch.autograd.Function):
         dlogits = dlogits.contiguous().float()
         dev = dlogits.device
         need_x = ctx.needs_input_grad[1]
-        need_p = ctx.needs_input_grad[4:]
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
             if kept.w_key != net._weights_key():
                 raise _lib.SrHipError('the discriminator weights changed between a forward and its backward')
-            packed = net._ensure_packed(lib, cfg, stream, bf16)
+            packed = net._packed(lib, cfg, stream, bf16)
             ws, wbytes = net._workspace(lib, cfg, n, dev, bf16)
-            sink = getattr(net, '_grad_sink', None)
-            grads = [None] * len(params)
-            dptrs = None
-            accumulate = 0
-            if any(need_p):
-                if not all(need_p):
-                    raise _lib.SrHipError('the whole-network discriminator backward needs all parameters to require grad or none')
-                if sink is not None:   # flat-arena mode: accumulate into the arena FlatAdam all-reduces and consumes
-                    dptrs = (C.c_void_p * len(params))(*sink.grad_ptrs)
-                    accumulate = 1
-                else:
-                    grads = [torch.empty_like(p) for p in params]
-                    dptrs = (C.c_void_p * len(params))(*[g.data_ptr() for g in grads])
+            grads, dptrs, accumulate = grad_targets(params, ctx.needs_input_grad[4:], net._grad_sink,
+                                                    'the whole-network discriminator backward needs all parameters to require grad or none')
             dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dev) if need_x else None
             pp = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-            _lib.check(_fn(lib, 'sr_vgg_backward', bf16)(C.byref(cfg), packed.data_ptr(), pp, kept.saved.data_ptr(), kept.saved.numel(),
-                                                         dlogits.data_ptr(), n, int(kept.train), dptrs, accumulate,
-                                                         dx.data_ptr() if dx is not None else None, ws.data_ptr(), wbytes, stream),
-                       'sr_vgg_backward')
+            bwd, name = symbol(lib, 'sr_vgg_backward', bf16, short=True)
+            _lib.check(bwd(C.byref(cfg), packed.data_ptr(), pp, kept.saved.data_ptr(), kept.saved.numel(), dlogits.data_ptr(), n,
+                           int(kept.train), dptrs, accumulate, dx.data_ptr() if dx is not None else None, ws.data_ptr(), wbytes,
+                           stream), name)
         return (None, dx, None, None) + tuple(grads)
 
 

@@ -158,3 +158,25 @@ def test_forward_is_graph_capturable(cuda, dtype):
         torch.cuda.synchronize()
         got = y.clone()
         assert torch.equal(got, net(x))
+
+
+@pytest.mark.parametrize('dtype', ['fp32', 'bf16'])
+def test_invalidate_packs_reaches_the_generators_weight_images(cuda, dtype):
+    """hip_ops.py promises that after a write through ``param.data``, which moves no version counter, a call of
+    invalidate_packs() is enough: the next forward runs on the new weights (the bits of a fresh network loaded with them)."""
+    cfg = dict(num_in_ch=3, num_out_ch=3, scale=4, num_feat=16, num_block=1, num_grow_ch=8, compute_dtype=dtype)
+    net = ira.build_network(dict(type='RRDBNet', **cfg)).to(cuda).eval()
+    x = torch.from_numpy(synth.uniform_input(7, (1, 3, 16, 16))).to(cuda)
+    bias = net.conv_last.bias
+    with torch.no_grad():
+        y0 = net(x)
+        version, ptr = bias._version, bias.data_ptr()
+        bias.data.view(-1).copy_(torch.tensor([0.5, -0.25, 0.125], device=cuda))
+        assert (bias._version, bias.data_ptr()) == (version, ptr)      # nothing torch keeps count of has moved
+        H.invalidate_packs()
+        y1 = net(x)
+        fresh = ira.build_network(dict(type='RRDBNet', **cfg)).to(cuda).eval()
+        fresh.load_state_dict(net.state_dict(), strict=True)
+        want = fresh(x)
+    assert torch.equal(y1, want)
+    assert not torch.equal(y1, y0)

@@ -11,8 +11,8 @@ for dt in ('fp32', 'bf16'):
     net.set_compute_dtype(dt)
     c = net._cfg()
     st = torch.cuda.current_stream().cuda_stream
-    for name, fn in (('fwd pack', lambda: (net._ensure_packed_bf16 if dt == 'bf16' else net._ensure_packed)(lib, c, st)),
-                     ('dgrad pack', lambda: net._ensure_packed_dgrad(lib, c, st, dt == 'bf16'))):
+    for name, fn in (('fwd pack', lambda: net._packed(lib, c, st, dt == 'bf16')),
+                     ('dgrad pack', lambda: net._packed(lib, c, st, dt == 'bf16', dgrad=True))):
         for _ in range(2):
             net.invalidate_packed(); fn()
         torch.cuda.synchronize(); t0 = time.perf_counter()
