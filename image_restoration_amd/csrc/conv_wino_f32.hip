@@ -10,19 +10,25 @@
 // in 4 consecutive registers, so all 16 points of one (cout, patch) sit in ONE lane, in 16 different accumulators — the output
 // transform is 24 per-lane adds and the epilogue's 16-byte CB8 stores are those of the direct kernel.
 //
-// One wave = 32 patches (one patch row, 64 pixel columns) x 32 couts x 16 points = 256 accumulator registers: one wave per SIMD.
-// Workgroup = NW waves = NW patch rows: output tile (2 NW rows) x 64 columns x 32 couts; blockIdx.y = 32-cout group.
+// One wave = 32 patches (one patch row, 64 pixel columns) x 32 couts x 8 points = 128 accumulator registers: the 16 points are split
+// by transform row over TWO waves, "low" (rows r = 0, 1 of V = B^T d B: points 0-7) and "high" (r = 2, 3: points 8-15), so a wave
+// fits in 256 registers and two waves share a SIMD: each covers the other's LDS reads, transform adds, barrier waits and epilogue.
+// Workgroup = 2 NW waves = NW patch rows x 2 halves (waves 0..NW-1 low, NW..2NW-1 high: at NW = 4 the two halves of a patch row are
+// the two waves of one SIMD): output tile (2 NW rows) x 64 columns x 32 couts; blockIdx.y = 32-cout group.
 // K is walked in chunks of one 8-channel CB8 block, one barrier per chunk; U is double buffered, X triple buffered (the operand
 // of chunk c + 1 is formed under the MFMAs of chunk c):
 //   LDS X image  [2 NW + 2][66][8] floats   raw halo'd tile, staged like conv_tile_f32 (buffer-descriptor LDS-DMA through the
 //                                           source map: zero padding = out-of-range offsets, nearest x2 upsample = src >> 1)
 //   LDS U image  [16 points][32 couts][8]   contiguous in HBM
-// Per chunk a lane (patch j, half h) reads the 4x4 raw patch of channels 4h..4h+3 (16 ds_read_b128), forms V = B^T d B in
-// registers (32 adds per channel) and issues 16 points x 4 K=2 steps = 64 MFMAs.
+// Per chunk a lane (patch j, half h) reads the three raw rows its two transform rows need (d0 d1 d2 low, d1 d2 d3 high), four
+// columns of channels 4h..4h+3 (12 ds_read_b128), forms its 8 values of V = B^T d B in registers and issues 8 points x 4 K=2
+// steps = 32 MFMAs on its 8 U planes.  Behind the last chunk the column step of the output transform is per wave; the row step
+// needs one transform row of the other half, exchanged once per tile through the then-dead X buffers.  Low stores output row
+// dy = 0 of its patch row, high dy = 1.
 //
-// Patches are anchored at EVEN image coordinates, chunks ascend, the order inside a chunk is fixed and every variant (NW = 4, 2, 1)
-// runs the same wave code: an output value depends on its image and its position only — not on tile shape, launch size or batch.
-// No inter-workgroup communication of any kind.
+// Patches are anchored at EVEN image coordinates, chunks ascend, the order inside a chunk and every expression tree are fixed and
+// every variant (NW = 4, 2, 1) runs the same wave code: an output value depends on its image and its position only — not on tile
+// shape, launch size or batch.  No inter-workgroup communication of any kind.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -55,20 +61,23 @@ constexpr int XROW = 66;  // 64 tile columns + halo
 
 template <int NW>
 constexpr int wino_x_bytes() {
-  return (((2 * NW + 2) * XROW * 32 + NW * 1024 - 1) / (NW * 1024)) * (NW * 1024);  // whole 1 KiB pieces for every wave
+  return (((2 * NW + 2) * XROW * 32 + NW * 1024 - 1) / (NW * 1024)) * (NW * 1024);  // whole 1 KiB pieces, a multiple of NW of them
 }
 template <int NW>
 constexpr int wino_lds_bytes() {
   return 3 * wino_x_bytes<NW>() + 2 * 16 * 1024;
 }
 
-// One output tile; the body of conv_wino_f32_kernel (a __device__ function: the host pass does not see the target builtins).
-template <int NW>
-__device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* smem) {
+// One output tile as seen by one wave of half HF (0 = low: transform rows 0, 1; 1 = high: rows 2, 3); the body of
+// conv_wino_f32_kernel (a __device__ function: the host pass does not see the target builtins).  Both halves pass the same barriers.
+template <int NW, int HF>
+__device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* smem, const int wave) {
+  constexpr int NV = 2 * NW;  // waves of the workgroup
   constexpr int XPIX = (2 * NW + 2) * XROW;
   constexpr int XBYTES = wino_x_bytes<NW>();
-  constexpr int NXU = XBYTES / 1024, NWU = 16;
-  constexpr int NXR = NXU / NW, NWR = NWU / NW;
+  constexpr int NXU = (XPIX * 32 + 1023) / 1024, NWU = 16;  // 1 KiB pieces of one X chunk / one U chunk
+  constexpr int NXR = (NXU + NV - 1) / NV, NWR = NWU / NV;  // per wave; the last X round is guarded (piece < NXU)
+  static_assert(NV * 8192 <= 3 * XBYTES, "the exchange of the output transform lives in the X buffers");
 
   // XCD-aware tile order (as conv_f32_kernel): each XCD gets a contiguous run of tiles
   int t;
@@ -83,8 +92,8 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   const int n = t / p.tiles_y;
   const int cog = blockIdx.y;
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = threadIdx.x & 63;
+  const int prow = wave - HF * NW;  // patch row of the tile
   const int j = lane & 31, h = lane >> 5;
   const int x0 = tx * 64, y0 = ty * (2 * NW);
   const int HWin = p.in_h * p.in_w;
@@ -96,7 +105,7 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   unsigned xvo[NXR];
 #pragma unroll
   for (int r = 0; r < NXR; ++r) {
-    const int u = r * NW + wave;
+    const int u = r * NV + wave;
     const int q = u * 64 + lane;
     const int pix = q >> 1, half = q & 1;
     const int row = pix / XROW, col = pix - row * XROW;
@@ -114,55 +123,58 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
       __builtin_amdgcn_make_buffer_rsrc((void*)ug, 0, (unsigned)((long long)p.cin_blocks * NWU * 1024), 0x00020000);
   const unsigned uvo = (lane ^ ((lane >> 4) & 1)) * 16;  // unit (cout i, half) <- half ^ bit3(i)
   // LDS: three X buffers (the raw tile of chunk c + 1 is transformed under the MFMAs of chunk c, so chunk c + 2 is in flight then) and
-  // two U buffers.  The pieces of a chunk are issued in four parts, one per group of MFMAs: a wave alone on its SIMD has nobody to
-  // cover the issue cost of an LDS-DMA piece, so the pieces go between MFMAs, not in front of them.
-  auto stage_x = [&](int buf, int cb, int part) {
+  // two U buffers.  A wave issues all its pieces of a chunk at the head of the chunk: the partner wave on the SIMD covers the issue
+  // cost, and the pieces get the whole chunk to land before the barrier that drains them.
+  auto stage_x = [&](int buf, int cb) {
     char* xs = smem + buf * XBYTES;
     const unsigned xso = (unsigned)cb * (unsigned)HWin * 32u;
 #pragma unroll
     for (int r = 0; r < NXR; ++r) {
-      const int u = r * NW + wave;
-      if ((r & 3) == part)
+      const int u = r * NV + wave;
+      if ((r + 1) * NV <= NXU || u < NXU)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rs, (__attribute__((address_space(3))) void*)(xs + u * 1024), 16, xvo[r], xso, 0, 0);
     }
   };
-  auto stage_u = [&](int buf, int cb, int part) {
+  auto stage_u = [&](int buf, int cb) {
     char* us = smem + 3 * XBYTES + buf * (NWU * 1024);
     const unsigned uso = (unsigned)cb * (NWU * 1024u);
 #pragma unroll
     for (int r = 0; r < NWR; ++r) {
-      const int u = r * NW + wave;  // unit = transform point
-      if ((r & 3) == part)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(u_rs, (__attribute__((address_space(3))) void*)(us + u * 1024), 16, uvo, uso + u * 1024u, 0, 0);
+      const int u = r * NV + wave;  // unit = transform point
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(u_rs, (__attribute__((address_space(3))) void*)(us + u * 1024), 16, uvo, uso + u * 1024u, 0, 0);
     }
   };
 
-  f32x16 acc[16];
+  f32x16 acc[8];  // points 8 HF .. 8 HF + 7
 #pragma unroll
-  for (int a = 0; a < 16; ++a)
+  for (int a = 0; a < 8; ++a)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
 
-  // byte offset of raw pixel (row 0, column c) of this lane's patch: tile row 2 wave, tile column 2 j + c, swizzled half
+  // byte offset of the first raw pixel this half reads (raw row HF of the patch, column c): tile row 2 prow + HF, tile column
+  // 2 j + c, swizzled half
   int xlane[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) xlane[c] = ((2 * wave) * XROW + 2 * j + c) * 32 + ((h ^ (((2 * j + c) >> 3) & 1)) * 16);
-  const int ulane = j * 32 + ((h ^ ((j >> 3) & 1)) * 16);
+  for (int c = 0; c < 4; ++c) xlane[c] = ((2 * prow + HF) * XROW + 2 * j + c) * 32 + ((h ^ (((2 * j + c) >> 3) & 1)) * 16);
+  const int ulane = HF * 8 * 1024 + j * 32 + ((h ^ ((j >> 3) & 1)) * 16);
 
-  // V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1], as one fixed tree: rows first (tr = B^T d), then columns
-  f32x4 tr[4][4], v[16];
+  // V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1], as one fixed tree: rows first (tr = B^T d), then columns.
+  // This half's two rows of tr: low d0 - d2, d1 + d2; high d2 - d1, d1 - d3
+  f32x4 tr[2][4], v[8];
   auto rows = [&](int buf) {
     const char* xb = smem + buf * XBYTES;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const f32x4 d0 = *(const f32x4*)(xb + xlane[c]);
-      const f32x4 d1 = *(const f32x4*)(xb + xlane[c] + XROW * 32);
-      const f32x4 d2 = *(const f32x4*)(xb + xlane[c] + 2 * XROW * 32);
-      const f32x4 d3 = *(const f32x4*)(xb + xlane[c] + 3 * XROW * 32);
-      tr[0][c] = d0 - d2;
-      tr[1][c] = d1 + d2;
-      tr[2][c] = d2 - d1;
-      tr[3][c] = d1 - d3;
+      const f32x4 e0 = *(const f32x4*)(xb + xlane[c]);
+      const f32x4 e1 = *(const f32x4*)(xb + xlane[c] + XROW * 32);
+      const f32x4 e2 = *(const f32x4*)(xb + xlane[c] + 2 * XROW * 32);
+      if constexpr (HF == 0) {  // e = d0, d1, d2
+        tr[0][c] = e0 - e2;
+        tr[1][c] = e1 + e2;
+      } else {  // e = d1, d2, d3
+        tr[0][c] = e1 - e0;
+        tr[1][c] = e0 - e2;
+      }
     }
   };
   auto cols = [&](int r) {
@@ -173,16 +185,13 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   };
 
   const int nchunk = p.cin_blocks;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    stage_x(0, 0, g);
-    stage_u(0, 0, g);
-    if (nchunk > 1) stage_x(1, 1, g);
-  }
+  stage_x(0, 0);
+  stage_u(0, 0);
+  if (nchunk > 1) stage_x(1, 1);
   __syncthreads();
   rows(0);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) cols(r);
+  for (int r = 0; r < 2; ++r) cols(r);
   int xb2 = 2 % 3, xb1 = 1;  // X buffers of chunks c + 2 and c + 1
   // one chunk; MORE / MORE2: chunks c + 1 / c + 2 exist (compile-time, so that the body is one straight line the scheduler can
   // interleave: the last two chunks are peeled)
@@ -193,27 +202,27 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
 #pragma unroll
     for (int q = 0; q < 4; ++q) a[0][q] = *(const f32x4*)(us + q * 1024);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {  // four points at a time: dependent MFMAs of one accumulator are four instructions apart
-      if (g < 3) {
+    for (int g = 0; g < 2; ++g) {  // four points at a time: dependent MFMAs of one accumulator are four instructions apart
+      if (g == 0) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) a[(g + 1) & 1][q] = *(const f32x4*)(us + ((g + 1) * 4 + q) * 1024);
+        for (int q = 0; q < 4; ++q) a[1][q] = *(const f32x4*)(us + (4 + q) * 1024);
+        if constexpr (more2) stage_x(xb2, c + 2);
+        if constexpr (more) stage_u((c + 1) & 1, c + 1);
       }
-      if constexpr (more2) stage_x(xb2, c + 2, g);
-      if constexpr (more) stage_u((c + 1) & 1, c + 1, g);
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          acc[g * 4 + q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g & 1][q][s], v[g * 4 + q][s], acc[g * 4 + q], 0, 0, 0);
-      // the next chunk's operand, behind the MFMAs that read the current one: the raw patch and its row transform under group 0,
-      // then V's row g - 1 once group g - 1 has been issued
+          acc[g * 4 + q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][q][s], v[g * 4 + q][s], acc[g * 4 + q], 0, 0, 0);
+      // the next chunk's operand, behind the MFMAs that read the current one: the raw rows and their row transform under group 0,
+      // then V's row 0 once group 0 has been issued
       if constexpr (more) {
         if (g == 0) rows(xb1);
-        else cols(g - 1);
+        else cols(0);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (more) cols(3);
+    if constexpr (more) cols(1);
     __syncthreads();  // drains the LDS-DMA issued in this chunk; frees U buffer c & 1 and the X buffer of chunk c + 1
     xb1 = xb2;
     xb2 = xb2 == 2 ? 0 : xb2 + 1;
@@ -224,55 +233,79 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   if (nchunk > 1) chunk(nchunk - 2, yes{}, no{});
   chunk(nchunk - 1, no{}, no{});
 
-  // ---- output transform Y = A^T (M A), A^T = [1 1 1 0; 0 1 -1 -1]: columns first, then rows, one fixed tree
-  f32x16 yv[2][2];
-  {
-    f32x16 ra[4][2];
+  // ---- output transform Y = A^T (M A), A^T = [1 1 1 0; 0 1 -1 -1]: columns first (per transform row: inside the wave), then rows,
+  // one fixed tree.  ra[0], ra[1] are transform rows 2 HF, 2 HF + 1
+  f32x16 ra[2][2];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      ra[r][0] = (acc[r * 4 + 0] + acc[r * 4 + 1]) + acc[r * 4 + 2];
-      ra[r][1] = (acc[r * 4 + 1] - acc[r * 4 + 2]) - acc[r * 4 + 3];
-    }
+  for (int r = 0; r < 2; ++r) {
+    ra[r][0] = (acc[r * 4 + 0] + acc[r * 4 + 1]) + acc[r * 4 + 2];
+    ra[r][1] = (acc[r * 4 + 1] - acc[r * 4 + 2]) - acc[r * 4 + 3];
+  }
+
+  // the row step needs one transform row of the other half: high sends row 2 to low, low sends row 1 to high, through the X buffers
+  // (dead behind the last chunk's barrier), 8 KiB per wave, each 16-byte store and load contiguous over the lanes
+  f32x16 yv[2];  // [dx]
+  {
+    char* mine = smem + wave * 8192 + lane * 16;
+    const char* theirs = smem + (HF ? wave - NW : wave + NW) * 8192 + lane * 16;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = ra[1 - HF][c][k * 4 + e];
+        *(f32x4*)(mine + (c * 4 + k) * 1024) = o;
+      }
+    __syncthreads();
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      yv[0][c] = (ra[0][c] + ra[1][c]) + ra[2][c];
-      yv[1][c] = (ra[1][c] - ra[2][c]) - ra[3][c];
+      f32x16 rb;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const f32x4 o = *(const f32x4*)(theirs + (c * 4 + k) * 1024);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rb[k * 4 + e] = o[e];
+      }
+      if constexpr (HF == 0) yv[c] = (ra[0][c] + ra[1][c]) + rb;  // (ra0 + ra1) + ra2
+      else yv[c] = (rb - ra[0][c]) - ra[1][c];                    // (ra1 - ra2) - ra3
     }
   }
 
-  // ---- epilogue (that of conv_tile_f32): bias, LeakyReLU, alpha, residual scale-adds, 16-byte CB8 stores
+  // ---- epilogue (that of conv_tile_f32): bias, LeakyReLU, alpha, residual scale-adds, 16-byte CB8 stores.  This half's output row
+  // is dy = HF
   const long long HW = (long long)p.H * p.W;
+  const int y = y0 + 2 * prow + HF;
 #pragma unroll
-  for (int dy = 0; dy < 2; ++dy) {
+  for (int dx = 0; dx < 2; ++dx) {
+    const int x = x0 + 2 * j + dx;
+    if (y >= p.H || x >= p.W) continue;
+    const long long pixoff = (long long)y * p.W + x;
 #pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {
-      const int y = y0 + 2 * wave + dy, x = x0 + 2 * j + dx;
-      if (y >= p.H || x >= p.W) continue;
-      const long long pixoff = (long long)y * p.W + x;
+    for (int g = 0; g < 4; ++g) {
+      const int cb = cog * 4 + g;
+      if (cb >= p.cout_blocks) continue;
+      f32x4 o;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int cb = cog * 4 + g;
-        if (cb >= p.cout_blocks) continue;
-        f32x4 o;
+      for (int e = 0; e < 4; ++e) o[e] = yv[dx][g * 4 + e];
+      const long long off = (cb * HW + pixoff) * 8 + h * 4;
+      if (p.bias) o += *(const f32x4*)(p.bias + cb * 8 + h * 4);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = yv[dy][dx][g * 4 + e];
-        const long long off = (cb * HW + pixoff) * 8 + h * 4;
-        if (p.bias) o += *(const f32x4*)(p.bias + cb * 8 + h * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = o[e] > 0.f ? o[e] : o[e] * p.slope;
-        o *= p.alpha;
-        if (p.res1 && cb < p.res_cb1) o += p.beta1 * *(const f32x4*)(p.res1 + (long long)n * p.res1_ns + off);
-        if (p.res2 && cb < p.res_cb1) o += p.beta2 * *(const f32x4*)(p.res2 + (long long)n * p.res2_ns + off);
-        *(f32x4*)(p.out + (long long)n * p.out_ns + off) = o;
-      }
+      for (int e = 0; e < 4; ++e) o[e] = o[e] > 0.f ? o[e] : o[e] * p.slope;
+      o *= p.alpha;
+      if (p.res1 && cb < p.res_cb1) o += p.beta1 * *(const f32x4*)(p.res1 + (long long)n * p.res1_ns + off);
+      if (p.res2 && cb < p.res_cb1) o += p.beta2 * *(const f32x4*)(p.res2 + (long long)n * p.res2_ns + off);
+      *(f32x4*)(p.out + (long long)n * p.out_ns + off) = o;
     }
   }
 }
 
 template <int NW>
-__global__ __launch_bounds__(NW * 64, 1) void conv_wino_f32_kernel(const WinoParams p) {
+__global__ __launch_bounds__(NW * 128, 2) void conv_wino_f32_kernel(const WinoParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  conv_wino_tile_f32<NW>(p, smem);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wave < NW) conv_wino_tile_f32<NW, 0>(p, smem, wave);
+  else conv_wino_tile_f32<NW, 1>(p, smem, wave);
 }
 
 template <int NW>
@@ -302,7 +335,7 @@ int launch_wino(const WinoParams& p0, const sr_conv3x3_desc* d, hipStream_t stre
     r.bytes = 4.0 * fl;
     sr::prof_begin(stream, r);
   }
-  hipLaunchKernelGGL(kern, dim3(p.tiles_x * p.tiles_y * d->n, groups), dim3(NW * 64), lds, stream, p);
+  hipLaunchKernelGGL(kern, dim3(p.tiles_x * p.tiles_y * d->n, groups), dim3(NW * 128), lds, stream, p);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("conv_wino_f32 launch");
   return SR_OK;
@@ -373,12 +406,14 @@ int conv3x3_wino_f32(const sr_conv3x3_desc* d, const float* image, hipStream_t s
   // kernels, which split a 32-cout tile over four waves, are faster there.  By H x W alone: never by n, so that a batched call and
   // a single-image call take the same arithmetic.
   if (!any_size && mode < 2 && (long long)p.H * p.W < 128 * 128) return SR_WINO_NOT_ELIGIBLE;
-  const long long rows4 = cdiv(p.H, 8), rows2 = cdiv(p.H, 4), rows1 = cdiv(p.H, 2);
+  const long long rows2 = cdiv(p.H, 4), rows1 = cdiv(p.H, 2);
   const long long per_row = (long long)cdiv(p.W, 64) * d->n * (d->cout / 32) * launch_concurrency();
   if (per_row * rows1 >= (1ll << 31)) return SR_WINO_NOT_ELIGIBLE;
-  // every variant gives the same bits: the tallest tile that still fills the chip (one workgroup of four waves per CU and round)
-  int nw = rows4 * per_row >= 256 ? 4 : rows2 * per_row >= 256 ? 2 : 1;
-  if (mode >= 2) nw = mode == 2 ? 4 : mode == 3 ? 2 : 1;
+  // every variant gives the same bits.  A launch that fills the chip takes NW = 2: two independent four-wave workgroups per CU (two
+  // waves per SIMD, as one eight-wave NW = 4 workgroup gives) whose barriers and tile boundaries drift apart measured 3.3 % faster
+  // than NW = 4 at the benchmark's size, so NW = 4 runs only when forced.  Below that, the tallest tile that still gives every CU a
+  // workgroup
+  const int nw = mode >= 2 ? (mode == 2 ? 4 : mode == 3 ? 2 : 1) : rows2 * per_row >= 256 ? 2 : 1;
   return nw == 4 ? launch_wino<4>(p, d, stream) : nw == 2 ? launch_wino<2>(p, d, stream) : launch_wino<1>(p, d, stream);
 }
 
