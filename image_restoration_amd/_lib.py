@@ -1,5 +1,5 @@
 """ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h,
-include/sr_hip_edsr.h and include/sr_hip_ca_bf16.h).
+include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h and include/sr_hip_dcn.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -379,6 +379,33 @@ CA_BF16_SIGNATURES = {
                                     C.c_int, C.c_int, C.c_float, C.c_void_p]),
 }
 
+
+class DcnDesc(C.Structure):
+    """struct sr_dcn_desc (include/sr_hip_dcn.h)."""
+    _fields_ = [('x', C.c_void_p), ('x_img_stride', C.c_int64), ('offset', C.c_void_p), ('offset_img_stride', C.c_int64),
+                ('mask', C.c_void_p), ('mask_img_stride', C.c_int64), ('mask_is_logit', C.c_int), ('wpacked', C.c_void_p),
+                ('bpacked', C.c_void_p), ('out', C.c_void_p), ('out_img_stride', C.c_int64), ('n', C.c_int), ('cin', C.c_int),
+                ('cout', C.c_int), ('h', C.c_int), ('w', C.c_int), ('deformable_groups', C.c_int), ('ksize', C.c_int),
+                ('stride', C.c_int), ('padding', C.c_int), ('dilation', C.c_int), ('groups', C.c_int), ('act_slope', C.c_float)]
+
+
+class DcnBwdDesc(C.Structure):
+    """struct sr_dcn_bwd_desc (include/sr_hip_dcn.h)."""
+    _fields_ = [('fwd', DcnDesc), ('dcol', C.c_void_p), ('dx', C.c_void_p), ('dx_img_stride', C.c_int64), ('doffset', C.c_void_p),
+                ('doffset_img_stride', C.c_int64), ('dmask', C.c_void_p), ('dmask_img_stride', C.c_int64)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_dcn.h declares
+DCN_SIGNATURES = {
+    'sr_dcn_fwd_f32': (C.c_int, [C.POINTER(DcnDesc), C.c_void_p]),
+    'sr_dcn_cols_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'sr_dcn_cols_f32': (C.c_int, [C.POINTER(DcnDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sr_dcn_packed_t_weight_floats': (C.c_size_t, [C.c_int, C.c_int]),
+    'sr_dcn_pack_t_f32': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'sr_dcn_weight_unpack_f32': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    'sr_dcn_bwd_data_f32': (C.c_int, [C.POINTER(DcnBwdDesc), C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -392,7 +419,7 @@ def load():
                          '(or `make -C image_restoration_amd/csrc`). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
-            + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()):
+            + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

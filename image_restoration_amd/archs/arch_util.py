@@ -4,11 +4,15 @@
 and default initialisation; it has no forward — the arithmetic of every layer is issued
 by the owning network through libsr_hip.so.
 """
+import logging
 import math
 
 import torch
 from torch import nn
 from torch.nn import init
+
+from .. import hip_autograd as A
+from ..ops.dcn import ModulatedDeformConvPack
 
 
 class Conv3x3Params(nn.Module):
@@ -84,3 +88,28 @@ class ResidualBlockNoBN(nn.Module):
         self.conv2 = Conv3x3Params(num_feat, num_feat)
         if not pytorch_init:
             default_init_weights([self.conv1, self.conv2], 0.1)
+
+
+class DCNv2Pack(ModulatedDeformConvPack):
+    """Modulated deformable conv for deformable alignment (reference arch_util.py:204-227): unlike ModulatedDeformConvPack the
+    offsets and the mask come from another feature map, ``feat``.  ``conv_offset`` is one sr_conv3x3_f32; the deformable conv
+    reads the two windows of its output in place with the sigmoid in the sampler (include/sr_hip_dcn.h).
+
+    Difference from the reference: its warning when mean|offset| > 50 costs a device reduction and a host synchronisation, so it
+    is evaluated in training mode only (the reference evaluates it on every call)."""
+
+    def forward_cb8(self, x, feat, act_slope=1.0):
+        """CB8 in, CB8 out; LeakyReLU(act_slope) fused into the deformable conv's epilogue."""
+        co = self.offsets_cb8(feat)
+        if self.training:
+            offset_absmean = self.offset_absmean(co)
+            if offset_absmean > 50:
+                logging.getLogger('basicsr').warning(f'Offset abs mean is {offset_absmean}, larger than 50.')
+        return self.deform_cb8(x, co, act_slope)
+
+    def forward(self, x, feat):
+        if x.dtype != torch.float32 or feat.dtype != torch.float32:
+            raise ValueError(f'DCNv2Pack: {x.dtype} / {feat.dtype} input is not supported; supported: fp32')
+        if not (x.is_cuda and feat.is_cuda):
+            raise NotImplementedError
+        return A.FromCB8.apply(self.forward_cb8(A.ToCB8.apply(x), A.ToCB8.apply(feat)), self.out_channels)

@@ -1037,5 +1037,9 @@ extern "C" const char* sr_kernel_name(int id) {
     static const char* wino[3] = {"conv_wino_f32_kernelILi4E", "conv_wino_f32_kernelILi2E", "conv_wino_f32_kernelILi1E"};
     return wino[id - 106];
   }
+  if (id >= 110 && id < 113) {  // dcn_ops.hip (include/sr_hip_dcn.h); 109 stays unnamed
+    static const char* dnames[3] = {"dcn_fwd_f32_kernel", "dcn_cols_kernel", "dcn_bwd_data_kernel"};
+    return dnames[id - 110];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -168,6 +168,16 @@ int backward_overlap();  // sr_dev_set_backward_overlap: -1 automatic (small lau
     }                                                                           \
   } while (0)
 
+// Couts per weight-image group of the fp32 MFMA convs (sr_conv3x3_pack_f32 / sr_convk_pack_f32): 64 where the padded cout is a
+// multiple of 64, else 32.  Usable in pack kernels.
+__host__ __device__ __forceinline__ int group_couts(int cout) { return (((cout + 31) / 32 * 32) % 64 == 0) ? 64 : 32; }
+
+// LDS-DMA of 16 bytes per lane through a buffer descriptor.  Kept in a __device__ function: with the builtin in a kernel body
+// itself, hipcc's host pass drops kernel stubs.
+__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff, char* lds_dst) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

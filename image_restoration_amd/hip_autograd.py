@@ -112,6 +112,76 @@ class ConvFn(torch.autograd.Function):
         return dx, dw, (db if ctx.has_bias else None), None
 
 
+class DCNFn(torch.autograd.Function):
+    """Modulated deformable 3x3/s1/p1 convolution (+bias, +LeakyReLU(act_slope)) on CB8 (include/sr_hip_dcn.h).
+
+    forward(x, offset, mask_or_logits, weight, bias, act_slope, deformable_groups, mask_is_logit[, windows]): ``offset`` /
+    ``mask`` are CB8 tensors of 18 * dg / 9 * dg channels (pad channels ignored).  With ``windows`` = ((first block, blocks) of
+    the offsets, (first block, blocks) of the mask) both arguments are the SAME tensor (DCNv2Pack: the conv_offset output, whose
+    two thirds are block-aligned when dg % 4 == 0); its gradient is then one tensor the kernel writes both windows of, returned
+    as the offset argument's gradient (the mask argument's is None, autograd adds the two).
+    forward  : sr_dcn_fwd_f32
+    backward : LeakyReLU mask against the saved output; columns (sr_dcn_cols_f32) -> sr_convd_wgrad_f32 ksize 1 ->
+               sr_dcn_weight_unpack_f32 for dweight / dbias; dcol = Wt dz (sr_convd_f32 ksize 1 on sr_dcn_pack_t_f32's image);
+               sr_dcn_bwd_data_f32 for doffset / dmask (bit-reproducible) and dx (atomicAdd: last bits depend on arrival order).
+    """
+
+    @staticmethod
+    def forward(ctx, x, offset, mask, weight, bias, act_slope, deformable_groups, mask_is_logit, *extra):
+        dg = deformable_groups
+        windows = extra[0] if extra else None
+        ctx.nextra = len(extra)
+        src = _cb8(x)
+        ctx.windows = windows   # ((off cb0, off cbn), (mask cb0, mask cbn)) when offset and mask are one tensor
+        off_w, mask_w = DCNFn._windows(offset, mask, windows)
+        out = H.dcn_fwd(src, off_w, mask_w, H.cached_pack('f32 fwd', weight, bias, lambda: H.PackedConvK(weight, bias)), dg,
+                        mask_is_logit=mask_is_logit, act_slope=act_slope)
+        ctx.save_for_backward(x, offset, mask if windows is None else None, weight, out.buf if act_slope != 1.0 else None)
+        ctx.act_slope, ctx.has_bias, ctx.dg, ctx.logit = act_slope, bias is not None, dg, bool(mask_is_logit)
+        ctx.param = weight if isinstance(weight, torch.nn.Parameter) else None
+        return out.buf
+
+    @staticmethod
+    def _windows(offset, mask, windows):
+        if windows is None:
+            return _cb8(offset), _cb8(mask)
+        (o0, on), (m0, mn) = windows
+        return H.CB8(offset, o0, on), H.CB8(offset, m0, mn)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, offset, mask, weight, y = ctx.saved_tensors
+        cout, cin = weight.shape[:2]
+        gy = gy.contiguous()
+        dz = _lrelu_bwd(gy, y, ctx.act_slope) if y is not None else gy
+        dzc, src = _cb8(dz), _cb8(x)
+        off_w, mask_w = DCNFn._windows(offset, mask, ctx.windows)
+        need_x, need_o, need_m, need_w, need_b = ctx.needs_input_grad[:5]
+        need_b = need_b and ctx.has_bias
+        if ctx.windows is not None:
+            need_o = need_m = need_o or need_m
+        dx = doff = dmsk = dw = db = None
+        if need_w or need_b:
+            cols = H.dcn_cols(src, off_w, mask_w, ctx.dg, mask_is_logit=ctx.logit)
+            dw, db = H.dcn_wgrad(cols, dzc, cout, cin, want_bias=ctx.has_bias)
+            del cols
+        if need_x or need_o or need_m:
+            dcol = H.convd(dzc, H.cached_pack('f32 dcn t', ctx.param, None, lambda: H.PackedDcnT(weight)))
+            do_w = dm_w = None
+            if need_o or need_m:
+                if ctx.windows is not None:   # one gradient tensor, two windows; blocks outside both stay zero
+                    doff = torch.zeros_like(offset)
+                    (o0, on), (m0, mn) = ctx.windows
+                    do_w, dm_w = H.CB8(doff, o0, on), H.CB8(doff, m0, mn)
+                else:                          # pad channels are not written by the kernel
+                    doff, dmsk = torch.zeros_like(offset), torch.zeros_like(mask)
+                    do_w, dm_w = _cb8(doff), _cb8(dmsk)
+            dxw = H.dcn_bwd_data(dcol, src, off_w, mask_w, ctx.dg, mask_is_logit=ctx.logit, want_dx=need_x, doffset=do_w, dmask=dm_w)
+            dx = dxw.buf if dxw is not None else None
+        return (dx, doff if need_o else None, dmsk if need_m else None, dw if need_w else None, db if need_b else None,
+                None, None, None) + (None,) * ctx.nextra
+
+
 class BNLReLUFn(torch.autograd.Function):
     """nn.BatchNorm2d + LeakyReLU on CB8 or CB16 (sr_bn_lrelu_fwd_f32 / sr_bn_lrelu_bwd_f32, or their _bf16 twins); parameters,
     statistics and running buffers fp32."""

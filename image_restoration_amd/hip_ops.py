@@ -895,3 +895,84 @@ def linear(x, w, b, act_slope=1.0, out=None):
     launch('sr_linear_fwd_f32', x.device, x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), n, k,
            w.shape[0], float(act_slope))
     return y
+
+
+# ---- modulated deformable convolution (DCNv2): forward, columns, scatter / coordinate gradients (include/sr_hip_dcn.h) ----
+
+class PackedDcnT:
+    """ksize-1 forward image of Wt[tap * cin + ci][co] of a 3x3 weight (sr_dcn_pack_t_f32): sr_convd_f32 with it turns dY into
+    the column gradient dcol of 9 * cin channels.  Quacks like a PackedConvK for ``convd``."""
+    ksize, mode, b = 1, 0, None
+
+    def __init__(self, weight):
+        _need_cuda(weight, 'PackedDcnT')
+        weight = weight.detach().contiguous().float()
+        cout, cin = weight.shape[:2]
+        assert weight.shape[2:] == (3, 3) and cin % 8 == 0
+        self.cout, self.src_channels = 9 * cin, (cout + 7) // 8 * 8
+        self.w = torch.empty(_lib.load().sr_dcn_packed_t_weight_floats(cout, cin), dtype=torch.float32, device=weight.device)
+        launch('sr_dcn_pack_t_f32', weight.device, weight.data_ptr(), cout, cin, self.w.data_ptr())
+
+
+def _dcn_desc(d, x, offset, mask, dg, mask_is_logit, cout):
+    """The operand and geometry fields of a struct sr_dcn_desc: ``x`` / ``offset`` / ``mask`` are CB8 windows."""
+    assert (offset.n, offset.h, offset.w) == (mask.n, mask.h, mask.w) == (x.n, x.h, x.w)
+    assert offset.channels >= 18 * dg and mask.channels >= 9 * dg
+    d.x, d.x_img_stride = x.ptr, x.img_stride
+    d.offset, d.offset_img_stride = offset.ptr, offset.img_stride
+    d.mask, d.mask_img_stride, d.mask_is_logit = mask.ptr, mask.img_stride, int(mask_is_logit)
+    d.n, d.cin, d.cout, d.h, d.w, d.deformable_groups = x.n, x.channels, cout, x.h, x.w, dg
+    d.ksize, d.stride, d.padding, d.dilation, d.groups, d.act_slope = 3, 1, 1, 1, 1, 1.0
+    return d
+
+
+def dcn_fwd(x, offset, mask, pc, dg, *, mask_is_logit=False, act_slope=1.0, out=None):
+    """out = lrelu(bias + sum W * mask * bilinear sample of x at the offset positions) — one sr_dcn_fwd_f32 launch.  ``x``: CB8
+    window of cin channels (cin / dg a multiple of 8); ``offset`` / ``mask``: CB8 windows of 18 * dg / 9 * dg channels in the
+    reference's order; ``pc``: PackedConvK or PackedConv (mode 0) of the 3x3 weight."""
+    assert pc.mode == 0 and x.channels == pc.src_channels
+    if out is None:
+        out = CB8.empty(x.n, pc.cout, x.h, x.w, x.device)
+    assert (out.n, out.h, out.w) == (x.n, x.h, x.w) and out.channels >= (pc.cout + 7) // 8 * 8
+    d = _dcn_desc(_lib.DcnDesc(), x, offset, mask, dg, mask_is_logit, pc.cout)
+    d.wpacked, d.bpacked = pc.w.data_ptr(), pc.b.data_ptr() if pc.b is not None else None
+    d.out, d.out_img_stride, d.act_slope = out.ptr, out.img_stride, act_slope
+    launch('sr_dcn_fwd_f32', x.device, C.byref(d))
+    return out
+
+
+def dcn_cols(x, offset, mask, dg, *, mask_is_logit=False):
+    """The masked columns as a CB8 tensor of 9 * cin channels, tap-major — sr_dcn_cols_f32."""
+    cols = CB8.empty(x.n, 9 * x.channels, x.h, x.w, x.device)
+    d = _dcn_desc(_lib.DcnDesc(), x, offset, mask, dg, mask_is_logit, 1)
+    launch('sr_dcn_cols_f32', x.device, C.byref(d), cols.ptr, cols.buf.numel() * 4)
+    return cols
+
+
+def dcn_wgrad(cols, dy, cout, cin, want_bias=True):
+    """(dweight [cout, cin, 3, 3], dbias [cout]) from the columns and the pre-activation output gradient: sr_convd_wgrad_f32
+    with ksize 1 over 9 * cin channels, then sr_dcn_weight_unpack_f32."""
+    dwc, db = convd_wgrad(cols, dy, cout, 9 * cin, ksize=1, want_bias=want_bias)
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=dwc.device)
+    launch('sr_dcn_weight_unpack_f32', dwc.device, dwc.data_ptr(), cout, cin, dw.data_ptr(), 0)
+    return dw, db
+
+
+def dcn_bwd_data(dcol, x, offset, mask, dg, *, mask_is_logit=False, want_dx=True, dx=None, doffset=None, dmask=None):
+    """dx (atomicAdd scatter into a zeroed CB8 tensor, or ADDED into the CB8 window ``dx`` when given; returned, or None) and,
+    into the CB8 windows ``doffset`` / ``dmask`` (given together or not at all), the offset and mask (or logit) gradients — one
+    sr_dcn_bwd_data_f32 launch."""
+    assert dcol.channels == 9 * x.channels and dcol.cb0 == 0 and dcol.cbn == dcol.buf.size(1)
+    if dx is None and want_dx:
+        dx = CB8.zeros(x.n, x.channels, x.h, x.w, x.device)
+    assert dx is None or (dx.n, dx.cbn, dx.h, dx.w) == (x.n, x.cbn, x.h, x.w)
+    d = _lib.DcnBwdDesc()
+    _dcn_desc(d.fwd, x, offset, mask, dg, mask_is_logit, 1)
+    d.dcol = dcol.ptr
+    if dx is not None:
+        d.dx, d.dx_img_stride = dx.ptr, dx.img_stride
+    if doffset is not None:
+        assert doffset.channels >= 18 * dg and dmask.channels >= 9 * dg
+        d.doffset, d.doffset_img_stride, d.dmask, d.dmask_img_stride = doffset.ptr, doffset.img_stride, dmask.ptr, dmask.img_stride
+    launch('sr_dcn_bwd_data_f32', x.device, C.byref(d))
+    return dx
