@@ -55,7 +55,24 @@ struct WinoParams {
   int src_shift;
   int res_cb1;
   float slope, alpha, beta1, beta2;
+#ifdef SR_WINO_STAMP
+  unsigned long long* stamps;  // diagnostic build only (tools/wino_phase.py): [workgroup][8] s_memtime values
+#endif
 };
+
+// Phase stamps of the diagnostic build (`make stamp`: its own library, never the product's): one lane per workgroup writes the clock
+// at entry, behind the first barrier, behind the last chunk's barrier, behind the exchange and behind its last store.
+#ifdef SR_WINO_STAMP
+#define WINO_STAMP(k)                                                                                               \
+  do {                                                                                                              \
+    if (p.stamps && wave == 0 && lane == 0)                                                                         \
+      p.stamps[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + (k)] = __builtin_amdgcn_s_memtime();             \
+  } while (0)
+#else
+#define WINO_STAMP(k) \
+  do {                \
+  } while (0)
+#endif
 
 constexpr int XROW = 66;  // 64 tile columns + halo
 
@@ -93,6 +110,7 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   const int cog = blockIdx.y;
 
   const int lane = threadIdx.x & 63;
+  WINO_STAMP(0);
   const int prow = wave - HF * NW;  // patch row of the tile
   const int j = lane & 31, h = lane >> 5;
   const int x0 = tx * 64, y0 = ty * (2 * NW);
@@ -189,6 +207,7 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   stage_u(0, 0);
   if (nchunk > 1) stage_x(1, 1);
   __syncthreads();
+  WINO_STAMP(1);
   rows(0);
 #pragma unroll
   for (int r = 0; r < 2; ++r) cols(r);
@@ -232,6 +251,7 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   for (int c = 0; c + 2 < nchunk; ++c) chunk(c, yes{}, yes{});
   if (nchunk > 1) chunk(nchunk - 2, yes{}, no{});
   chunk(nchunk - 1, no{}, no{});
+  WINO_STAMP(2);
 
   // ---- output transform Y = A^T (M A), A^T = [1 1 1 0; 0 1 -1 -1]: columns first (per transform row: inside the wave), then rows,
   // one fixed tree.  ra[0], ra[1] are transform rows 2 HF, 2 HF + 1
@@ -272,6 +292,8 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
     }
   }
 
+  WINO_STAMP(3);
+
   // ---- epilogue (that of conv_tile_f32): bias, LeakyReLU, alpha, residual scale-adds, 16-byte CB8 stores.  This half's output row
   // is dy = HF
   const long long HW = (long long)p.H * p.W;
@@ -298,6 +320,7 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
       *(f32x4*)(p.out + (long long)n * p.out_ns + off) = o;
     }
   }
+  WINO_STAMP(4);
 }
 
 template <int NW>
@@ -308,9 +331,16 @@ __global__ __launch_bounds__(NW * 128, 2) void conv_wino_f32_kernel(const WinoPa
   else conv_wino_tile_f32<NW, 1>(p, smem, wave);
 }
 
+#ifdef SR_WINO_STAMP
+unsigned long long* g_wino_stamps = nullptr;
+#endif
+
 template <int NW>
 int launch_wino(const WinoParams& p0, const sr_conv3x3_desc* d, hipStream_t stream) {
   WinoParams p = p0;
+#ifdef SR_WINO_STAMP
+  p.stamps = g_wino_stamps;
+#endif
   p.tiles_x = sr::cdiv(p.W, 64);
   p.tiles_y = sr::cdiv(p.H, 2 * NW);
   constexpr int lds = wino_lds_bytes<NW>();
@@ -423,6 +453,14 @@ extern "C" int sr_dev_set_wino_f32(int mode) {  // development switch (not in th
   g_wino_mode = (mode >= 0 && mode <= 4) ? mode : 1;
   return SR_OK;
 }
+
+#ifdef SR_WINO_STAMP
+// diagnostic build only: device buffer of 8 values per workgroup of the next launches, or null
+extern "C" int sr_dev_set_wino_stamps(unsigned long long* buf) {
+  g_wino_stamps = buf;
+  return SR_OK;
+}
+#endif
 
 // Test hooks: one conv on the Winograd kernel (returns 1 = not eligible, nothing launched), and the weight image of one conv.
 extern "C" int sr_dev_conv3x3_wino_f32(const sr_conv3x3_desc* d, const float* wino_image, void* stream) {

@@ -357,9 +357,16 @@ int forward_impl(const sr_rrdbnet_cfg* cfg, const float* packed, const float* x,
   // sequence on G HIP streams (the caller's + side streams forked/joined with events).  Two kernels are then
   // resident at any time and one group's per-launch ramp-up / drain (measured ~11.6 us of a 79-430 us conv) is
   // covered by the other group's steady state.  Each group keeps >= 512 workgroups per launch (2 per CU).
+  // Default: 2 for an inference forward whose trunk launches are a few rounds of workgroups (at most kGroupAutoWgs of them per
+  // launch: 8 rounds of 512), as the 50-100 us Winograd launches of a batch of 16 128x128 tiles are.  All workgroups of such a
+  // launch run in step: they reach the epilogue's burst of stores together, and the launch fills and drains with MFMAs idle; the
+  // other group's launch runs under that (397.7-398.5 -> 415.1-418.6 images/s; 3 and 4 groups are slower).  A launch of
+  // many rounds (the 544x544 cells of the tiler: 18) has drifted apart by itself and measured 0.1-0.5 % slower in two groups, and
+  // the training forward (direct kernels, 123-470 us launches) < 0.5 % faster (section 7): both keep 1.
+  constexpr long long kGroupAutoWgs = 4096;
   const long long wg_per_image = (long long)sr::cdiv(w, 32) * sr::cdiv(h, 8);
   int groups = sr::forward_groups();
-  if (groups == 0) groups = 1;  // fp32 default: no grouping (include/sr_hip.h)
+  if (groups == 0) groups = (!train && n * wg_per_image <= kGroupAutoWgs) ? 2 : 1;
   while (groups > 1 && (n / groups) * wg_per_image < g_group_min_wgs) --groups;
   if (groups > n) groups = n;
   if (hipMemsetAsync(W.sync, 0, W.sync_ints * kSyncBlocks * sizeof(int32_t), stream) != hipSuccess) {

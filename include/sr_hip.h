@@ -407,9 +407,12 @@ int sr_rrdbnet_forward_f32(const sr_rrdbnet_cfg* cfg, const float* packed, const
 
 /* Tuning knob (process-wide): the whole-network forwards can cut the batch into `groups` image groups (1..4) that run
  * the same launch sequence concurrently on internal side streams forked from / joined to `stream` with events (no host
- * synchronisation, graph-capturable, results bit-identical).  groups = 0 (default) chooses per path: the fp32 forward uses 1
- * (measured on MI355X the overlap buys < 0.5 %: its per-launch cost is LDS-DMA refill traffic and the output-store drain,
- * not idle CUs); the bf16 inference forward uses up to 4 while every group keeps >= 64 workgroups per launch (its 20-80 us launches
+ * synchronisation, graph-capturable, results bit-identical).  groups = 0 (default) chooses per path: the fp32 inference forward
+ * uses 2 while every group keeps >= 512 workgroups per launch and the batch is at most 8 rounds of workgroups per launch (the
+ * workgroups of its 50-100 us Winograd launches run in step, and the other group's launch covers their store bursts, fill and
+ * drain: +2.2 to +4.5 %, by machine, at batch 16 of 128x128 tiles on MI355X; larger launches, such as a batch of 544x544 cells, keep 1); the fp32
+ * training forward uses 1 (on the direct kernels' 123-470 us launches the overlap buys < 0.5 %); the bf16 inference forward
+ * uses up to 4 while every group keeps >= 64 workgroups per launch (its 20-80 us launches
  * spend a third of their time in ramp-up, tail and epilogue drain, which another group's launches fill: +7 % at batch 16,
  * +13 % at batch 32 of 128x128 tiles; the training forward keeps 1, grouping measured no gain there). */
 int sr_set_forward_groups(int groups);
