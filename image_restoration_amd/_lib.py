@@ -1,5 +1,5 @@
 """ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h,
-include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h and include/sr_hip_dcn.h).
+include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h, include/sr_hip_dcn.h and include/sr_hip_edvr.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -406,6 +406,28 @@ DCN_SIGNATURES = {
     'sr_dcn_bwd_data_f32': (C.c_int, [C.POINTER(DcnBwdDesc), C.c_void_p]),
 }
 
+
+class ConvS2Desc(C.Structure):
+    """struct sr_conv3x3s2_desc (include/sr_hip_edvr.h)."""
+    _fields_ = [('in_', C.c_void_p), ('in_img_stride', C.c_int64), ('cin_pad', C.c_int), ('in_h', C.c_int), ('in_w', C.c_int),
+                ('wpacked', C.c_void_p), ('bpacked', C.c_void_p), ('cout', C.c_int), ('out', C.c_void_p),
+                ('out_img_stride', C.c_int64), ('n', C.c_int), ('act_slope', C.c_float)]
+
+
+_P, _S, _I = C.c_void_p, C.c_int64, C.c_int
+# name -> (restype, argtypes); every symbol include/sr_hip_edvr.h declares
+EDVR_SIGNATURES = {
+    'sr_conv3x3s2_f32': (C.c_int, [C.POINTER(ConvS2Desc), _P]),
+    'sr_conv3x3s2_lds_bytes': (C.c_size_t, [_I, _I, _I, _I]),
+    'sr_cb8_zero_insert2_f32': (C.c_int, [_P, _S, _P, _S, _I, _I, _I, _I, _P]),
+    'sr_pool3x3s2_fwd_f32': (C.c_int, [_P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _P]),
+    'sr_pool3x3s2_bwd_f32': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _P]),
+    'sr_tsa_corr_fwd_f32': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _P, _S, _I, _I, _I, _I, _I, _P]),
+    'sr_tsa_corr_bwd_f32': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _S, _P, _P, _P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _I, _P]),
+    'sr_tsa_gate_fwd_f32': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _P]),
+    'sr_tsa_gate_bwd_f32': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _P]),
+}
+
 _lib = None
 
 
@@ -419,7 +441,7 @@ def load():
                          '(or `make -C image_restoration_amd/csrc`). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
-            + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()):
+            + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

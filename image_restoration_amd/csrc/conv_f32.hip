@@ -1041,5 +1041,11 @@ extern "C" const char* sr_kernel_name(int id) {
     static const char* dnames[3] = {"dcn_fwd_f32_kernel", "dcn_cols_kernel", "dcn_bwd_data_kernel"};
     return dnames[id - 110];
   }
+  if (id >= 114 && id < 123) {  // edvr_ops.hip (include/sr_hip_edvr.h); 113 stays unnamed
+    static const char* vnames[9] = {"conv3x3s2_f32_kernel", "cb8_zero_insert2_kernel", "pool3x3s2_fwd_kernel",
+                                    "pool3x3s2_bwd_kernel", "tsa_corr_fwd_kernel",     "tsa_corr_bwd_kernel",
+                                    "tsa_corr_bwd_ref_kernel", "tsa_gate_fwd_kernel",  "tsa_gate_bwd_kernel"};
+    return vnames[id - 114];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -602,3 +602,164 @@ class LReLUFn(torch.autograd.Function):
     def backward(ctx, gy):
         y, = ctx.saved_tensors
         return _lrelu_bwd(gy.contiguous(), y, ctx.slope), None
+
+
+# ---- EDVR (include/sr_hip_edvr.h) ----
+
+class ConvS2Fn(torch.autograd.Function):
+    """3x3 / stride 2 / pad 1 convolution (+bias, +LeakyReLU(act_slope)) on CB8: (H + 1) // 2 x (W + 1) // 2.
+
+    forward  : sr_conv3x3s2_f32
+    backward : LeakyReLU mask against the saved output, sr_cb8_zero_insert2_f32, then the stride-1 operators on the zero-inserted
+               gradient: sr_conv3x3_f32 (mode-1 weights) for dx, sr_conv3x3_wgrad_f32 for dweight / dbias.  Both are exact (the
+               added products are zeros) and each costs one full-resolution conv.
+    """
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act_slope):
+        out = H.conv3x3s2(_cb8(x), H.cached_pack('f32 fwd', weight, bias, lambda: H.PackedConv(weight, bias)), act_slope=act_slope)
+        ctx.save_for_backward(x, weight, out.buf if act_slope != 1.0 else None)
+        ctx.act_slope, ctx.has_bias = act_slope, bias is not None
+        ctx.param = weight if isinstance(weight, torch.nn.Parameter) else None
+        return out.buf
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, y = ctx.saved_tensors
+        cout, cin = weight.shape[:2]
+        gy = gy.contiguous()
+        dz = _lrelu_bwd(gy, y, ctx.act_slope) if y is not None else gy
+        src = _cb8(x)
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        need_b = need_b and ctx.has_bias
+        dx = dw = db = None
+        if need_x or need_w or need_b:
+            full = H.zero_insert2(_cb8(dz), src.h, src.w)
+            if need_x:
+                dx = H.conv3x3(full, H.cached_pack('f32 dgrad', ctx.param, None, lambda: H.PackedConv(weight, None, mode=1))).buf
+                if dx.size(1) != x.size(1):
+                    dx = dx[:, :x.size(1)].contiguous()
+            if need_w or need_b:
+                dw, db = H.conv3x3_wgrad(src, full, cout, cin, want_bias=ctx.has_bias)
+        return dx, dw, (db if ctx.has_bias else None), None
+
+
+class Conv1x1Fn(torch.autograd.Function):
+    """1x1 convolution (+bias, +LeakyReLU(act_slope)) on CB8.
+
+    forward  : sr_convd_f32 with ksize 1
+    backward : LeakyReLU mask against the saved output; sr_convd_f32 with ksize 1 on the mode-1 image for dx;
+               sr_convd_wgrad_f32 with ksize 1 for dweight / dbias.
+    """
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act_slope):
+        out = H.convd(_cb8(x), H.cached_pack('f32 fwd 1x1', weight, bias, lambda: H.PackedConvK(weight, bias)), act_slope=act_slope)
+        ctx.save_for_backward(x, weight, out.buf if act_slope != 1.0 else None)
+        ctx.act_slope, ctx.has_bias = act_slope, bias is not None
+        ctx.param = weight if isinstance(weight, torch.nn.Parameter) else None
+        return out.buf
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, y = ctx.saved_tensors
+        cout, cin = weight.shape[:2]
+        gy = gy.contiguous()
+        dz = _lrelu_bwd(gy, y, ctx.act_slope) if y is not None else gy
+        dzc, src = _cb8(dz), _cb8(x)
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        need_b = need_b and ctx.has_bias
+        dx = dw = db = None
+        if need_x:
+            dx = H.convd(dzc, H.cached_pack('f32 dgrad 1x1', ctx.param, None, lambda: H.PackedConvK(weight, None, mode=1))).buf
+            if dx.size(1) != x.size(1):
+                dx = dx[:, :x.size(1)].contiguous()
+        if need_w or need_b:
+            dw, db = H.convd_wgrad(src, dzc, cout, cin, ksize=1, want_bias=ctx.has_bias)
+        return dx, dw, (db if ctx.has_bias else None), None
+
+
+class Pool3x3s2Fn(torch.autograd.Function):
+    """torch.cat([MaxPool2d(3, 2, 1)(x), AvgPool2d(3, 2, 1)(x)], 1) on CB8 (sr_pool3x3s2_fwd_f32 / sr_pool3x3s2_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return H.pool3x3s2(_cb8(x)).buf
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        return H.pool3x3s2_bwd(_cb8(x), _cb8(g.contiguous())).buf
+
+
+class TSACorrFn(torch.autograd.Function):
+    """TSA's temporal attention on CB8: forward(emb [b*t], emb_ref [b], aligned [b*t], t) -> aligned * sigmoid(sum_c emb *
+    emb_ref) as [b, t * C/8, h, w, 8], the channel concatenation over the frames (the same memory as [b*t, C/8, h, w, 8]) —
+    sr_tsa_corr_fwd_f32 / sr_tsa_corr_bwd_f32."""
+
+    @staticmethod
+    def forward(ctx, emb, emb_ref, aligned, t):
+        emb, emb_ref, aligned = emb.contiguous(), emb_ref.contiguous(), aligned.contiguous()
+        prob, out = H.tsa_corr(_cb8(emb), _cb8(emb_ref), _cb8(aligned), t)
+        ctx.save_for_backward(emb, emb_ref, aligned, prob)
+        bt, cb, h, w, _ = out.buf.shape
+        return out.buf.view(bt // t, t * cb, h, w, 8)
+
+    @staticmethod
+    def backward(ctx, g):
+        emb, emb_ref, aligned, prob = ctx.saved_tensors
+        g = g.contiguous().view(emb.shape)
+        dal, demb, dref = H.tsa_corr_bwd(_cb8(g), _cb8(emb), _cb8(emb_ref), _cb8(aligned), prob)
+        return demb.buf, dref.buf, dal.buf, None
+
+
+class TSAGateFn(torch.autograd.Function):
+    """feat * sigmoid(attn) * 2 + attn_add on CB8 (sr_tsa_gate_fwd_f32 / sr_tsa_gate_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, feat, attn, attn_add):
+        feat, attn, attn_add = feat.contiguous(), attn.contiguous(), attn_add.contiguous()
+        ctx.save_for_backward(feat, attn)
+        return H.tsa_gate(_cb8(feat), _cb8(attn), _cb8(attn_add)).buf
+
+    @staticmethod
+    def backward(ctx, g):
+        feat, attn = ctx.saved_tensors
+        g = g.contiguous()
+        df, da = H.tsa_gate_bwd(_cb8(g), _cb8(feat), _cb8(attn))
+        return df.buf, da.buf, g
+
+
+class PixelShuffleFn(torch.autograd.Function):
+    """nn.PixelShuffle(r) on CB8, ``channels`` real output channels (sr_cb8_pixel_shuffle_f32 / sr_cb8_pixel_unshuffle_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, channels, r):
+        ctx.args = (channels, r)
+        return H.pixel_shuffle(_cb8(x.contiguous()), channels, r).buf
+
+    @staticmethod
+    def backward(ctx, g):
+        channels, r = ctx.args
+        return H.pixel_unshuffle(_cb8(g.contiguous()), channels, r).buf, None, None
+
+
+class BilinearUpFn(torch.autograd.Function):
+    """F.interpolate(x, scale_factor=s, mode='bilinear', align_corners=False) on NCHW fp32, added into ``acc`` [N, C, s*H, s*W]
+    in place when given (sr_bilinear_up_f32 / sr_bilinear_up_bwd_f32); both inputs receive gradients."""
+
+    @staticmethod
+    def forward(ctx, x, s, acc=None):
+        ctx.s, ctx.has_acc = s, acc is not None
+        if acc is None:
+            return H.bilinear_up(x, s)
+        ctx.mark_dirty(acc)
+        H.bilinear_up(x, s, out=acc)
+        return acc
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        return (H.bilinear_up_bwd(g, ctx.s) if ctx.needs_input_grad[0] else None), None, (g if ctx.has_acc else None)

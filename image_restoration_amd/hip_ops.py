@@ -976,3 +976,119 @@ def dcn_bwd_data(dcol, x, offset, mask, dg, *, mask_is_logit=False, want_dx=True
         d.doffset, d.doffset_img_stride, d.dmask, d.dmask_img_stride = doffset.ptr, doffset.img_stride, dmask.ptr, dmask.img_stride
     launch('sr_dcn_bwd_data_f32', x.device, C.byref(d))
     return dx
+
+
+# ---- EDVR: stride-2 conv and its zero insertion, TSA's pooling, correlation and gate (include/sr_hip_edvr.h) ----
+
+def _arg(cond, msg):
+    """Bad arguments of the EDVR wrappers are ValueErrors (the C ABI's SR_EINVAL)."""
+    if not cond:
+        raise ValueError(msg)
+
+
+def _same(a, *others):
+    return all((o.n, o.cbn, o.h, o.w) == (a.n, a.cbn, a.h, a.w) for o in others)
+
+
+def conv3x3s2(src, pc, out=None, *, act_slope=1.0):
+    """out = lrelu(conv(src) + bias) for a 3x3 / stride 2 / pad 1 conv: (H + 1) // 2 x (W + 1) // 2 — one sr_conv3x3s2_f32
+    launch.  ``pc``: PackedConvK or PackedConv (mode 0) of the 3x3 weight."""
+    _arg(pc.mode == 0 and getattr(pc, 'ksize', 3) == 3, 'conv3x3s2: needs the forward image of a 3x3 weight')
+    _arg(src.channels == pc.src_channels, f'conv3x3s2: source has {src.channels} channels, the weight image {pc.src_channels}')
+    ho, wo = (src.h + 1) // 2, (src.w + 1) // 2
+    if out is None:
+        out = CB8.empty(src.n, pc.cout, ho, wo, src.device)
+    _arg((out.n, out.h, out.w) == (src.n, ho, wo) and out.channels >= (pc.cout + 7) // 8 * 8, 'conv3x3s2: output window does not fit')
+    d = _lib.ConvS2Desc()
+    d.in_, d.in_img_stride, d.cin_pad, d.in_h, d.in_w = src.ptr, src.img_stride, pc.src_channels, src.h, src.w
+    d.wpacked, d.bpacked, d.cout = pc.w.data_ptr(), pc.b.data_ptr() if pc.b is not None else None, pc.cout
+    d.out, d.out_img_stride, d.n, d.act_slope = out.ptr, out.img_stride, src.n, act_slope
+    launch('sr_conv3x3s2_f32', src.device, C.byref(d))
+    return out
+
+
+def zero_insert2(dy, h, w, out=None):
+    """``dy`` ((h + 1) // 2 x (w + 1) // 2) at the even positions of a zero-filled h x w tensor — sr_cb8_zero_insert2_f32."""
+    _arg((dy.h, dy.w) == ((h + 1) // 2, (w + 1) // 2), f'zero_insert2: {dy.h}x{dy.w} is not the stride-2 size of {h}x{w}')
+    if out is None:
+        out = CB8.empty(dy.n, dy.channels, h, w, dy.device)
+    _arg((out.n, out.cbn, out.h, out.w) == (dy.n, dy.cbn, h, w), 'zero_insert2: output window does not fit')
+    launch('sr_cb8_zero_insert2_f32', dy.device, dy.ptr, dy.img_stride, out.ptr, out.img_stride, dy.n, dy.cbn, h, w)
+    return out
+
+
+def pool3x3s2(src, out=None):
+    """torch.cat([MaxPool2d(3, 2, 1)(x), AvgPool2d(3, 2, 1)(x)], 1) as one CB8 tensor of 2 * channels — one sr_pool3x3s2_fwd_f32
+    launch writing both windows.  ``out``: a CB8 window of 2 * src.cbn blocks."""
+    ho, wo = (src.h + 1) // 2, (src.w + 1) // 2
+    if out is None:
+        out = CB8.empty(src.n, 2 * src.channels, ho, wo, src.device)
+    _arg((out.n, out.cbn, out.h, out.w) == (src.n, 2 * src.cbn, ho, wo), 'pool3x3s2: output window does not fit')
+    mx, av = CB8(out.buf, out.cb0, src.cbn), CB8(out.buf, out.cb0 + src.cbn, src.cbn)
+    launch('sr_pool3x3s2_fwd_f32', src.device, src.ptr, src.img_stride, mx.ptr, mx.img_stride, av.ptr, av.img_stride, src.n,
+           src.cbn, src.h, src.w)
+    return out
+
+
+def pool3x3s2_bwd(src, g, out=None):
+    """dx of pool3x3s2 from its source and ``g``, the gradient of the [max, avg] tensor — sr_pool3x3s2_bwd_f32."""
+    ho, wo = (src.h + 1) // 2, (src.w + 1) // 2
+    _arg((g.n, g.cbn, g.h, g.w) == (src.n, 2 * src.cbn, ho, wo), 'pool3x3s2_bwd: gradient does not fit the source')
+    if out is None:
+        out = CB8.empty(src.n, src.channels, src.h, src.w, src.device)
+    _arg(_same(src, out), 'pool3x3s2_bwd: output window does not fit')
+    gm, ga = CB8(g.buf, g.cb0, src.cbn), CB8(g.buf, g.cb0 + src.cbn, src.cbn)
+    launch('sr_pool3x3s2_bwd_f32', src.device, src.ptr, src.img_stride, gm.ptr, gm.img_stride, ga.ptr, ga.img_stride, out.ptr,
+           out.img_stride, src.n, src.cbn, src.h, src.w)
+    return out
+
+
+def tsa_corr(emb, emb_ref, aligned, t, out=None):
+    """TSA's temporal attention: (prob [b, t, h, w], aligned * prob as CB8 [b * t, c]) with prob = sigmoid(sum_c emb * emb_ref) —
+    one sr_tsa_corr_fwd_f32 launch.  ``emb`` / ``aligned``: CB8 windows of b * t images, ``emb_ref``: of b images."""
+    _arg(t >= 1 and emb.n == emb_ref.n * t, f'tsa_corr: {emb.n} frames are not {emb_ref.n} x {t}')
+    _arg(_same(emb, aligned) and (emb_ref.cbn, emb_ref.h, emb_ref.w) == (emb.cbn, emb.h, emb.w), 'tsa_corr: shapes differ')
+    if out is None:
+        out = CB8.empty(emb.n, emb.channels, emb.h, emb.w, emb.device)
+    _arg(_same(emb, out), 'tsa_corr: output window does not fit')
+    prob = torch.empty((emb_ref.n, t, emb.h, emb.w), dtype=torch.float32, device=emb.device)
+    launch('sr_tsa_corr_fwd_f32', emb.device, emb.ptr, emb.img_stride, emb_ref.ptr, emb_ref.img_stride, aligned.ptr,
+           aligned.img_stride, prob.data_ptr(), out.ptr, out.img_stride, emb_ref.n, t, emb.channels, emb.h, emb.w)
+    return prob, out
+
+
+def tsa_corr_bwd(g, emb, emb_ref, aligned, prob):
+    """(d aligned, d emb, d emb_ref) of tsa_corr from ``g``, the gradient of its CB8 output — sr_tsa_corr_bwd_f32."""
+    b, t = prob.shape[:2]
+    _arg(prob.is_contiguous() and prob.dtype == torch.float32 and tuple(prob.shape) == (emb_ref.n, t, emb.h, emb.w) and emb.n == b * t,
+         'tsa_corr_bwd: prob does not fit')
+    _arg(_same(emb, aligned, g) and (emb_ref.cbn, emb_ref.h, emb_ref.w) == (emb.cbn, emb.h, emb.w), 'tsa_corr_bwd: shapes differ')
+    dal = CB8.empty(emb.n, emb.channels, emb.h, emb.w, emb.device)
+    demb = CB8.empty(emb.n, emb.channels, emb.h, emb.w, emb.device)
+    dref = CB8.empty(b, emb.channels, emb.h, emb.w, emb.device)
+    dcorr = torch.empty_like(prob)
+    launch('sr_tsa_corr_bwd_f32', emb.device, g.ptr, g.img_stride, emb.ptr, emb.img_stride, emb_ref.ptr, emb_ref.img_stride,
+           aligned.ptr, aligned.img_stride, prob.data_ptr(), dcorr.data_ptr(), dal.ptr, dal.img_stride, demb.ptr, demb.img_stride,
+           dref.ptr, dref.img_stride, b, t, emb.channels, emb.h, emb.w)
+    return dal, demb, dref
+
+
+def tsa_gate(feat, attn, attn_add, out=None):
+    """out = feat * sigmoid(attn) * 2 + attn_add on CB8 windows of equal shape — sr_tsa_gate_fwd_f32."""
+    _arg(_same(feat, attn, attn_add), 'tsa_gate: shapes differ')
+    if out is None:
+        out = CB8.empty(feat.n, feat.channels, feat.h, feat.w, feat.device)
+    _arg(_same(feat, out), 'tsa_gate: output window does not fit')
+    launch('sr_tsa_gate_fwd_f32', feat.device, feat.ptr, feat.img_stride, attn.ptr, attn.img_stride, attn_add.ptr,
+           attn_add.img_stride, out.ptr, out.img_stride, feat.n, feat.cbn, feat.h, feat.w)
+    return out
+
+
+def tsa_gate_bwd(g, feat, attn):
+    """(d feat, d attn) of tsa_gate from ``g``, the gradient of its output (d attn_add is ``g``) — sr_tsa_gate_bwd_f32."""
+    _arg(_same(feat, attn, g), 'tsa_gate_bwd: shapes differ')
+    df = CB8.empty(feat.n, feat.channels, feat.h, feat.w, feat.device)
+    da = CB8.empty(feat.n, feat.channels, feat.h, feat.w, feat.device)
+    launch('sr_tsa_gate_bwd_f32', feat.device, g.ptr, g.img_stride, feat.ptr, feat.img_stride, attn.ptr, attn.img_stride, df.ptr,
+           df.img_stride, da.ptr, da.img_stride, feat.n, feat.cbn, feat.h, feat.w)
+    return df, da
