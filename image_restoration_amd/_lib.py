@@ -428,6 +428,29 @@ EDVR_SIGNATURES = {
     'sr_tsa_gate_bwd_f32': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _P]),
 }
 
+
+class DcnBf16Desc(C.Structure):
+    """struct sr_dcn_bf16_desc (include/sr_hip_edvr_bf16.h)."""
+    _fields_ = [('x', C.c_void_p), ('x_img_stride', C.c_int64), ('offset', C.c_void_p), ('offset_img_stride', C.c_int64),
+                ('mask', C.c_void_p), ('mask_img_stride', C.c_int64), ('mask_is_logit', C.c_int), ('wpacked', C.c_void_p),
+                ('bpacked', C.c_void_p), ('out', C.c_void_p), ('out_img_stride', C.c_int64), ('n', C.c_int), ('cin', C.c_int),
+                ('cout', C.c_int), ('h', C.c_int), ('w', C.c_int), ('deformable_groups', C.c_int), ('ksize', C.c_int),
+                ('stride', C.c_int), ('padding', C.c_int), ('dilation', C.c_int), ('groups', C.c_int), ('act_slope', C.c_float)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_edvr_bf16.h declares
+EDVR_BF16_SIGNATURES = {
+    'sr_dcn_fwd_bf16': (C.c_int, [C.POINTER(DcnBf16Desc), _P]),
+    'sr_dcn_bf16_lds_bytes': (C.c_size_t, [_I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'sr_conv1x1_packed_weight_elems_bf16': (C.c_size_t, [_I, _I]),
+    'sr_conv1x1_pack_bf16': (C.c_int, [_P, _P, _I, _I, _P, _P, _P]),
+    'sr_conv1x1_bf16': (C.c_int, [_P, _S, _P, _P, _P, _S, _I, _I, _I, _I, _I, C.c_float, _P]),
+    'sr_cb16_subsample2_bf16': (C.c_int, [_P, _S, _P, _S, _I, _I, _I, _I, _P]),
+    'sr_pool3x3s2_fwd_bf16': (C.c_int, [_P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _P]),
+    'sr_tsa_corr_fwd_bf16': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _P, _S, _I, _I, _I, _I, _I, _P]),
+    'sr_tsa_gate_fwd_bf16': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _P]),
+}
+
 _lib = None
 
 
@@ -441,7 +464,8 @@ def load():
                          '(or `make -C image_restoration_amd/csrc`). There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
-            + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()):
+            + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
+            + list(EDVR_BF16_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

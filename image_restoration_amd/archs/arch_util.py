@@ -12,6 +12,7 @@ from torch import nn
 from torch.nn import init
 
 from .. import hip_autograd as A
+from .. import hip_ops as H
 from ..ops.dcn import ModulatedDeformConvPack
 
 
@@ -106,6 +107,16 @@ class DCNv2Pack(ModulatedDeformConvPack):
             if offset_absmean > 50:
                 logging.getLogger('basicsr').warning(f'Offset abs mean is {offset_absmean}, larger than 50.')
         return self.deform_cb8(x, co, act_slope)
+
+    def forward_cb16(self, x, feat, act_slope=1.0):
+        """The bf16 inference path: hip_ops.CB16 in, CB16 out.  ``conv_offset`` is one sr_conv3x3_bf16 that stores its 27 * dg
+        outputs as fp32 NCHW planes (offsets keep fp32 resolution), which sr_dcn_fwd_bf16 reads in place with the sigmoid in the
+        sampler.  No offset warning: this path is inference."""
+        dg = self.deformable_groups
+        co = torch.empty((feat.n, 27 * dg, feat.h, feat.w), dtype=torch.float32, device=feat.device)
+        H.conv3x3_bf16(feat, H.packed_conv_bf16(self.conv_offset), out_nchw=co)
+        return H.dcn_fwd_bf16(x, co[:, :18 * dg], co[:, 18 * dg:], H.packed_conv_bf16(self), dg, mask_is_logit=True,
+                              act_slope=act_slope)
 
     def forward(self, x, feat):
         if x.dtype != torch.float32 or feat.dtype != torch.float32:

@@ -19,11 +19,18 @@ The frames are a batch: PCD alignment runs ONCE on the b*t images with the centr
 reference calls it t times); every image is processed independently, so the result is the per-frame loop's bit for bit, and the
 expand's autograd sums the reference pyramid's gradients over t.  Channel concatenation, frame selection and the expand are
 tensor plumbing on the CB8 storage.
+
+``EDVR(..., compute_dtype='bf16')`` (forward only) runs the same layer list on hip_ops.CB16 windows between
+sr_nchw_to_cb16_bf16 and conv_last's fp32 NCHW store: sr_conv3x3_bf16 (the stride-2 convs followed by sr_cb16_subsample2_bf16),
+sr_dcn_fwd_bf16 on fp32 offset / mask planes, sr_conv1x1_bf16, sr_pool3x3s2_fwd_bf16, sr_tsa_corr_fwd_bf16, sr_tsa_gate_fwd_bf16,
+sr_bilinear2x_fwd_bf16, sr_cb16_pixel_shuffle_bf16; the x4 base is still sr_bilinear_up_f32 of the fp32 centre frame.  Each
+module's ``forward_cb16`` is its ``forward_cb8`` on those launches.
 """
 import torch
 from torch import nn
 
 from .. import hip_autograd as A
+from .. import hip_ops as H
 from ..utils.registry import ARCH_REGISTRY
 from .arch_util import Conv3x3Params, DCNv2Pack, ResidualBlockNoBN, make_layer
 
@@ -43,6 +50,33 @@ def _conv1x1(m, x, slope=0.1):
 def _resblock(m, x):
     """ResidualBlockNoBN: x + conv2(relu(conv1(x)))."""
     return A.AddFn.apply(x, _conv(m.conv2, _conv(m.conv1, x, 0.0), 1.0))
+
+
+# ---- the bf16 inference path: hip_ops.CB16 windows between sr_nchw_to_cb16_bf16 and conv_last's fp32 NCHW store ----
+
+def _conv16(m, x, slope=0.1, **kw):
+    return H.conv3x3_bf16(x, H.packed_conv_bf16(m), act_slope=slope, **kw)
+
+
+def _conv_s2_16(m, x, slope=0.1):
+    """3x3 / stride 2 / pad 1: the stride-1 conv sampled at the even positions (4x the MACs of a native stride-2 kernel)."""
+    return H.subsample2_bf16(_conv16(m, x, slope))
+
+
+def _conv1x1_16(m, x, slope=0.1):
+    return H.conv1x1_bf16(x, H.packed_conv_bf16(m), act_slope=slope)
+
+
+def _resblock16(m, x, extra=None):
+    """ResidualBlockNoBN (+ ``extra``): both additions in conv2's epilogue, one rounding."""
+    kw = dict(res2=extra, beta2=1.0) if extra is not None else {}
+    return _conv16(m.conv2, _conv16(m.conv1, x, 0.0), 1.0, res1=x, beta1=1.0, **kw)
+
+
+def _cat16(*ts):
+    """torch.cat along the channel-block dimension of whole CB16 tensors."""
+    assert all(t.cb0 == 0 and t.cbn == t.buf.size(1) for t in ts)
+    return H.CB16(torch.cat([t.buf for t in ts], dim=1))
 
 
 def _check_input(x, what, dims):
@@ -125,6 +159,28 @@ class PCDAlignment(nn.Module):
         offset = conv(self.cas_offset_conv2, conv(self.cas_offset_conv1, torch.cat([feat, ref[0]], dim=1)))
         return self.cas_dcnpack.forward_cb8(feat, offset, 0.1)
 
+    def forward_cb16(self, nbr, ref):
+        """forward_cb8's layer list on hip_ops.CB16 windows (bf16 inference): the pyramids as lists of CB16 -> aligned L1, CB16."""
+        upsampled_offset, upsampled_feat = None, None
+        for i in range(3, 0, -1):
+            level = f'l{i}'
+            offset = _conv16(self.offset_conv1[level], _cat16(nbr[i - 1], ref[i - 1]))
+            if i == 3:
+                offset = _conv16(self.offset_conv2[level], offset)
+            else:
+                offset = _conv16(self.offset_conv2[level], _cat16(offset, upsampled_offset))
+                offset = _conv16(self.offset_conv3[level], offset)
+            if i < 3:
+                feat = self.dcn_pack[level].forward_cb16(nbr[i - 1], offset)
+                feat = _conv16(self.feat_conv[level], _cat16(feat, upsampled_feat), 0.1 if i > 1 else 1.0)
+            else:
+                feat = self.dcn_pack[level].forward_cb16(nbr[i - 1], offset, 0.1)
+            if i > 1:
+                upsampled_offset = H.cb16_scale(H.bilinear2x_bf16(offset), 2.0)   # exact: a power of two
+                upsampled_feat = H.bilinear2x_bf16(feat)
+        offset = _conv16(self.cas_offset_conv2, _conv16(self.cas_offset_conv1, _cat16(feat, ref[0])))
+        return self.cas_dcnpack.forward_cb16(feat, offset, 0.1)
+
     def forward(self, nbr_feat_l, ref_feat_l):
         for t in list(nbr_feat_l) + list(ref_feat_l):
             if not t.is_cuda:
@@ -199,6 +255,30 @@ class TSAFusion(nn.Module):
         # sigmoid(attn) * 2 is about 1 for a freshly initialised branch (attn near 0), so the gate starts as the identity
         return A.TSAGateFn.apply(feat, attn, attn_add)
 
+    def forward_cb16(self, aligned, b, t):
+        """forward_cb8's layer list on hip_ops.CB16 windows (bf16 inference); ``aligned``: a whole CB16 tensor of b * t images."""
+        bt, cb, h, w = aligned.n, aligned.cbn, aligned.h, aligned.w
+        if bt != b * t or t != self.num_frame:
+            raise ValueError(f'TSAFusion: {bt} images are not {b} x num_frame={self.num_frame}')
+        if h % 4 or w % 4:
+            raise ValueError(f'TSAFusion: the height and width must be multiples of 4 (got {h}x{w})')
+        center = H.CB16(aligned.buf.view(b, t, cb, h, w, 16)[:, self.center_frame_idx].contiguous())
+        embedding_ref = _conv16(self.temporal_attn1, center, 1.0)
+        embedding = _conv16(self.temporal_attn2, aligned, 1.0)
+        fused = H.tsa_corr_bf16(embedding, embedding_ref, aligned, t)
+        fused = H.CB16(fused.buf.view(b, t * cb, h, w, 16))                 # (b, t*c): what the fusion convs read
+        feat = _conv1x1_16(self.feat_fusion, fused)
+        attn = _conv1x1_16(self.spatial_attn1, fused)
+        attn = _conv1x1_16(self.spatial_attn2, H.pool3x3s2_bf16(attn))
+        attn_level = _conv1x1_16(self.spatial_attn_l1, attn)
+        attn_level = _conv16(self.spatial_attn_l2, H.pool3x3s2_bf16(attn_level))
+        attn_level = H.bilinear2x_bf16(_conv16(self.spatial_attn_l3, attn_level))
+        attn = _conv16(self.spatial_attn3, attn, res1=attn_level, beta1=1.0)   # the addition in the conv's epilogue
+        attn = H.bilinear2x_bf16(_conv1x1_16(self.spatial_attn4, attn))
+        attn = _conv16(self.spatial_attn5, attn, 1.0)
+        attn_add = _conv1x1_16(self.spatial_attn_add2, _conv1x1_16(self.spatial_attn_add1, attn), 1.0)
+        return H.tsa_gate_bf16(feat, attn, attn_add)
+
     def forward(self, aligned_feat):
         _check_input(aligned_feat, 'TSAFusion', 5)
         b, t, c, h, w = aligned_feat.shape
@@ -267,6 +347,27 @@ class PredeblurModule(nn.Module):
             feat_l1 = _resblock(self.resblock_l1[i], feat_l1)
         return feat_l1
 
+    def forward_cb16(self, x):
+        """forward_cb8's layer list on hip_ops.CB16 windows (bf16 inference); the two additions run in the epilogue of the
+        preceding residual block's second conv."""
+        self._check_size(x.h, x.w)
+        feat_l1 = _conv16(self.conv_first, x)
+        if self.hr_in:
+            feat_l1 = _conv_s2_16(self.stride_conv_hr1, feat_l1)
+            feat_l1 = _conv_s2_16(self.stride_conv_hr2, feat_l1)
+        feat_l2 = _conv_s2_16(self.stride_conv_l2, feat_l1)
+        feat_l3 = _conv_s2_16(self.stride_conv_l3, feat_l2)
+
+        feat_l3 = H.bilinear2x_bf16(_resblock16(self.resblock_l3, feat_l3))
+        feat_l2 = _resblock16(self.resblock_l2_1, feat_l2, feat_l3)
+        feat_l2 = H.bilinear2x_bf16(_resblock16(self.resblock_l2_2, feat_l2))
+
+        feat_l1 = _resblock16(self.resblock_l1[0], feat_l1)
+        feat_l1 = _resblock16(self.resblock_l1[1], feat_l1, feat_l2)
+        for i in range(2, 5):
+            feat_l1 = _resblock16(self.resblock_l1[i], feat_l1)
+        return feat_l1
+
     def forward(self, x):
         _check_input(x, 'PredeblurModule', 4)
         self._check_size(x.size(2), x.size(3))
@@ -296,6 +397,11 @@ class EDVR(nn.Module):
         hr_in (bool): the input already has the output's size (needs with_predeblur).  Default: False.
         with_predeblur (bool): run PredeblurModule and a 1x1 conv instead of the first conv.  Default: False.
         with_tsa (bool): fuse with TSAFusion; otherwise with one 1x1 conv over the t * num_feat channels.  Default: True.
+        compute_dtype (str): this project's own key, 'fp32' or 'bf16' (anything else is a ValueError).  'bf16' needs num_feat to
+            be a multiple of 16 (CB16 activations) and is forward only (eval mode or no_grad): bf16 activations and weight
+            images rounded from the fp32 parameters, fp32 accumulation, offsets and mask logits of the deformable convs in
+            fp32, conv_last and the x4 base of the fp32 centre frame in fp32.  The parameters, their names and their
+            initialisation do not depend on it.  Default: 'fp32'.
     """
 
     def __init__(self,
@@ -309,11 +415,17 @@ class EDVR(nn.Module):
                  center_frame_idx=None,
                  hr_in=False,
                  with_predeblur=False,
-                 with_tsa=True):
+                 with_tsa=True,
+                 compute_dtype='fp32'):
         super().__init__()
+        if compute_dtype not in ('fp32', 'bf16'):
+            raise ValueError(f"compute dtype must be 'fp32' or 'bf16', got {compute_dtype!r}")
         if deformable_groups <= 0 or num_feat % (8 * deformable_groups):
             raise ValueError(f'EDVR: num_feat={num_feat} must be a multiple of 8 * deformable_groups={deformable_groups} '
                              '(a CB8 block never straddles two deformable groups)')
+        if compute_dtype == 'bf16' and num_feat % 16:
+            raise ValueError(f'EDVR in bf16 needs num_feat to be a multiple of 16 (CB16 activations), got {num_feat!r}')
+        self.compute_dtype = compute_dtype
         if hr_in and not with_predeblur:
             raise ValueError('EDVR: hr_in needs with_predeblur=True (only the pre-deblur module brings a high-resolution input '
                              'down by 4; without it the x4 output cannot be added to the centre frame)')
@@ -364,6 +476,44 @@ class EDVR(nn.Module):
             ref_l.append(c.expand(b, t, cb, h, w, 8).reshape(b * t, cb, h, w, 8))
         return self.pcd_align.forward_cb8(feat_l, ref_l)
 
+    def forward_bf16(self, x):
+        """The layer list of ``forward`` on CB16 bf16 activations; fp32 NCHW in and out."""
+        b, t, c, h, w = x.shape
+        ci = self.center_frame_idx
+        x_center = x[:, ci].contiguous()
+        frames = H.nchw_to_cb16(x.reshape(b * t, c, h, w))
+        if self.with_predeblur:
+            feat_l1 = _conv1x1_16(self.conv_1x1, self.predeblur.forward_cb16(frames), 1.0)
+        else:
+            feat_l1 = _conv16(self.conv_first, frames)
+        for blk in self.feature_extraction:
+            feat_l1 = _resblock16(blk, feat_l1)
+        feat_l2 = _conv16(self.conv_l2_2, _conv_s2_16(self.conv_l2_1, feat_l1))
+        feat_l3 = _conv16(self.conv_l3_2, _conv_s2_16(self.conv_l3_1, feat_l2))
+
+        feat_l = [feat_l1, feat_l2, feat_l3]
+        ref_l = []
+        for f in feat_l:   # the centre frame's pyramid expanded over t
+            v = f.buf.view(b, t, f.cbn, f.h, f.w, 16)[:, ci:ci + 1]
+            ref_l.append(H.CB16(v.expand(b, t, f.cbn, f.h, f.w, 16).reshape(b * t, f.cbn, f.h, f.w, 16).contiguous()))
+        aligned = self.pcd_align.forward_cb16(feat_l, ref_l)
+
+        if self.with_tsa:
+            out = self.fusion.forward_cb16(aligned, b, t)
+        else:
+            fused = H.CB16(aligned.buf.view(b, t * aligned.cbn, aligned.h, aligned.w, 16))
+            out = _conv1x1_16(self.fusion, fused, 1.0)
+        for blk in self.reconstruction:
+            out = _resblock16(blk, out)
+        out = H.pixel_shuffle_bf16(_conv16(self.upconv1, out), self.num_feat, 2)
+        out = H.pixel_shuffle_bf16(_conv16(self.upconv2, out), 64, 2)
+        out = _conv16(self.conv_hr, out)
+        y = torch.empty((b, 3, out.h, out.w), dtype=torch.float32, device=x.device)
+        _conv16(self.conv_last, out, 1.0, out_nchw=y)
+        if self.hr_in:
+            return A.AddFn.apply(y, x_center)
+        return H.bilinear_up(x_center, 4, out=y)
+
     def forward(self, x):
         _check_input(x, 'EDVR', 5)
         b, t, c, h, w = x.shape
@@ -373,6 +523,13 @@ class EDVR(nn.Module):
         if h % m or w % m:
             raise ValueError(f'EDVR: the height and width must be multiples of {m} (got {h}x{w})')
         _need_gpu(x)
+        if self.compute_dtype == 'bf16':
+            needs_graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+            if needs_graph and self.training:
+                raise NotImplementedError("EDVR with compute_dtype='bf16' is forward only (eval mode or torch.no_grad()); train "
+                                          "with compute_dtype='fp32'")
+            with torch.no_grad():
+                return self.forward_bf16(x)
 
         x_center = x[:, self.center_frame_idx].contiguous()
         frames = A.ToCB8.apply(x.reshape(b * t, c, h, w))

@@ -1047,5 +1047,10 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "tsa_corr_bwd_ref_kernel", "tsa_gate_fwd_kernel",  "tsa_gate_bwd_kernel"};
     return vnames[id - 114];
   }
+  if (id >= 124 && id < 130) {  // dcn_ops_bf16.hip, edvr_ops_bf16.hip (include/sr_hip_edvr_bf16.h); 123 stays unnamed
+    static const char* hnames[6] = {"deform16_fwd_kernel", "pw16_conv_kernel",  "cb16_subsample2_kernel",
+                                    "pool16_s2_fwd_kernel", "tsa16_corr_kernel", "tsa16_gate_kernel"};
+    return hnames[id - 124];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -68,3 +68,42 @@ def paired_paths_from_lmdb(folders, keys):
     if names != set(lmdb_keys(gt_dir)):
         raise ValueError(f'Keys in {lq_key}_folder and {gt_key}_folder are different.')
     return [_pair(lq_key, gt_key, n, n) for n in sorted(names)]
+
+
+_FRAME_PADDINGS = ('replicate', 'reflection', 'reflection_circle', 'circle')
+
+
+def generate_frame_indices(crt_idx, max_frame_num, num_frames, padding='reflection'):
+    """The ``num_frames`` frame numbers (from 0) of the clip centred on frame ``crt_idx`` of a sequence of ``max_frame_num``
+    frames.  Where the window of ``num_frames // 2`` frames on either side reaches past an end of the sequence, ``padding``
+    says which frame stands in for a position ``d`` frames past that end (d = 1 is the first missing frame):
+
+        replicate          the end frame itself
+        reflection         the frame d inside the end, mirrored at the end frame
+        reflection_circle  the frame d beyond the window's other side, so the stand-ins continue the clip away from the end
+        circle             the position shifted by ``num_frames`` back into the sequence
+
+    With crt_idx = 0 and num_frames = 5 these give [0, 0, 0, 1, 2], [2, 1, 0, 1, 2], [4, 3, 0, 1, 2] and [3, 4, 0, 1, 2].
+    An even ``num_frames`` or an unknown mode is a ValueError."""
+    if num_frames % 2 != 1:
+        raise ValueError(f'generate_frame_indices: num_frames={num_frames} must be odd (a clip has a centre frame)')
+    if padding not in _FRAME_PADDINGS:
+        raise ValueError(f'generate_frame_indices: unknown padding {padding!r}; one of {", ".join(_FRAME_PADDINGS)}')
+    last, half = max_frame_num - 1, num_frames // 2
+    first_pos, last_pos = crt_idx - half, crt_idx + half
+    out = []
+    for pos in range(first_pos, last_pos + 1):
+        if 0 <= pos <= last:
+            out.append(pos)
+            continue
+        before = pos < 0
+        d = -pos if before else pos - last
+        if padding == 'replicate':
+            out.append(0 if before else last)
+        elif padding == 'reflection':
+            out.append(d if before else last - d)
+        elif padding == 'reflection_circle':
+            out.append(last_pos + d if before else first_pos - d)
+        else:
+            out.append(pos + num_frames if before else pos - num_frames)
+    return out

@@ -1092,3 +1092,172 @@ def tsa_gate_bwd(g, feat, attn):
     launch('sr_tsa_gate_bwd_f32', feat.device, g.ptr, g.img_stride, feat.ptr, feat.img_stride, attn.ptr, attn.img_stride, df.ptr,
            df.img_stride, da.ptr, da.img_stride, feat.n, feat.cbn, feat.h, feat.w)
     return df, da
+
+
+# ---- EDVR in bf16: deformable conv, 1x1 conv, subsample, pooling, correlation and gate on CB16 (include/sr_hip_edvr_bf16.h) ----
+
+def _launch_arg(name, dev, *args):
+    """``launch`` for the entry points of sr_hip_edvr_bf16.h: their SR_EINVAL is a ValueError, as the wrappers' own checks."""
+    try:
+        launch(name, dev, *args)
+    except _lib.SrHipError as e:
+        if '(status -1)' in str(e):
+            raise ValueError(str(e)) from None
+        raise
+
+
+def _bias_image(bias, cout, dev):
+    return None if bias is None else torch.empty(_lib.load().sr_conv3x3_packed_bias_floats(cout), dtype=torch.float32, device=dev)
+
+
+class PackedConv1x1BF16:
+    """bf16 MFMA weight image (+ fp32 bias) of one 1x1 conv over CB16 — sr_conv1x1_pack_bf16."""
+    mode, ksize = 0, 1
+
+    def __init__(self, weight, bias=None):
+        _need_cuda(weight, 'PackedConv1x1BF16')
+        weight = weight.detach().contiguous().float()
+        cout, cin = weight.shape[:2]
+        _arg(weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1), 'PackedConv1x1BF16: needs a [cout, cin, 1, 1] weight')
+        _arg(cin % 16 == 0, f'PackedConv1x1BF16: cin={cin} must be a multiple of 16 (CB16)')
+        self.cout, self.src_channels = cout, cin
+        dev = weight.device
+        self.w = torch.empty(_lib.load().sr_conv1x1_packed_weight_elems_bf16(cout, cin), dtype=torch.bfloat16, device=dev)
+        self.b = _bias_image(bias, cout, dev)
+        if bias is not None:
+            bias = bias.detach().contiguous().float()
+        _launch_arg('sr_conv1x1_pack_bf16', dev, weight.data_ptr(), bias.data_ptr() if bias is not None else None, cout, cin,
+                    self.w.data_ptr(), self.b.data_ptr() if self.b is not None else None)
+
+
+def packed_conv_bf16(conv):
+    """The bf16 forward image of a parameter container (3x3: PackedConvBF16, 1x1: PackedConv1x1BF16), cached per parameter
+    version under a bf16 key."""
+    w, b = conv.weight, conv.bias
+    if w.shape[2] == 3:
+        return cached_pack('bf16 image', w, b, lambda: PackedConvBF16(w, b))
+    return cached_pack('bf16 image 1x1', w, b, lambda: PackedConv1x1BF16(w, b))
+
+
+def conv1x1_bf16(src, pc, out=None, *, act_slope=1.0):
+    """out = bf16(lrelu(W x + bias)) for a 1x1 conv on CB16 — one sr_conv1x1_bf16 launch.  ``pc``: PackedConv1x1BF16."""
+    _arg(getattr(pc, 'ksize', 3) == 1 and pc.mode == 0, 'conv1x1_bf16: needs the forward image of a 1x1 weight')
+    _arg(src.channels == pc.src_channels, f'conv1x1_bf16: source has {src.channels} channels, the weight image {pc.src_channels}')
+    if out is None:
+        out = CB16.empty(src.n, pc.cout, src.h, src.w, src.device)
+    _arg((out.n, out.h, out.w) == (src.n, src.h, src.w) and out.channels >= (pc.cout + 15) // 16 * 16,
+         'conv1x1_bf16: output window does not fit')
+    _launch_arg('sr_conv1x1_bf16', src.device, src.ptr, src.img_stride, pc.w.data_ptr(), pc.b.data_ptr() if pc.b is not None else None,
+                out.ptr, out.img_stride, src.n, pc.src_channels, pc.cout, src.h, src.w, float(act_slope))
+    return out
+
+
+def _planes(t, channels, like, what):
+    """(pointer, image stride in floats) of an fp32 NCHW tensor or channel slice whose images are dense planes."""
+    _arg(t.dtype == torch.float32 and t.dim() == 4 and tuple(t.shape) == (like.n, channels, like.h, like.w)
+         and tuple(t.stride()[1:]) == (like.h * like.w, like.w, 1), f'{what}: needs dense fp32 planes [{like.n}, {channels}, {like.h}, {like.w}]')
+    return t.data_ptr(), t.stride(0) if like.n > 1 else max(t.stride(0), channels * like.h * like.w)
+
+
+def dcn_fwd_bf16(x, offset, mask, pc, dg, *, mask_is_logit=False, act_slope=1.0, out=None):
+    """Modulated deformable 3x3 conv on CB16 — one sr_dcn_fwd_bf16 launch.  ``x``: CB16 window of cin channels (cin / dg a
+    multiple of 8); ``offset`` / ``mask``: fp32 NCHW tensors (or channel slices of one) of 18 * dg / 9 * dg planes in the
+    reference's order; ``pc``: PackedConvBF16 (mode 0) of the 3x3 weight."""
+    _arg(pc.mode == 0 and getattr(pc, 'ksize', 3) == 3, 'dcn_fwd_bf16: needs the forward image of a 3x3 weight')
+    _arg(x.channels == pc.src_channels, f'dcn_fwd_bf16: source has {x.channels} channels, the weight image {pc.src_channels}')
+    _arg(dg > 0 and x.channels % dg == 0 and (x.channels // dg) % 8 == 0,
+         f'dcn_fwd_bf16: cin {x.channels} / deformable_groups {dg} must be a multiple of 8')
+    if out is None:
+        out = CB16.empty(x.n, pc.cout, x.h, x.w, x.device)
+    _arg((out.n, out.h, out.w) == (x.n, x.h, x.w) and out.channels >= (pc.cout + 15) // 16 * 16, 'dcn_fwd_bf16: output window does not fit')
+    d = _lib.DcnBf16Desc()
+    d.x, d.x_img_stride = x.ptr, x.img_stride
+    d.offset, d.offset_img_stride = _planes(offset, 18 * dg, x, 'dcn_fwd_bf16 offset')
+    d.mask, d.mask_img_stride = _planes(mask, 9 * dg, x, 'dcn_fwd_bf16 mask')
+    d.mask_is_logit = int(mask_is_logit)
+    d.wpacked, d.bpacked = pc.w.data_ptr(), pc.b.data_ptr() if pc.b is not None else None
+    d.out, d.out_img_stride = out.ptr, out.img_stride
+    d.n, d.cin, d.cout, d.h, d.w, d.deformable_groups = x.n, x.channels, pc.cout, x.h, x.w, dg
+    d.ksize, d.stride, d.padding, d.dilation, d.groups, d.act_slope = 3, 1, 1, 1, 1, float(act_slope)
+    _launch_arg('sr_dcn_fwd_bf16', x.device, C.byref(d))
+    return out
+
+
+def dcn_bf16_instance(cout, n, h, w):
+    """(COT, tile rows, dynamic LDS bytes) of the sr_dcn_fwd_bf16 launch for this shape — sr_dcn_bf16_lds_bytes."""
+    cot, rows = C.c_int(0), C.c_int(0)
+    lds = _lib.load().sr_dcn_bf16_lds_bytes(cout, n, h, w, C.byref(cot), C.byref(rows))
+    return cot.value, rows.value, lds
+
+
+def subsample2_bf16(src, out=None):
+    """The even rows and columns of a CB16 window: (H + 1) // 2 x (W + 1) // 2 — sr_cb16_subsample2_bf16."""
+    ho, wo = (src.h + 1) // 2, (src.w + 1) // 2
+    if out is None:
+        out = CB16.empty(src.n, src.channels, ho, wo, src.device)
+    _arg((out.n, out.cbn, out.h, out.w) == (src.n, src.cbn, ho, wo), 'subsample2_bf16: output window does not fit')
+    _launch_arg('sr_cb16_subsample2_bf16', src.device, src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, src.cbn, src.h, src.w)
+    return out
+
+
+def pool3x3s2_bf16(src, out=None):
+    """torch.cat([MaxPool2d(3, 2, 1)(x), AvgPool2d(3, 2, 1)(x)], 1) as one CB16 tensor of 2 * channels — one
+    sr_pool3x3s2_fwd_bf16 launch writing both windows.  ``out``: a CB16 window of 2 * src.cbn blocks."""
+    ho, wo = (src.h + 1) // 2, (src.w + 1) // 2
+    if out is None:
+        out = CB16.empty(src.n, 2 * src.channels, ho, wo, src.device)
+    _arg((out.n, out.cbn, out.h, out.w) == (src.n, 2 * src.cbn, ho, wo), 'pool3x3s2_bf16: output window does not fit')
+    mx, av = CB16(out.buf, out.cb0, src.cbn), CB16(out.buf, out.cb0 + src.cbn, src.cbn)
+    _launch_arg('sr_pool3x3s2_fwd_bf16', src.device, src.ptr, src.img_stride, mx.ptr, mx.img_stride, av.ptr, av.img_stride, src.n,
+                src.cbn, src.h, src.w)
+    return out
+
+
+def tsa_corr_bf16(emb, emb_ref, aligned, t, out=None, want_prob=False):
+    """TSA's temporal attention on CB16: aligned * sigmoid(sum_c emb * emb_ref) as CB16 [b * t, c] (and prob [b, t, h, w] fp32
+    with ``want_prob``) — one sr_tsa_corr_fwd_bf16 launch.  ``emb`` / ``aligned``: windows of b * t images, ``emb_ref``: of b."""
+    _arg(t >= 1 and emb.n == emb_ref.n * t, f'tsa_corr_bf16: {emb.n} frames are not {emb_ref.n} x {t}')
+    _arg(_same(emb, aligned) and (emb_ref.cbn, emb_ref.h, emb_ref.w) == (emb.cbn, emb.h, emb.w), 'tsa_corr_bf16: shapes differ')
+    if out is None:
+        out = CB16.empty(emb.n, emb.channels, emb.h, emb.w, emb.device)
+    _arg(_same(emb, out), 'tsa_corr_bf16: output window does not fit')
+    prob = torch.empty((emb_ref.n, t, emb.h, emb.w), dtype=torch.float32, device=emb.device) if want_prob else None
+    _launch_arg('sr_tsa_corr_fwd_bf16', emb.device, emb.ptr, emb.img_stride, emb_ref.ptr, emb_ref.img_stride, aligned.ptr,
+                aligned.img_stride, prob.data_ptr() if want_prob else None, out.ptr, out.img_stride, emb_ref.n, t, emb.channels,
+                emb.h, emb.w)
+    return (prob, out) if want_prob else out
+
+
+def tsa_gate_bf16(feat, attn, attn_add, out=None):
+    """out = bf16(feat * sigmoid(attn) * 2 + attn_add) on CB16 windows of equal shape — sr_tsa_gate_fwd_bf16."""
+    _arg(_same(feat, attn, attn_add), 'tsa_gate_bf16: shapes differ')
+    if out is None:
+        out = CB16.empty(feat.n, feat.channels, feat.h, feat.w, feat.device)
+    _arg(_same(feat, out), 'tsa_gate_bf16: output window does not fit')
+    _launch_arg('sr_tsa_gate_fwd_bf16', feat.device, feat.ptr, feat.img_stride, attn.ptr, attn.img_stride, attn_add.ptr,
+                attn_add.img_stride, out.ptr, out.img_stride, feat.n, feat.cbn, feat.h, feat.w)
+    return out
+
+
+def bilinear2x_bf16(src, skip=None):
+    """F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) of ``src`` (of bf16(src + skip) when given) on CB16 —
+    sr_bilinear2x_fwd_bf16."""
+    _arg(skip is None or _same(src, skip), 'bilinear2x_bf16: shapes differ')
+    out = CB16.empty(src.n, src.channels, 2 * src.h, 2 * src.w, src.device)
+    launch('sr_bilinear2x_fwd_bf16', src.device, src.ptr, src.img_stride, skip.ptr if skip is not None else None,
+           skip.img_stride if skip is not None else 0, out.ptr, out.img_stride, src.n, src.cbn, src.h, src.w)
+    return out
+
+
+def cb16_add(a, b):
+    """bf16(a + b) of two whole CB16 tensors of equal shape — sr_cb16_add_bf16."""
+    _arg(tuple(a.buf.shape) == tuple(b.buf.shape) and a.cbn == a.buf.size(1) and b.cbn == b.buf.size(1), 'cb16_add: shapes differ')
+    out = CB16(torch.empty_like(a.buf))
+    launch('sr_cb16_add_bf16', a.device, a.ptr, b.ptr, out.ptr, a.buf.numel())
+    return out
+
+
+def cb16_scale(t, a):
+    """t = bf16(a * t) in place on a CB16 window (exact for a power of two) — sr_cb16_axpby_bf16 with b = 0."""
+    launch('sr_cb16_axpby_bf16', t.device, t.ptr, t.img_stride, t.ptr, t.img_stride, float(a), 0.0, t.n, t.cbn, t.h, t.w)
+    return t
