@@ -2,7 +2,13 @@
 network.  Parameter names, shapes and defaults are the reference's, so its checkpoints load key for key; like the reference,
 only EDVR is registered in ARCH_REGISTRY.
 
-Between the entry ToCB8 and the exit FromCB8 every activation is CB8 and every layer is an autograd Function of hip_autograd:
+Every module states its layer list ONCE (``_layers(ops, ...)``; ``EDVR._run(x, ops)``) against a table of operations, and there
+are two tables: ``_CB8Ops`` (fp32, with gradients) and ``_CB16Ops`` (bf16, forward only).  A table says how a layer is launched
+and which neighbouring additions it fuses; which layers there are, their parameters, slopes and skips is said by the list alone.
+``forward_cb8`` / ``forward_cb16`` of a module are its list on the one table or the other.
+
+``_CB8Ops``: between the entry ToCB8 and the exit FromCB8 every activation is a raw CB8 tensor [n, cb, h, w, 8] and every layer is
+an autograd Function of hip_autograd:
 
     3x3 convs                       ConvFn (sr_conv3x3_f32), LeakyReLU / ReLU in the epilogue
     3x3 stride-2 convs              ConvS2Fn (sr_conv3x3s2_f32; backward on the zero-inserted gradient)
@@ -15,16 +21,16 @@ Between the entry ToCB8 and the exit FromCB8 every activation is CB8 and every l
     pixel shuffle                   PixelShuffleFn; the LeakyReLU after it runs in the upconv's epilogue (it commutes)
     bilinear x4 base                BilinearUpFn, added into the NCHW output in place
 
+``_CB16Ops`` (``EDVR(..., compute_dtype='bf16')``): hip_ops.CB16 windows between sr_nchw_to_cb16_bf16 and the last
+conv's fp32 NCHW store: sr_conv3x3_bf16 (the stride-2 convs followed by sr_cb16_subsample2_bf16; a skip addition after a conv runs
+in its epilogue), sr_dcn_fwd_bf16 on fp32 offset / mask planes (DCNv2Pack.forward_cb16), sr_conv1x1_bf16, sr_pool3x3s2_fwd_bf16,
+sr_tsa_corr_fwd_bf16, sr_tsa_gate_fwd_bf16, sr_bilinear2x_fwd_bf16, sr_cb16_pixel_shuffle_bf16; the x4 base is still
+sr_bilinear_up_f32 of the fp32 centre frame.
+
 The frames are a batch: PCD alignment runs ONCE on the b*t images with the centre frame's pyramid expanded over t (the
 reference calls it t times); every image is processed independently, so the result is the per-frame loop's bit for bit, and the
 expand's autograd sums the reference pyramid's gradients over t.  Channel concatenation, frame selection and the expand are
-tensor plumbing on the CB8 storage.
-
-``EDVR(..., compute_dtype='bf16')`` (forward only) runs the same layer list on hip_ops.CB16 windows between
-sr_nchw_to_cb16_bf16 and conv_last's fp32 NCHW store: sr_conv3x3_bf16 (the stride-2 convs followed by sr_cb16_subsample2_bf16),
-sr_dcn_fwd_bf16 on fp32 offset / mask planes, sr_conv1x1_bf16, sr_pool3x3s2_fwd_bf16, sr_tsa_corr_fwd_bf16, sr_tsa_gate_fwd_bf16,
-sr_bilinear2x_fwd_bf16, sr_cb16_pixel_shuffle_bf16; the x4 base is still sr_bilinear_up_f32 of the fp32 centre frame.  Each
-module's ``forward_cb16`` is its ``forward_cb8`` on those launches.
+tensor plumbing on the channel-blocked storage, written once for both tables (``_Ops``).
 """
 import torch
 from torch import nn
@@ -35,48 +41,116 @@ from ..utils.registry import ARCH_REGISTRY
 from .arch_util import Conv3x3Params, DCNv2Pack, ResidualBlockNoBN, make_layer
 
 
-def _conv(m, x, slope=0.1):
-    return A.ConvFn.apply(x, m.weight, m.bias, slope)
+class _Ops:
+    """What the two tables share: the frame plumbing, on the storage [n, cb, h, w, lanes] of a whole activation (``raw``; ``wrap``
+    makes an activation of a view of one, with a copy only where the table's layers need contiguous storage)."""
+
+    def dims(self, x):
+        return tuple(self.raw(x).shape[:4])
+
+    def _clips(self, x, b, t):
+        return self.raw(x).view(b, t, *self.raw(x).shape[1:])
+
+    def center(self, x, b, t, idx):
+        """Frame ``idx`` of every clip of a b * t batch: b images."""
+        return self.wrap(self._clips(x, b, t)[:, idx].contiguous())
+
+    def center_over_t(self, x, b, t, idx):
+        """The same frame expanded over t: b * t images (in fp32 the expand's autograd sums the gradients over t).  For b == 1
+        the result is still a view, stride 0 over t: no copy unless ``wrap`` makes one."""
+        v = self._clips(x, b, t)[:, idx:idx + 1]
+        return self.wrap(v.expand(b, t, *v.shape[2:]).reshape(self.raw(x).shape))
+
+    def frames_to_channels(self, x, b, t):
+        """(b * t, cb) read as (b, t * cb): a clip's frames concatenated by channel, the same memory."""
+        _, cb, *rest = self.raw(x).shape
+        return self.wrap(self.raw(x).view(b, t * cb, *rest))
 
 
-def _conv_s2(m, x, slope=0.1):
-    return A.ConvS2Fn.apply(x, m.weight, m.bias, slope)
+class _CB8Ops(_Ops):
+    """fp32: autograd Functions of hip_autograd on raw CB8 tensors [n, cb, h, w, 8]."""
+    raw = wrap = staticmethod(lambda x: x)
+    enter = A.ToCB8.apply
+    pool = A.Pool3x3s2Fn.apply
+    tsa_corr = A.TSACorrFn.apply        # its output already is (b, t*c)
+    tsa_gate = A.TSAGateFn.apply
+    pixel_shuffle = A.PixelShuffleFn.apply
+    dcn = staticmethod(DCNv2Pack.forward_cb8)
+
+    def conv(self, m, x, slope=0.1):
+        return A.ConvFn.apply(x, m.weight, m.bias, slope)
+
+    def conv_s2(self, m, x, slope=0.1):
+        return A.ConvS2Fn.apply(x, m.weight, m.bias, slope)
+
+    def conv1x1(self, m, x, slope=0.1):
+        return A.Conv1x1Fn.apply(x, m.weight, m.bias, slope)
+
+    def conv_add(self, m, x, other, slope=0.1):
+        return A.AddFn.apply(self.conv(m, x, slope), other)
+
+    def conv_nchw(self, m, x):
+        return A.FromCB8.apply(self.conv(m, x, 1.0), m.out_channels)
+
+    def resblock(self, m, x, extra=None):
+        """ResidualBlockNoBN: x + conv2(relu(conv1(x))) (+ ``extra``)."""
+        y = A.AddFn.apply(x, self.conv(m.conv2, self.conv(m.conv1, x, 0.0), 1.0))
+        return y if extra is None else A.AddFn.apply(y, extra)
+
+    def cat(self, *ts):
+        return torch.cat(ts, dim=1)
+
+    def up2(self, x, scale=1.0):
+        y = A.Bilinear2xFn.apply(x)
+        return y if scale == 1.0 else y * scale
 
 
-def _conv1x1(m, x, slope=0.1):
-    return A.Conv1x1Fn.apply(x, m.weight, m.bias, slope)
+class _CB16Ops(_Ops):
+    """bf16, forward only: hip_ops launches on whole hip_ops.CB16 windows; the weight images are hip_ops.packed_conv_bf16's."""
+    raw, wrap = staticmethod(lambda x: x.buf), staticmethod(lambda buf: H.CB16(buf.contiguous()))
+    enter = staticmethod(H.nchw_to_cb16)
+    pool = staticmethod(H.pool3x3s2_bf16)
+    tsa_gate = staticmethod(H.tsa_gate_bf16)
+    pixel_shuffle = staticmethod(H.pixel_shuffle_bf16)
+    dcn = staticmethod(DCNv2Pack.forward_cb16)
+
+    def conv(self, m, x, slope=0.1, **kw):
+        return H.conv3x3_bf16(x, H.packed_conv_bf16(m), act_slope=slope, **kw)
+
+    def conv_s2(self, m, x, slope=0.1):
+        """3x3 / stride 2 / pad 1: the stride-1 conv sampled at the even positions (4x the MACs of a native stride-2 kernel)."""
+        return H.subsample2_bf16(self.conv(m, x, slope))
+
+    def conv1x1(self, m, x, slope=0.1):
+        return H.conv1x1_bf16(x, H.packed_conv_bf16(m), act_slope=slope)
+
+    def conv_add(self, m, x, other, slope=0.1):
+        return self.conv(m, x, slope, res1=other, beta1=1.0)   # the addition in the conv's epilogue
+
+    def conv_nchw(self, m, x):
+        y = torch.empty((x.n, m.out_channels, x.h, x.w), dtype=torch.float32, device=x.device)
+        self.conv(m, x, 1.0, out_nchw=y)
+        return y
+
+    def resblock(self, m, x, extra=None):
+        """ResidualBlockNoBN (+ ``extra``): both additions in conv2's epilogue, one rounding."""
+        kw = dict(res2=extra, beta2=1.0) if extra is not None else {}
+        return self.conv(m.conv2, self.conv(m.conv1, x, 0.0), 1.0, res1=x, beta1=1.0, **kw)
+
+    def cat(self, *ts):
+        """torch.cat along the channel-block dimension of whole CB16 tensors."""
+        assert all(t.cb0 == 0 and t.cbn == t.buf.size(1) for t in ts)
+        return H.CB16(torch.cat([t.buf for t in ts], dim=1))
+
+    def up2(self, x, scale=1.0):
+        y = H.bilinear2x_bf16(x)
+        return y if scale == 1.0 else H.cb16_scale(y, scale)   # exact for a power of two
+
+    def tsa_corr(self, emb, emb_ref, aligned, t):
+        return self.frames_to_channels(H.tsa_corr_bf16(emb, emb_ref, aligned, t), emb_ref.n, t)
 
 
-def _resblock(m, x):
-    """ResidualBlockNoBN: x + conv2(relu(conv1(x)))."""
-    return A.AddFn.apply(x, _conv(m.conv2, _conv(m.conv1, x, 0.0), 1.0))
-
-
-# ---- the bf16 inference path: hip_ops.CB16 windows between sr_nchw_to_cb16_bf16 and conv_last's fp32 NCHW store ----
-
-def _conv16(m, x, slope=0.1, **kw):
-    return H.conv3x3_bf16(x, H.packed_conv_bf16(m), act_slope=slope, **kw)
-
-
-def _conv_s2_16(m, x, slope=0.1):
-    """3x3 / stride 2 / pad 1: the stride-1 conv sampled at the even positions (4x the MACs of a native stride-2 kernel)."""
-    return H.subsample2_bf16(_conv16(m, x, slope))
-
-
-def _conv1x1_16(m, x, slope=0.1):
-    return H.conv1x1_bf16(x, H.packed_conv_bf16(m), act_slope=slope)
-
-
-def _resblock16(m, x, extra=None):
-    """ResidualBlockNoBN (+ ``extra``): both additions in conv2's epilogue, one rounding."""
-    kw = dict(res2=extra, beta2=1.0) if extra is not None else {}
-    return _conv16(m.conv2, _conv16(m.conv1, x, 0.0), 1.0, res1=x, beta1=1.0, **kw)
-
-
-def _cat16(*ts):
-    """torch.cat along the channel-block dimension of whole CB16 tensors."""
-    assert all(t.cb0 == 0 and t.cbn == t.buf.size(1) for t in ts)
-    return H.CB16(torch.cat([t.buf for t in ts], dim=1))
+_FP32, _BF16 = _CB8Ops(), _CB16Ops()
 
 
 def _check_input(x, what, dims):
@@ -132,54 +206,36 @@ class PCDAlignment(nn.Module):
         self.cas_dcnpack = DCNv2Pack(num_feat, num_feat, 3, padding=1, deformable_groups=deformable_groups)
         self.num_feat = num_feat
 
-    _conv = staticmethod(_conv)
-
-    def forward_cb8(self, nbr, ref):
-        """The two pyramids as lists of CB8 tensors (L1, L2, L3) -> the aligned L1 features, CB8."""
-        conv = self._conv
+    def _layers(self, ops, nbr, ref):
+        conv, cat = ops.conv, ops.cat
         upsampled_offset, upsampled_feat = None, None
         for i in range(3, 0, -1):
             level = f'l{i}'
-            offset = conv(self.offset_conv1[level], torch.cat([nbr[i - 1], ref[i - 1]], dim=1))
+            offset = conv(self.offset_conv1[level], cat(nbr[i - 1], ref[i - 1]))
             if i == 3:
                 offset = conv(self.offset_conv2[level], offset)
             else:
-                offset = conv(self.offset_conv2[level], torch.cat([offset, upsampled_offset], dim=1))
+                offset = conv(self.offset_conv2[level], cat(offset, upsampled_offset))
                 offset = conv(self.offset_conv3[level], offset)
+            # LeakyReLU after the level-3 deformable conv; on the finer levels it follows feat_conv, and on level 2 only: the
+            # level-1 feat_conv output goes on without activation
+            feat = ops.dcn(self.dcn_pack[level], nbr[i - 1], offset, 0.1 if i == 3 else 1.0)
             if i < 3:
-                feat = self.dcn_pack[level].forward_cb8(nbr[i - 1], offset)
-                # LeakyReLU on level 2 only: the level-1 feat_conv output goes on without activation
-                feat = conv(self.feat_conv[level], torch.cat([feat, upsampled_feat], dim=1), 0.1 if i > 1 else 1.0)
-            else:
-                feat = self.dcn_pack[level].forward_cb8(nbr[i - 1], offset, 0.1)
+                feat = conv(self.feat_conv[level], cat(feat, upsampled_feat), 0.1 if i > 1 else 1.0)
             if i > 1:  # hand offsets and features to the next finer level; offsets count pixels, so they double as well
-                upsampled_offset = A.Bilinear2xFn.apply(offset) * 2
-                upsampled_feat = A.Bilinear2xFn.apply(feat)
+                upsampled_offset = ops.up2(offset, 2.0)
+                upsampled_feat = ops.up2(feat)
         # the last deformable conv, its offsets from the aligned features and the centre frame
-        offset = conv(self.cas_offset_conv2, conv(self.cas_offset_conv1, torch.cat([feat, ref[0]], dim=1)))
-        return self.cas_dcnpack.forward_cb8(feat, offset, 0.1)
+        offset = conv(self.cas_offset_conv2, conv(self.cas_offset_conv1, cat(feat, ref[0])))
+        return ops.dcn(self.cas_dcnpack, feat, offset, 0.1)
+
+    def forward_cb8(self, nbr, ref):
+        """The two pyramids as lists of CB8 tensors (L1, L2, L3) -> the aligned L1 features, CB8."""
+        return self._layers(_FP32, nbr, ref)
 
     def forward_cb16(self, nbr, ref):
-        """forward_cb8's layer list on hip_ops.CB16 windows (bf16 inference): the pyramids as lists of CB16 -> aligned L1, CB16."""
-        upsampled_offset, upsampled_feat = None, None
-        for i in range(3, 0, -1):
-            level = f'l{i}'
-            offset = _conv16(self.offset_conv1[level], _cat16(nbr[i - 1], ref[i - 1]))
-            if i == 3:
-                offset = _conv16(self.offset_conv2[level], offset)
-            else:
-                offset = _conv16(self.offset_conv2[level], _cat16(offset, upsampled_offset))
-                offset = _conv16(self.offset_conv3[level], offset)
-            if i < 3:
-                feat = self.dcn_pack[level].forward_cb16(nbr[i - 1], offset)
-                feat = _conv16(self.feat_conv[level], _cat16(feat, upsampled_feat), 0.1 if i > 1 else 1.0)
-            else:
-                feat = self.dcn_pack[level].forward_cb16(nbr[i - 1], offset, 0.1)
-            if i > 1:
-                upsampled_offset = H.cb16_scale(H.bilinear2x_bf16(offset), 2.0)   # exact: a power of two
-                upsampled_feat = H.bilinear2x_bf16(feat)
-        offset = _conv16(self.cas_offset_conv2, _conv16(self.cas_offset_conv1, _cat16(feat, ref[0])))
-        return self.cas_dcnpack.forward_cb16(feat, offset, 0.1)
+        """The same on hip_ops.CB16 windows (bf16 inference): the pyramids as lists of CB16 -> aligned L1, CB16."""
+        return self._layers(_BF16, nbr, ref)
 
     def forward(self, nbr_feat_l, ref_feat_l):
         for t in list(nbr_feat_l) + list(ref_feat_l):
@@ -229,55 +285,39 @@ class TSAFusion(nn.Module):
         self.spatial_attn_add1 = Conv3x3Params(num_feat, num_feat, ksize=1)
         self.spatial_attn_add2 = Conv3x3Params(num_feat, num_feat, ksize=1)
 
-    def forward_cb8(self, aligned, b, t):
-        bt, cb, h, w, _ = aligned.shape
+    def _layers(self, ops, aligned, b, t):
+        conv, conv1x1 = ops.conv, ops.conv1x1
+        bt, _, h, w = ops.dims(aligned)
         if bt != b * t or t != self.num_frame:
             raise ValueError(f'TSAFusion: {bt} images are not {b} x num_frame={self.num_frame}')
         if h % 4 or w % 4:
             raise ValueError(f'TSAFusion: the height and width must be multiples of 4 (got {h}x{w})')
         # per-frame weights from the correlation with the centre frame
-        center = aligned.view(b, t, cb, h, w, 8)[:, self.center_frame_idx].contiguous()
-        embedding_ref = _conv(self.temporal_attn1, center, 1.0)
-        embedding = _conv(self.temporal_attn2, aligned, 1.0)
-        fused = A.TSACorrFn.apply(embedding, embedding_ref, aligned, t)   # (b, t*c): aligned * sigmoid(correlation)
-        feat = _conv1x1(self.feat_fusion, fused)
+        center = ops.center(aligned, b, t, self.center_frame_idx)
+        embedding_ref = conv(self.temporal_attn1, center, 1.0)
+        embedding = conv(self.temporal_attn2, aligned, 1.0)
+        fused = ops.tsa_corr(embedding, embedding_ref, aligned, t)   # (b, t*c): aligned * sigmoid(correlation)
+        feat = conv1x1(self.feat_fusion, fused)
         # attention branch, half resolution
-        attn = _conv1x1(self.spatial_attn1, fused)
-        attn = _conv1x1(self.spatial_attn2, A.Pool3x3s2Fn.apply(attn))
+        attn = conv1x1(self.spatial_attn1, fused)
+        attn = conv1x1(self.spatial_attn2, ops.pool(attn))
         # quarter resolution and back
-        attn_level = _conv1x1(self.spatial_attn_l1, attn)
-        attn_level = _conv(self.spatial_attn_l2, A.Pool3x3s2Fn.apply(attn_level))
-        attn_level = A.Bilinear2xFn.apply(_conv(self.spatial_attn_l3, attn_level))
-        attn = A.AddFn.apply(_conv(self.spatial_attn3, attn), attn_level)
-        attn = A.Bilinear2xFn.apply(_conv1x1(self.spatial_attn4, attn))
-        attn = _conv(self.spatial_attn5, attn, 1.0)
-        attn_add = _conv1x1(self.spatial_attn_add2, _conv1x1(self.spatial_attn_add1, attn), 1.0)
+        attn_level = conv1x1(self.spatial_attn_l1, attn)
+        attn_level = conv(self.spatial_attn_l2, ops.pool(attn_level))
+        attn_level = ops.up2(conv(self.spatial_attn_l3, attn_level))
+        attn = ops.conv_add(self.spatial_attn3, attn, attn_level)
+        attn = ops.up2(conv1x1(self.spatial_attn4, attn))
+        attn = conv(self.spatial_attn5, attn, 1.0)
+        attn_add = conv1x1(self.spatial_attn_add2, conv1x1(self.spatial_attn_add1, attn), 1.0)
         # sigmoid(attn) * 2 is about 1 for a freshly initialised branch (attn near 0), so the gate starts as the identity
-        return A.TSAGateFn.apply(feat, attn, attn_add)
+        return ops.tsa_gate(feat, attn, attn_add)
+
+    def forward_cb8(self, aligned, b, t):
+        return self._layers(_FP32, aligned, b, t)
 
     def forward_cb16(self, aligned, b, t):
-        """forward_cb8's layer list on hip_ops.CB16 windows (bf16 inference); ``aligned``: a whole CB16 tensor of b * t images."""
-        bt, cb, h, w = aligned.n, aligned.cbn, aligned.h, aligned.w
-        if bt != b * t or t != self.num_frame:
-            raise ValueError(f'TSAFusion: {bt} images are not {b} x num_frame={self.num_frame}')
-        if h % 4 or w % 4:
-            raise ValueError(f'TSAFusion: the height and width must be multiples of 4 (got {h}x{w})')
-        center = H.CB16(aligned.buf.view(b, t, cb, h, w, 16)[:, self.center_frame_idx].contiguous())
-        embedding_ref = _conv16(self.temporal_attn1, center, 1.0)
-        embedding = _conv16(self.temporal_attn2, aligned, 1.0)
-        fused = H.tsa_corr_bf16(embedding, embedding_ref, aligned, t)
-        fused = H.CB16(fused.buf.view(b, t * cb, h, w, 16))                 # (b, t*c): what the fusion convs read
-        feat = _conv1x1_16(self.feat_fusion, fused)
-        attn = _conv1x1_16(self.spatial_attn1, fused)
-        attn = _conv1x1_16(self.spatial_attn2, H.pool3x3s2_bf16(attn))
-        attn_level = _conv1x1_16(self.spatial_attn_l1, attn)
-        attn_level = _conv16(self.spatial_attn_l2, H.pool3x3s2_bf16(attn_level))
-        attn_level = H.bilinear2x_bf16(_conv16(self.spatial_attn_l3, attn_level))
-        attn = _conv16(self.spatial_attn3, attn, res1=attn_level, beta1=1.0)   # the addition in the conv's epilogue
-        attn = H.bilinear2x_bf16(_conv1x1_16(self.spatial_attn4, attn))
-        attn = _conv16(self.spatial_attn5, attn, 1.0)
-        attn_add = _conv1x1_16(self.spatial_attn_add2, _conv1x1_16(self.spatial_attn_add1, attn), 1.0)
-        return H.tsa_gate_bf16(feat, attn, attn_add)
+        """The same on hip_ops.CB16 windows (bf16 inference); ``aligned``: a whole CB16 tensor of b * t images."""
+        return self._layers(_BF16, aligned, b, t)
 
     def forward(self, aligned_feat):
         _check_input(aligned_feat, 'TSAFusion', 5)
@@ -327,46 +367,32 @@ class PredeblurModule(nn.Module):
         if h % m or w % m:
             raise ValueError(f'PredeblurModule: the height and width must be multiples of {m} (got {h}x{w})')
 
-    def forward_cb8(self, x):
-        self._check_size(x.size(2), x.size(3))
-        feat_l1 = _conv(self.conv_first, x)
+    def _layers(self, ops, x):
+        conv_s2, resblock = ops.conv_s2, ops.resblock
+        self._check_size(*ops.dims(x)[2:])
+        feat_l1 = ops.conv(self.conv_first, x)
         if self.hr_in:
-            feat_l1 = _conv_s2(self.stride_conv_hr1, feat_l1)
-            feat_l1 = _conv_s2(self.stride_conv_hr2, feat_l1)
-        feat_l2 = _conv_s2(self.stride_conv_l2, feat_l1)
-        feat_l3 = _conv_s2(self.stride_conv_l3, feat_l2)
+            feat_l1 = conv_s2(self.stride_conv_hr1, feat_l1)
+            feat_l1 = conv_s2(self.stride_conv_hr2, feat_l1)
+        feat_l2 = conv_s2(self.stride_conv_l2, feat_l1)
+        feat_l3 = conv_s2(self.stride_conv_l3, feat_l2)
 
-        feat_l3 = A.Bilinear2xFn.apply(_resblock(self.resblock_l3, feat_l3))
-        feat_l2 = A.AddFn.apply(_resblock(self.resblock_l2_1, feat_l2), feat_l3)
-        feat_l2 = A.Bilinear2xFn.apply(_resblock(self.resblock_l2_2, feat_l2))
+        # each coarser level is upsampled and added to the next finer one after that level's first block(s)
+        feat_l3 = ops.up2(resblock(self.resblock_l3, feat_l3))
+        feat_l2 = resblock(self.resblock_l2_1, feat_l2, feat_l3)
+        feat_l2 = ops.up2(resblock(self.resblock_l2_2, feat_l2))
 
-        for i in range(2):
-            feat_l1 = _resblock(self.resblock_l1[i], feat_l1)
-        feat_l1 = A.AddFn.apply(feat_l1, feat_l2)
-        for i in range(2, 5):
-            feat_l1 = _resblock(self.resblock_l1[i], feat_l1)
+        for i, blk in enumerate(self.resblock_l1):
+            feat_l1 = resblock(blk, feat_l1, feat_l2 if i == 1 else None)
         return feat_l1
+
+    def forward_cb8(self, x):
+        return self._layers(_FP32, x)
 
     def forward_cb16(self, x):
-        """forward_cb8's layer list on hip_ops.CB16 windows (bf16 inference); the two additions run in the epilogue of the
-        preceding residual block's second conv."""
-        self._check_size(x.h, x.w)
-        feat_l1 = _conv16(self.conv_first, x)
-        if self.hr_in:
-            feat_l1 = _conv_s2_16(self.stride_conv_hr1, feat_l1)
-            feat_l1 = _conv_s2_16(self.stride_conv_hr2, feat_l1)
-        feat_l2 = _conv_s2_16(self.stride_conv_l2, feat_l1)
-        feat_l3 = _conv_s2_16(self.stride_conv_l3, feat_l2)
-
-        feat_l3 = H.bilinear2x_bf16(_resblock16(self.resblock_l3, feat_l3))
-        feat_l2 = _resblock16(self.resblock_l2_1, feat_l2, feat_l3)
-        feat_l2 = H.bilinear2x_bf16(_resblock16(self.resblock_l2_2, feat_l2))
-
-        feat_l1 = _resblock16(self.resblock_l1[0], feat_l1)
-        feat_l1 = _resblock16(self.resblock_l1[1], feat_l1, feat_l2)
-        for i in range(2, 5):
-            feat_l1 = _resblock16(self.resblock_l1[i], feat_l1)
-        return feat_l1
+        """The same on hip_ops.CB16 windows (bf16 inference); the two additions run in the epilogue of the preceding residual
+        block's second conv."""
+        return self._layers(_BF16, x)
 
     def forward(self, x):
         _check_input(x, 'PredeblurModule', 4)
@@ -466,53 +492,49 @@ class EDVR(nn.Module):
         self.conv_hr = Conv3x3Params(64, 64)
         self.conv_last = Conv3x3Params(64, 3)
 
+    def _align(self, ops, feat_l, b, t):
+        ref_l = [ops.center_over_t(f, b, t, self.center_frame_idx) for f in feat_l]
+        return self.pcd_align._layers(ops, feat_l, ref_l)
+
     def align_cb8(self, feat_l, b, t):
         """PCD alignment of every frame to the centre frame in one batched call: ``feat_l`` = the pyramid (L1, L2, L3) of the
         b * t frames, CB8; the centre frame's pyramid is expanded over t."""
-        ref_l = []
-        for f in feat_l:
-            _, cb, h, w, _ = f.shape
-            c = f.view(b, t, cb, h, w, 8)[:, self.center_frame_idx:self.center_frame_idx + 1]
-            ref_l.append(c.expand(b, t, cb, h, w, 8).reshape(b * t, cb, h, w, 8))
-        return self.pcd_align.forward_cb8(feat_l, ref_l)
+        return self._align(_FP32, feat_l, b, t)
 
-    def forward_bf16(self, x):
-        """The layer list of ``forward`` on CB16 bf16 activations; fp32 NCHW in and out."""
+    def _run(self, x, ops):
+        """The layer list; fp32 NCHW in and out, ``ops`` activations in between."""
+        conv, resblock = ops.conv, ops.resblock
         b, t, c, h, w = x.shape
-        ci = self.center_frame_idx
-        x_center = x[:, ci].contiguous()
-        frames = H.nchw_to_cb16(x.reshape(b * t, c, h, w))
-        if self.with_predeblur:
-            feat_l1 = _conv1x1_16(self.conv_1x1, self.predeblur.forward_cb16(frames), 1.0)
-        else:
-            feat_l1 = _conv16(self.conv_first, frames)
-        for blk in self.feature_extraction:
-            feat_l1 = _resblock16(blk, feat_l1)
-        feat_l2 = _conv16(self.conv_l2_2, _conv_s2_16(self.conv_l2_1, feat_l1))
-        feat_l3 = _conv16(self.conv_l3_2, _conv_s2_16(self.conv_l3_1, feat_l2))
+        x_center = x[:, self.center_frame_idx].contiguous()
+        frames = ops.enter(x.reshape(b * t, c, h, w))
 
-        feat_l = [feat_l1, feat_l2, feat_l3]
-        ref_l = []
-        for f in feat_l:   # the centre frame's pyramid expanded over t
-            v = f.buf.view(b, t, f.cbn, f.h, f.w, 16)[:, ci:ci + 1]
-            ref_l.append(H.CB16(v.expand(b, t, f.cbn, f.h, f.w, 16).reshape(b * t, f.cbn, f.h, f.w, 16).contiguous()))
-        aligned = self.pcd_align.forward_cb16(feat_l, ref_l)
+        # level-1 features of every frame
+        if self.with_predeblur:
+            feat_l1 = ops.conv1x1(self.conv_1x1, self.predeblur._layers(ops, frames), 1.0)
+        else:
+            feat_l1 = conv(self.conv_first, frames)
+        for blk in self.feature_extraction:
+            feat_l1 = resblock(blk, feat_l1)
+        feat_l2 = conv(self.conv_l2_2, ops.conv_s2(self.conv_l2_1, feat_l1))
+        feat_l3 = conv(self.conv_l3_2, ops.conv_s2(self.conv_l3_1, feat_l2))
+
+        # PCD alignment, all frames at once
+        aligned = self._align(ops, [feat_l1, feat_l2, feat_l3], b, t)
 
         if self.with_tsa:
-            out = self.fusion.forward_cb16(aligned, b, t)
+            out = self.fusion._layers(ops, aligned, b, t)
         else:
-            fused = H.CB16(aligned.buf.view(b, t * aligned.cbn, aligned.h, aligned.w, 16))
-            out = _conv1x1_16(self.fusion, fused, 1.0)
+            out = ops.conv1x1(self.fusion, ops.frames_to_channels(aligned, b, t), 1.0)
         for blk in self.reconstruction:
-            out = _resblock16(blk, out)
-        out = H.pixel_shuffle_bf16(_conv16(self.upconv1, out), self.num_feat, 2)
-        out = H.pixel_shuffle_bf16(_conv16(self.upconv2, out), 64, 2)
-        out = _conv16(self.conv_hr, out)
-        y = torch.empty((b, 3, out.h, out.w), dtype=torch.float32, device=x.device)
-        _conv16(self.conv_last, out, 1.0, out_nchw=y)
+            out = resblock(blk, out)
+        # the LeakyReLU after each pixel shuffle commutes with it: it runs in the upconv's epilogue
+        out = ops.pixel_shuffle(conv(self.upconv1, out), self.num_feat, 2)
+        out = ops.pixel_shuffle(conv(self.upconv2, out), 64, 2)
+        out = conv(self.conv_hr, out)
+        out = ops.conv_nchw(self.conv_last, out)
         if self.hr_in:
-            return A.AddFn.apply(y, x_center)
-        return H.bilinear_up(x_center, 4, out=y)
+            return A.AddFn.apply(out, x_center)
+        return A.BilinearUpFn.apply(x_center, 4, out)
 
     def forward(self, x):
         _check_input(x, 'EDVR', 5)
@@ -529,38 +551,5 @@ class EDVR(nn.Module):
                 raise NotImplementedError("EDVR with compute_dtype='bf16' is forward only (eval mode or torch.no_grad()); train "
                                           "with compute_dtype='fp32'")
             with torch.no_grad():
-                return self.forward_bf16(x)
-
-        x_center = x[:, self.center_frame_idx].contiguous()
-        frames = A.ToCB8.apply(x.reshape(b * t, c, h, w))
-
-        # level-1 features of every frame
-        if self.with_predeblur:
-            feat_l1 = _conv1x1(self.conv_1x1, self.predeblur.forward_cb8(frames), 1.0)
-        else:
-            feat_l1 = _conv(self.conv_first, frames)
-        for blk in self.feature_extraction:
-            feat_l1 = _resblock(blk, feat_l1)
-        feat_l2 = _conv(self.conv_l2_2, _conv_s2(self.conv_l2_1, feat_l1))
-        feat_l3 = _conv(self.conv_l3_2, _conv_s2(self.conv_l3_1, feat_l2))
-
-        # PCD alignment, all frames at once
-        aligned = self.align_cb8([feat_l1, feat_l2, feat_l3], b, t)
-
-        if self.with_tsa:
-            feat = self.fusion.forward_cb8(aligned, b, t)
-        else:
-            bt, cb, fh, fw, _ = aligned.shape
-            feat = _conv1x1(self.fusion, aligned.view(b, t * cb, fh, fw, 8), 1.0)
-
-        out = feat
-        for blk in self.reconstruction:
-            out = _resblock(blk, out)
-        # the LeakyReLU after each pixel shuffle commutes with it: it runs in the upconv's epilogue
-        out = A.PixelShuffleFn.apply(_conv(self.upconv1, out), self.num_feat, 2)
-        out = A.PixelShuffleFn.apply(_conv(self.upconv2, out), 64, 2)
-        out = _conv(self.conv_hr, out)
-        out = A.FromCB8.apply(_conv(self.conv_last, out, 1.0), 3)
-        if self.hr_in:
-            return A.AddFn.apply(out, x_center)
-        return A.BilinearUpFn.apply(x_center, 4, out)
+                return self._run(x, _BF16)
+        return self._run(x, _FP32)

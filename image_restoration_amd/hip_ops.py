@@ -1249,14 +1249,6 @@ def bilinear2x_bf16(src, skip=None):
     return out
 
 
-def cb16_add(a, b):
-    """bf16(a + b) of two whole CB16 tensors of equal shape — sr_cb16_add_bf16."""
-    _arg(tuple(a.buf.shape) == tuple(b.buf.shape) and a.cbn == a.buf.size(1) and b.cbn == b.buf.size(1), 'cb16_add: shapes differ')
-    out = CB16(torch.empty_like(a.buf))
-    launch('sr_cb16_add_bf16', a.device, a.ptr, b.ptr, out.ptr, a.buf.numel())
-    return out
-
-
 def cb16_scale(t, a):
     """t = bf16(a * t) in place on a CB16 window (exact for a power of two) — sr_cb16_axpby_bf16 with b = 0."""
     launch('sr_cb16_axpby_bf16', t.device, t.ptr, t.img_stride, t.ptr, t.img_stride, float(a), 0.0, t.n, t.cbn, t.h, t.w)

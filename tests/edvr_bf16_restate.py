@@ -1,4 +1,4 @@
-"""A float64 model of EDVR's bf16 inference forward (EDVR.forward_bf16): tests/edvr_restate.py and tests/dcn_restate.py with a
+"""A float64 model of EDVR's bf16 inference forward (EDVR in bf16): tests/edvr_restate.py and tests/dcn_restate.py with a
 bf16 round trip wherever the HIP path stores or rounds a tensor, and nowhere else.
 
 Rounded (``rt``): the converted frames; every conv, deformable-conv and 1x1 output after its epilogue (bias, activation and the
