@@ -1,5 +1,6 @@
 """ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h,
-include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h, include/sr_hip_dcn.h and include/sr_hip_edvr.h).
+include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h, include/sr_hip_dcn.h, include/sr_hip_edvr.h, include/sr_hip_edvr_bf16.h and
+include/sr_hip_stylegan2.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -451,6 +452,15 @@ EDVR_BF16_SIGNATURES = {
     'sr_tsa_gate_fwd_bf16': (C.c_int, [_P, _S, _P, _S, _P, _S, _P, _S, _I, _I, _I, _I, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/sr_hip_stylegan2.h declares
+STYLEGAN2_SIGNATURES = {
+    'sr_upfirdn2d_f32': (C.c_int, [_P, _S, _P, _S, _P] + [_I] * 15 + [_P]),
+    'sr_upfirdn2d_instance': (C.c_int, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    'sr_fused_bias_act_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _S, C.c_float, C.c_float, _P]),
+    'sr_fused_bias_act_workspace_bytes': (C.c_size_t, [_I, _I, _S]),
+    'sr_fused_bias_act_bwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _S, C.c_float, C.c_float, _P, C.c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -465,7 +475,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
-            + list(EDVR_BF16_SIGNATURES.items()):
+            + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1052,5 +1052,11 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "pool16_s2_fwd_kernel", "tsa16_corr_kernel", "tsa16_gate_kernel"};
     return hnames[id - 124];
   }
+  if (id >= 131 && id < 138) {  // stylegan2_ops.hip (include/sr_hip_stylegan2.h); 130 stays unnamed
+    static const char* snames[7] = {"upfirdn2d_kernelILi0ELi0ELi0EE", "upfirdn2d_kernelILi1ELi1ELi4EE", "upfirdn2d_kernelILi2ELi1ELi4EE",
+                                    "upfirdn2d_kernelILi1ELi2ELi4EE", "fused_bias_act_kernel<*,false>", "fused_bias_act_kernel<*,true>",
+                                    "fused_bias_act_finish_kernel"};
+    return snames[id - 131];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -1253,3 +1253,82 @@ def cb16_scale(t, a):
     """t = bf16(a * t) in place on a CB16 window (exact for a power of two) — sr_cb16_axpby_bf16 with b = 0."""
     launch('sr_cb16_axpby_bf16', t.device, t.ptr, t.img_stride, t.ptr, t.img_stride, float(a), 0.0, t.n, t.cbn, t.h, t.w)
     return t
+
+
+# ---- StyleGAN2 building blocks: upfirdn2d and the fused bias + LeakyReLU on NCHW tensors (include/sr_hip_stylegan2.h) ----
+
+def upfirdn2d_instance(kh, kw, up_x, up_y, down_x, down_y):
+    """(instance, tile rows, LDS bytes) of an sr_upfirdn2d_f32 call with this filter size and these factors
+    (sr_upfirdn2d_instance): 0 generic, 1 / 2 / 3 the 4x4 filter at (up, down) = (1, 1) / (2, 1) / (1, 2); tiles are 64 columns
+    wide.  ValueError when the filter or the factors are not supported."""
+    th, lds = C.c_int(0), C.c_size_t(0)
+    inst = _lib.load().sr_upfirdn2d_instance(kh, kw, up_x, up_y, down_x, down_y, C.byref(th), C.byref(lds))
+    _arg(inst >= 0, f'upfirdn2d: filter {kh}x{kw}, up ({up_x}, {up_y}), down ({down_x}, {down_y}) is not supported; supported: '
+                    'fp32, filter sides 1..16, factors 1..8')
+    return inst, th.value, lds.value
+
+
+def upfirdn2d_out_size(in_h, in_w, kh, kw, up, down, pad):
+    """(out_h, out_w) of upfirdn2d: (in * up + pad0 + pad1 - k) // down + 1 per axis; up, down = (x, y), pad = (x0, x1, y0, y1)."""
+    return ((in_h * up[1] + pad[2] + pad[3] - kh) // down[1] + 1, (in_w * up[0] + pad[0] + pad[1] - kw) // down[0] + 1)
+
+
+def upfirdn2d(x, kernel, up, down, pad, out=None):
+    """Up-sample by ``up`` = (x, y), pad by ``pad`` = (x0, x1, y0, y1), convolve with the [kh, kw] ``kernel``, keep every
+    ``down``-th sample, on every plane of the contiguous fp32 NCHW tensor ``x`` — one sr_upfirdn2d_f32 launch."""
+    _need_cuda(x, 'upfirdn2d')
+    _arg(x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32, 'upfirdn2d: needs a contiguous fp32 NCHW tensor')
+    _arg(kernel.dim() == 2 and kernel.is_contiguous() and kernel.dtype == torch.float32 and kernel.device == x.device,
+         'upfirdn2d: needs a contiguous fp32 [kh, kw] kernel on the device of the input')
+    n, c, h, w = x.shape
+    kh, kw = kernel.shape
+    upfirdn2d_instance(kh, kw, up[0], up[1], down[0], down[1])
+    oh, ow = upfirdn2d_out_size(h, w, kh, kw, up, down, pad)
+    _arg(oh > 0 and ow > 0, f'upfirdn2d: output size {oh}x{ow} is not positive (input {h}x{w}, kernel {kh}x{kw}, up {tuple(up)}, '
+                            f'down {tuple(down)}, pad {tuple(pad)})')
+    if out is None:
+        out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
+    _arg(tuple(out.shape) == (n, c, oh, ow) and out.is_contiguous() and out.dtype == torch.float32, 'upfirdn2d: output does not fit')
+    if n * c:
+        _launch_arg('sr_upfirdn2d_f32', x.device, x.data_ptr(), c * h * w, out.data_ptr(), c * oh * ow, kernel.data_ptr(), n, c, h, w, 1,
+                    kh, kw, up[0], up[1], down[0], down[1], *pad)
+    return out
+
+
+def _act_shape(x, what):
+    _need_cuda(x, what)
+    _arg(x.dim() >= 2 and x.is_contiguous() and x.dtype == torch.float32, f'{what}: needs a contiguous fp32 tensor of rank >= 2')
+    inner = 1
+    for s in x.shape[2:]:
+        inner *= s
+    return x.size(0), x.size(1), inner
+
+
+def fused_bias_act(x, bias=None, ref=None, slope=0.2, scale=2 ** 0.5):
+    """lrelu(x + bias[c], slope) * scale with the channel on dimension 1; the sign comes from ``ref`` where one is given — one
+    sr_fused_bias_act_f32 launch."""
+    n, c, inner = _act_shape(x, 'fused_bias_act')
+    _arg(bias is None or (bias.dim() == 1 and bias.numel() == c and bias.is_contiguous() and bias.dtype == torch.float32),
+         f'fused_bias_act: needs a contiguous fp32 bias of {c} values')
+    _arg(ref is None or (ref.shape == x.shape and ref.is_contiguous() and ref.dtype == torch.float32), 'fused_bias_act: ref does not fit')
+    out = torch.empty_like(x)
+    if x.numel():
+        _launch_arg('sr_fused_bias_act_f32', x.device, x.data_ptr(), None if bias is None else bias.data_ptr(),
+                    None if ref is None else ref.data_ptr(), out.data_ptr(), n, c, inner, float(slope), float(scale))
+    return out
+
+
+def fused_bias_act_bwd(g, out, slope=0.2, scale=2 ** 0.5, want_bias=True):
+    """(gx, gbias) of fused_bias_act from the gradient ``g`` of its output ``out``: gx = lrelu_by(out)(g) * scale, gbias[c] its sum
+    over every other dimension, from the same pass — sr_fused_bias_act_bwd_f32."""
+    n, c, inner = _act_shape(g, 'fused_bias_act_bwd')
+    _arg(out.shape == g.shape and out.is_contiguous() and out.dtype == torch.float32, 'fused_bias_act_bwd: out does not fit')
+    gx = torch.empty_like(g)
+    gbias = torch.zeros(c, dtype=torch.float32, device=g.device) if want_bias else None
+    if g.numel():
+        nbytes = _lib.load().sr_fused_bias_act_workspace_bytes(n, c, inner) if want_bias else 0
+        ws = scratch(g.device, nbytes, 'act') if want_bias else None
+        _launch_arg('sr_fused_bias_act_bwd_f32', g.device, g.data_ptr(), out.data_ptr(), gx.data_ptr(),
+                    gbias.data_ptr() if want_bias else None, n, c, inner, float(slope), float(scale),
+                    ws.data_ptr() if want_bias else None, nbytes)
+    return gx, gbias
