@@ -51,6 +51,7 @@ from image_restoration_amd import hip_ops as H
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dcn_restate as R  # noqa: E402
+from bf16_opwise import check, hulp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -58,12 +59,6 @@ EPS = 2.0 ** -24
 K_EPI, K_SAMPLE, K_SIGMOID = 2, 8, 4
 NAN16 = 0x7FC1
 D = torch.float64
-
-
-def hulp(v):
-    """Half a bf16 ulp of |v| (0 at 0)."""
-    v = v.abs().clamp_min(2.0 ** -126)
-    return torch.exp2(torch.floor(torch.log2(v)) - 8)
 
 
 def bf(t):
@@ -105,14 +100,6 @@ def slack_kept(win, what):
 
 def bits(win):
     return win.buf.cpu().view(torch.int16).clone()
-
-
-def check(got, want, bound, what):
-    err = (got - want).abs()
-    ratio = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
-    print(f'{what}: max err {float(err.max()):.3e}, largest err / bound {ratio:.3f}')
-    assert bool((err <= bound).all()), f'{what}: err / bound = {ratio:.3f}'
-    return ratio
 
 
 # ------------------------------------------------------------------------------------------------------ deformable conv

@@ -108,6 +108,8 @@ PINNED = {
     'sr_vgg_forward_f32': 'tests/test_training_gpu.py::test_vgg_gradient_quality_vs_float64',
     'sr_vgg_backward_f32': 'tests/test_training_gpu.py::test_vgg_gradient_quality_vs_float64',
     'sr_vgg_apply_stats_f32': 'tests/test_vgg_driver_gpu.py::test_driver_is_bit_identical_to_the_per_layer_route',
+    # the bf16 whole-network drivers: bit identity to the per-layer route is what these rows pin; the per-layer route's ops are pinned
+    # one by one against float64 in tests/test_vgg_bf16_opwise_gpu.py
     'sr_vgg_pack_bf16': 'tests/test_vgg_driver_gpu.py::test_driver_is_bit_identical_to_the_per_layer_route',
     'sr_vgg_forward_bf16': 'tests/test_vgg_driver_gpu.py::test_driver_is_bit_identical_to_the_per_layer_route',
     'sr_vgg_backward_bf16': 'tests/test_vgg_driver_gpu.py::test_driver_is_bit_identical_to_the_per_layer_route',
