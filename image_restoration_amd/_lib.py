@@ -1,6 +1,6 @@
 """ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h,
-include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h, include/sr_hip_dcn.h, include/sr_hip_edvr.h, include/sr_hip_edvr_bf16.h and
-include/sr_hip_stylegan2.h).
+include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h, include/sr_hip_dcn.h, include/sr_hip_edvr.h, include/sr_hip_edvr_bf16.h,
+include/sr_hip_stylegan2.h and include/sr_hip_train_groups.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -461,6 +461,19 @@ STYLEGAN2_SIGNATURES = {
     'sr_fused_bias_act_bwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _S, C.c_float, C.c_float, _P, C.c_size_t, _P]),
 }
 
+
+class AdamClass(C.Structure):
+    """struct sr_adam_class (include/sr_hip_train_groups.h)."""
+    _fields_ = [('lr', C.c_float), ('step', C.c_int), ('active', C.c_int)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_train_groups.h declares
+TRAIN_GROUPS_SIGNATURES = {
+    'sr_adam_step_groups_f32': (C.c_int, [_P, _P, _P, _P, _S, _P, C.POINTER(AdamClass), _I] + [C.c_float] * 5 + [_P, _P, _P]),
+    'sr_adam_class_table': (C.c_int, [C.POINTER(AdamClass), _I, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+}
+
 _lib = None
 
 
@@ -475,7 +488,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
-            + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()):
+            + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1058,5 +1058,6 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "fused_bias_act_finish_kernel"};
     return snames[id - 131];
   }
+  if (id == 139) return "adam_groups_kernel";  // adam_groups.hip (include/sr_hip_train_groups.h); 138 stays unnamed
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -57,3 +57,39 @@ class DevicePatchPipeline:
         out['lq'] = self._launch(batch['lq_u8'], origin, 1, sym, self.gt_size // self.scale)
         out['gt'] = self._launch(batch['gt_u8'], origin, self.scale, sym, self.gt_size)
         return out
+
+
+class DeviceClipPipeline(DevicePatchPipeline):
+    """The same for clips (``REDSDataset(device_augment: true | full)``): the batch holds uint8 LQ windows [B, t, h, w, 3], one uint8
+    GT window [B, H, W, 3] per clip and one symmetry code (and, with ``full``, one window origin) per clip.  A clip's frames share
+    its crop and its symmetry, so the LQ side is the image case on the B * t frames with each clip's code and origin repeated t
+    times — a reshape, not a new kernel: sr_patch_augment_u8_f32 once on the frames, once on the GT."""
+
+    @staticmethod
+    def per_frame(sym, origin, t):
+        """Host half: the per-clip symmetry codes [B] and window origins [B, 2] (or None) as per-frame arrays [B * t], [B * t, 2]."""
+        sym_t = sym.to(torch.int32).repeat_interleave(t).contiguous()
+        origin_t = None if origin is None else origin.to(torch.int32).repeat_interleave(t, dim=0).contiguous()
+        return sym_t, origin_t
+
+    def output_shapes(self, b, t):
+        lq = self.gt_size // self.scale
+        return (b, t, 3, lq, lq), (b, 3, self.gt_size, self.gt_size)
+
+    def __call__(self, batch):
+        if 'lq_u8' not in batch:
+            return batch
+        clips = batch['lq_u8']
+        if clips.dim() != 5 or clips.size(4) != 3:
+            raise ValueError(f'expected a uint8 [B, t, H, W, 3] batch of clips, got {tuple(clips.shape)}')
+        b, t, h, w, _ = clips.shape
+        sym = batch['sym'].to(torch.int32).contiguous()
+        origin = batch.get('window')
+        if origin is not None:
+            origin = origin.to(torch.int32)
+        sym_t, origin_t = self.per_frame(sym, origin, t)
+        lq_shape, _ = self.output_shapes(b, t)
+        out = {k: v for k, v in batch.items() if k not in ('lq_u8', 'gt_u8', 'sym', 'window')}
+        out['lq'] = self._launch(clips.reshape(b * t, h, w, 3), origin_t, 1, sym_t, self.gt_size // self.scale).view(lq_shape)
+        out['gt'] = self._launch(batch['gt_u8'], origin, self.scale, sym, self.gt_size)
+        return out

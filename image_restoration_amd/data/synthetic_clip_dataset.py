@@ -1,0 +1,42 @@
+"""Synthetic training clips with REDSDataset's sample dict (``lq`` [t, c, h, w], ``gt`` [c, h, w] of the centre frame, ``key``), so
+the EDVR quick start runs without REDS: one random texture per clip (uniform noise, numpy PCG64), translated from frame to frame by
+the clip's own motion, a whole number of LQ pixels per frame, and the LQ frames are the x``scale`` box average of the GT frames.
+The motion is free of sub-pixel parts on both grids, so every LQ frame is exactly the box average of a GT window."""
+import numpy as np
+import torch
+from torch.utils import data
+
+from ..utils.registry import DATASET_REGISTRY
+
+
+@DATASET_REGISTRY.register()
+class SyntheticClipDataset(data.Dataset):
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        self.length = int(opt.get('num_samples', 256))
+        self.gt_size = int(opt.get('gt_size', 128))
+        self.scale = int(opt.get('scale', 4))
+        self.num_frame = int(opt.get('num_frame', 5))
+        self.max_motion = int(opt.get('max_motion', 2))   # LQ pixels per frame, each axis
+        self.seed = int(opt.get('seed', 0))
+        if self.num_frame % 2 != 1:
+            raise ValueError(f'num_frame should be odd number, but got {self.num_frame}')
+        if self.gt_size % self.scale:
+            raise ValueError(f'gt_size={self.gt_size} must be a multiple of scale={self.scale}')
+
+    def __len__(self):
+        return self.length
+
+    def __getitem__(self, index):
+        rng = np.random.default_rng(self.seed * 1000003 + index)
+        t, s, g = self.num_frame, self.scale, self.gt_size
+        my, mx = (int(v) for v in rng.integers(-self.max_motion, self.max_motion + 1, size=2))
+        reach = self.max_motion * (t - 1) * s
+        texture = rng.random((3, g + reach, g + reach), dtype=np.float32)
+        y0, x0 = (reach if my < 0 else 0), (reach if mx < 0 else 0)
+        frames = np.stack([texture[:, y0 + k * my * s:y0 + k * my * s + g, x0 + k * mx * s:x0 + k * mx * s + g] for k in range(t)])
+        lq = frames.reshape(t, 3, g // s, s, g // s, s).mean(axis=(3, 5), dtype=np.float32)
+        return {'lq': torch.from_numpy(np.ascontiguousarray(lq)), 'gt': torch.from_numpy(np.ascontiguousarray(frames[t // 2])),
+                'key': f'synthetic/{index:08d}'}

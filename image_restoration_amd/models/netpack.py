@@ -44,24 +44,52 @@ class NetPack:
         self.adam = None
         self.shadow = None
         self.shadow_arena = None
+        self._shadow_epoch = None
 
     # -------------------------------------------------------------- construction
-    def attach_adam(self, settings, log=None):
+    def attach_adam(self, settings, log=None, group_of=None, group_lrs=None):
         """``settings`` is the yml block ``train.optim_<label>`` minus its ``type`` (lr, weight_decay, betas, ...).
-        Parameters with requires_grad False stay outside the arena, with the reference's warning (sr_model.py:78-83)."""
-        chosen = []
+        Parameters with requires_grad False stay outside the arena, with the reference's warning (sr_model.py:78-83).
+        ``group_of`` (parameter name -> group index) with ``group_lrs`` (one learning rate per group) builds torch's parameter
+        groups, in index order; without them there is one group, as before."""
+        chosen, grouped = [], {}
         for name, p in self.net.named_parameters():
             if p.requires_grad:
                 chosen.append(p)
+                if group_of is not None:
+                    grouped.setdefault(group_of(name), []).append(p)
             elif log is not None:
                 log.warning(f'Params {name} will not be optimized.')
+        if group_of is not None:
+            chosen = [dict(params=grouped[g], lr=group_lrs[g]) for g in sorted(grouped)]
         self.adam = optim.FlatAdam(chosen, modules=[self.net], **settings)
         self.adam.all_params = list(self.net.parameters())   # freeze() toggles these every step: one walk of the module tree, here
         return self.adam
 
     def attach_shadow(self, shadow_net):
         self.shadow = shadow_net.eval()
-        self.shadow_arena = optim.flatten_parameters(shadow_net)
+        order = None
+        if self.adam is not None and len(self.adam.param_groups) > 1:
+            # parameter groups put the live arena in group order: the shadow's arena must have the same layout for the blend
+            name_of = {id(p): n for n, p in self.net.named_parameters()}
+            twin = dict(shadow_net.named_parameters())
+            order = [twin[name_of[id(p)]] for p in self.adam.params]
+            if len(order) != len(twin):
+                raise ValueError('an EMA shadow with parameter groups needs every parameter of the network in the optimiser')
+        self.shadow_arena = optim.flatten_parameters(shadow_net, order)
+        self._shadow_epoch = None
+        if not hasattr(shadow_net, 'invalidate_packed'):
+            # a per-layer network without a pack generation of its own (EDVR): the blend rewrites its parameters behind torch's
+            # version counter, so hip_ops.cached_pack keys their weight images on this counter, as it does for FlatAdam's
+            self._shadow_epoch = [0]
+            for p in shadow_net.parameters():
+                p._sr_epoch = self._shadow_epoch
+
+    def _shadow_rewritten(self):
+        if self._shadow_epoch is not None:
+            self._shadow_epoch[0] += 1
+        else:
+            self.shadow.invalidate_packed()
 
     # -------------------------------------------------------------- one optimiser step
     def freeze(self, frozen=True):
@@ -105,11 +133,13 @@ class NetPack:
         if decay == 0:
             with torch.no_grad():
                 self.shadow_arena.copy_(live)
-            self.shadow.invalidate_packed()
+            self._shadow_rewritten()
         else:
             if not live.is_cuda:
                 raise RuntimeError('EMA update runs only on a HIP device')
             optim.ema_update(self.shadow_arena, live, decay, modules=[self.shadow])
+            if self._shadow_epoch is not None:
+                self._shadow_epoch[0] += 1
 
     # -------------------------------------------------------------- replicas
     def state_tensors(self, buffers_only=False):

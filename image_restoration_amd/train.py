@@ -13,7 +13,7 @@ import time
 import torch
 from torch.utils.data import DataLoader
 
-from .data import DeviceFeed, DevicePatchPipeline, EnlargedSampler, HostFeed, PrefetchDataLoader
+from .data import DeviceClipPipeline, DeviceFeed, DevicePatchPipeline, EnlargedSampler, HostFeed, PrefetchDataLoader
 from .models import build_model
 from .utils.options import dict2str, parse_options
 from .utils.registry import DATASET_REGISTRY
@@ -22,6 +22,14 @@ from .utils.registry import DATASET_REGISTRY
 def build_dataset(dataset_opt):
     opt = dict(dataset_opt)
     return DATASET_REGISTRY.get(opt['type'])(opt)
+
+
+CLIP_DATASETS = ('REDSDataset', )   # their device_augment batches hold clips [B, t, H, W, 3]
+
+
+def device_pipeline_class(dataset_opt):
+    """The per-batch device pipeline of a ``device_augment`` dataset: clips or single images."""
+    return DeviceClipPipeline if dataset_opt['type'] in CLIP_DATASETS else DevicePatchPipeline
 
 
 def create_train_loader(opt):
@@ -99,7 +107,7 @@ def train_pipeline(root_path, argv=None):
     # datasets.train.prefetch_mode: None / 'cpu' iterate the loader, 'cuda' stages the next batch on a copy stream
     train_block = next(v for v in opt['datasets'].values() if v['phase'] == 'train')
     prefetch_mode = train_block.get('prefetch_mode')
-    device_side = DevicePatchPipeline(train_block) if train_block.get('device_augment') else None
+    device_side = device_pipeline_class(train_block)(train_block) if train_block.get('device_augment') else None
     if device_side is not None and prefetch_mode != 'cuda':
         raise ValueError("device_augment needs prefetch_mode: cuda (the augmentation kernel runs on the feed's copy stream)")
     if prefetch_mode is None or prefetch_mode == 'cpu':
