@@ -1,6 +1,6 @@
 """ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h,
 include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h, include/sr_hip_dcn.h, include/sr_hip_edvr.h, include/sr_hip_edvr_bf16.h,
-include/sr_hip_stylegan2.h and include/sr_hip_train_groups.h).
+include/sr_hip_stylegan2.h, include/sr_hip_train_groups.h and include/sr_hip_degrade.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -474,6 +474,16 @@ TRAIN_GROUPS_SIGNATURES = {
                                       C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
+# name -> (restype, argtypes); every symbol include/sr_hip_degrade.h declares
+DEGRADE_SIGNATURES = {
+    'sr_filter2d_f32': (C.c_int, [_P, _P, _P] + [_I] * 6 + [_P]),
+    'sr_resize_bilinear_f32': (C.c_int, [_P, _P, _P, _P] + [_I] * 6 + [_P]),
+    'sr_add_gaussian_noise_f32': (C.c_int, [_P] * 6 + [_I] * 6 + [_P]),
+    'sr_diffjpeg_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'sr_diffjpeg_bwd_f32': (C.c_int, [_P] * 5 + [_I, _I, _I, _P]),
+    'sr_degrade_finish_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
+}
+
 _lib = None
 
 
@@ -488,7 +498,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
-            + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()):
+            + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
+            + list(DEGRADE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

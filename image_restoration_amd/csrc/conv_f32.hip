@@ -1059,5 +1059,10 @@ extern "C" const char* sr_kernel_name(int id) {
     return snames[id - 131];
   }
   if (id == 139) return "adam_groups_kernel";  // adam_groups.hip (include/sr_hip_train_groups.h); 138 stays unnamed
+  if (id >= 141 && id < 147) {  // degrade_ops.hip (include/sr_hip_degrade.h); 140 stays unnamed
+    static const char* gnames[6] = {"filter2d_kernel", "resize_bilinear_kernel", "gaussian_noise_kernel<*>",
+                                    "diffjpeg_kernel", "diffjpeg_bwd_kernel",    "degrade_finish_kernel<*>"};
+    return gnames[id - 141];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

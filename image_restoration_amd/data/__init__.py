@@ -3,7 +3,8 @@ augmentation and prefetchers, the REDS training clips and the
 clip datasets for benchmarks / smoke training."""
 from .data_sampler import EnlargedSampler  # noqa: F401
 from .paired_image_dataset import PairedImageDataset  # noqa: F401
-from .device_pipeline import DeviceClipPipeline, DevicePatchPipeline  # noqa: F401
+from .device_pipeline import DeviceClipPipeline, DeviceDegradePipeline, DevicePatchPipeline  # noqa: F401
+from .ocr_degradation_dataset import OCRDegradationDataset  # noqa: F401
 from .prefetch_dataloader import (BackgroundIterator, CPUPrefetcher, CUDAPrefetcher, DeviceFeed, HostFeed,  # noqa: F401
                                   PrefetchDataLoader)
 from .reds_dataset import REDSDataset  # noqa: F401

@@ -1332,3 +1332,141 @@ def fused_bias_act_bwd(g, out, slope=0.2, scale=2 ** 0.5, want_bias=True):
                     gbias.data_ptr() if want_bias else None, n, c, inner, float(slope), float(scale),
                     ws.data_ptr() if want_bias else None, nbytes)
     return gx, gbias
+
+
+# ---- the degradation chain of the plate training set on NCHW tensors (include/sr_hip_degrade.h) ----
+
+def _image_batch(t, what, channels=None):
+    _need_cuda(t, what)
+    _arg(t.dim() == 4 and t.is_contiguous() and t.dtype == torch.float32 and t.numel() > 0
+         and (channels is None or t.size(1) == channels),
+         f'{what}: needs a non-empty contiguous fp32 [B, {channels or "C"}, H, W] tensor, got {t.dtype} {tuple(t.shape)}')
+    return t.shape
+
+
+def _per_sample(v, b, like, what, width=None):
+    """A per-sample fp32 device array [B] (or [B, width]) from a tensor, a sequence or a number; None stays None."""
+    if v is None:
+        return None
+    if not torch.is_tensor(v):
+        v = torch.tensor(v, dtype=torch.float32)
+        if v.dim() == 0:
+            v = v.expand(b)
+    v = v.to(device=like.device, dtype=torch.float32).contiguous()
+    _arg(tuple(v.shape) == ((b,) if width is None else (b, width)), f'{what}: expected {b} per-sample values, got {tuple(v.shape)}')
+    return v
+
+
+def ragged_sizes(sizes, b, hmax, wmax, dev, what='sizes'):
+    """The int32 device array [B, 2] of (h_i, w_i) a ragged batch travels with.  A sequence or a CPU tensor is checked here (every
+    entry in 1..Hmax x 1..Wmax: the C ABI cannot refuse what lies on the device, its kernels clamp); a device tensor passes as is."""
+    if sizes is None:
+        return None
+    if torch.is_tensor(sizes) and sizes.is_cuda:
+        _arg(sizes.dtype == torch.int32 and tuple(sizes.shape) == (b, 2) and sizes.is_contiguous(),
+             f'{what}: a device size array is int32 [{b}, 2]')
+        return sizes
+    host = torch.as_tensor(sizes).to(torch.int64).reshape(-1, 2)
+    _arg(host.size(0) == b, f'{what}: {host.size(0)} sizes for a batch of {b}')
+    _arg(bool((host >= 1).all()) and int(host[:, 0].max()) <= hmax and int(host[:, 1].max()) <= wmax,
+         f'{what}: every (h, w) must lie in 1..{hmax} x 1..{wmax}, got {host.tolist()}')
+    return host.to(torch.int32).to(dev)
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def filter2d(img, kernel, out=None):
+    """Correlation of every plane of ``img`` [B, C, H, W] with ``kernel`` [1 or B, k, k] under the reflect border — one
+    sr_filter2d_f32 launch."""
+    b, c, h, w = _image_batch(img, 'filter2d')
+    _arg(kernel.dim() == 3 and kernel.size(1) == kernel.size(2) and kernel.dtype == torch.float32 and kernel.device == img.device,
+         f'filter2d: needs an fp32 [1 or B, k, k] kernel on the device of the image, got {kernel.dtype} {tuple(kernel.shape)}')
+    kernel = kernel.contiguous()
+    k, kb = kernel.size(1), kernel.size(0)
+    _arg(k % 2 == 1 and k <= 21, f'filter2d: kernel size {k} is not supported: odd, 1..21')
+    _arg(h > k // 2 and w > k // 2, f'filter2d: a {h}x{w} image is too small to reflect by {k // 2}')
+    _arg(kb in (1, b), f'filter2d: {kb} kernels for a batch of {b}')
+    if out is None:
+        out = torch.empty_like(img)
+    _arg(out.shape == img.shape and out.is_contiguous() and out.dtype == torch.float32 and out.data_ptr() != img.data_ptr(),
+         'filter2d: output does not fit (and cannot be the input)')
+    _launch_arg('sr_filter2d_f32', img.device, img.data_ptr(), kernel.data_ptr(), out.data_ptr(), b, c, h, w, k, kb)
+    return out
+
+
+def resize_bilinear(x, size, src_sizes=None, dst_sizes=None, out=None):
+    """``x`` [B, C, Hs, Ws] to [B, C, *size], bilinear, half-pixel centres, no antialiasing; with size arrays each sample is
+    resized from / to its own rectangle and the rest of the output is zero — one sr_resize_bilinear_f32 launch."""
+    b, c, hs, ws = _image_batch(x, 'resize_bilinear')
+    hd, wd = int(size[0]), int(size[1])
+    _arg(hd > 0 and wd > 0, f'resize_bilinear: output size {hd}x{wd} is not positive')
+    ss = ragged_sizes(src_sizes, b, hs, ws, x.device, 'resize_bilinear: src_sizes')
+    ds = ragged_sizes(dst_sizes, b, hd, wd, x.device, 'resize_bilinear: dst_sizes')
+    if out is None:
+        out = torch.empty((b, c, hd, wd), dtype=torch.float32, device=x.device)
+    _arg(tuple(out.shape) == (b, c, hd, wd) and out.is_contiguous() and out.dtype == torch.float32 and out.data_ptr() != x.data_ptr(),
+         'resize_bilinear: output does not fit (and cannot be the input)')
+    _launch_arg('sr_resize_bilinear_f32', x.device, x.data_ptr(), _p(ss), out.data_ptr(), _p(ds), b, c, hs, ws, hd, wd)
+    return out
+
+
+def add_gaussian_noise(x, noise, sigma, noise_gray=None, gray=None, clip=True, rounds=False, out=None):
+    """x + noise * sigma[b] / 255 (the gray plane for every channel where gray[b] is set), then the reference's clip / round cases
+    — one sr_add_gaussian_noise_f32 launch."""
+    b, c, h, w = _image_batch(x, 'add_gaussian_noise')
+    _arg(noise.shape == x.shape and noise.is_contiguous() and noise.dtype == torch.float32 and noise.device == x.device,
+         'add_gaussian_noise: noise does not fit the image')
+    sigma = _per_sample(sigma, b, x, 'add_gaussian_noise: sigma')
+    gray = _per_sample(gray, b, x, 'add_gaussian_noise: gray')
+    _arg(gray is None or noise_gray is not None, 'add_gaussian_noise: gray needs noise_gray')
+    _arg(noise_gray is None or (tuple(noise_gray.shape) == (b, 1, h, w) and noise_gray.is_contiguous() and noise_gray.dtype == torch.float32
+                                and noise_gray.device == x.device), f'add_gaussian_noise: noise_gray must be fp32 [{b}, 1, {h}, {w}]')
+    if out is None:
+        out = torch.empty_like(x)
+    _arg(out.shape == x.shape and out.is_contiguous() and out.dtype == torch.float32, 'add_gaussian_noise: output does not fit')
+    _launch_arg('sr_add_gaussian_noise_f32', x.device, x.data_ptr(), noise.data_ptr(), _p(noise_gray), sigma.data_ptr(), _p(gray),
+                out.data_ptr(), b, c, h, w, int(bool(clip)), int(bool(rounds)))
+    return out
+
+
+def diffjpeg(x, factor, sizes=None, differentiable=False, out=None):
+    """DiffJPEG's round trip of the RGB batch ``x`` [B, 3, H, W] in [0, 1] with the quantisation factors ``factor`` [B] — one
+    sr_diffjpeg_f32 launch."""
+    b, _, h, w = _image_batch(x, 'diffjpeg', 3)
+    factor = _per_sample(factor, b, x, 'diffjpeg: factor')
+    sz = ragged_sizes(sizes, b, h, w, x.device, 'diffjpeg: sizes')
+    if out is None:
+        out = torch.empty_like(x)
+    _arg(out.shape == x.shape and out.is_contiguous() and out.dtype == torch.float32, 'diffjpeg: output does not fit')
+    _launch_arg('sr_diffjpeg_f32', x.device, x.data_ptr(), _p(sz), factor.data_ptr(), out.data_ptr(), b, h, w, int(bool(differentiable)))
+    return out
+
+
+def diffjpeg_bwd(x, factor, grad_out, sizes=None):
+    """The gradient of diffjpeg(differentiable=True) with respect to ``x`` — one sr_diffjpeg_bwd_f32 launch; nothing but ``x`` was
+    saved."""
+    b, _, h, w = _image_batch(x, 'diffjpeg_bwd', 3)
+    _need_cuda(grad_out, 'diffjpeg_bwd')
+    grad_out = grad_out.contiguous()
+    _arg(grad_out.shape == x.shape and grad_out.dtype == torch.float32, 'diffjpeg_bwd: grad_out does not fit')
+    factor = _per_sample(factor, b, x, 'diffjpeg_bwd: factor')
+    sz = ragged_sizes(sizes, b, h, w, x.device, 'diffjpeg_bwd: sizes')
+    gx = torch.empty_like(x)
+    _launch_arg('sr_diffjpeg_bwd_f32', x.device, x.data_ptr(), _p(sz), factor.data_ptr(), grad_out.data_ptr(), gx.data_ptr(), b, h, w)
+    return gx
+
+
+def degrade_finish(x, jitter=None, gray=None, mean=None, std=None, out=None):
+    """The tail of the degradation: per-sample jitter shift + clip, gray where set, round to 8 bits, normalise — one
+    sr_degrade_finish_f32 launch on the RGB batch ``x`` [B, 3, H, W]."""
+    b, _, h, w = _image_batch(x, 'degrade_finish', 3)
+    jitter = _per_sample(jitter, b, x, 'degrade_finish: jitter', 3)
+    gray = _per_sample(gray, b, x, 'degrade_finish: gray')
+    f3 = [None if v is None else (C.c_float * 3)(*[float(t) for t in v]) for v in (mean, std)]
+    if out is None:
+        out = torch.empty_like(x)
+    _arg(out.shape == x.shape and out.is_contiguous() and out.dtype == torch.float32, 'degrade_finish: output does not fit')
+    _launch_arg('sr_degrade_finish_f32', x.device, x.data_ptr(), _p(jitter), _p(gray), out.data_ptr(), b, h, w, f3[0], f3[1])
+    return out

@@ -13,7 +13,7 @@ import time
 import torch
 from torch.utils.data import DataLoader
 
-from .data import DeviceClipPipeline, DeviceFeed, DevicePatchPipeline, EnlargedSampler, HostFeed, PrefetchDataLoader
+from .data import DeviceClipPipeline, DeviceDegradePipeline, DeviceFeed, DevicePatchPipeline, EnlargedSampler, HostFeed, PrefetchDataLoader
 from .models import build_model
 from .utils.options import dict2str, parse_options
 from .utils.registry import DATASET_REGISTRY
@@ -25,10 +25,14 @@ def build_dataset(dataset_opt):
 
 
 CLIP_DATASETS = ('REDSDataset', )   # their device_augment batches hold clips [B, t, H, W, 3]
+DEGRADE_DATASETS = ('OCRDegradationDataset', )   # device_degrade: the batch holds uint8 GT images and the drawn degradation
 
 
 def device_pipeline_class(dataset_opt):
-    """The per-batch device pipeline of a ``device_augment`` dataset: clips or single images."""
+    """The per-batch device pipeline of a ``device_augment`` dataset (clips or single images) or of the ``device_degrade`` plate
+    set."""
+    if dataset_opt['type'] in DEGRADE_DATASETS:
+        return DeviceDegradePipeline
     return DeviceClipPipeline if dataset_opt['type'] in CLIP_DATASETS else DevicePatchPipeline
 
 
@@ -107,9 +111,10 @@ def train_pipeline(root_path, argv=None):
     # datasets.train.prefetch_mode: None / 'cpu' iterate the loader, 'cuda' stages the next batch on a copy stream
     train_block = next(v for v in opt['datasets'].values() if v['phase'] == 'train')
     prefetch_mode = train_block.get('prefetch_mode')
-    device_side = device_pipeline_class(train_block)(train_block) if train_block.get('device_augment') else None
+    device_side = device_pipeline_class(train_block)(train_block) if train_block.get('device_augment') or train_block.get('device_degrade') \
+        else None
     if device_side is not None and prefetch_mode != 'cuda':
-        raise ValueError("device_augment needs prefetch_mode: cuda (the augmentation kernel runs on the feed's copy stream)")
+        raise ValueError("device_augment / device_degrade needs prefetch_mode: cuda (the augmentation kernel runs on the feed's copy stream)")
     if prefetch_mode is None or prefetch_mode == 'cpu':
         prefetcher = HostFeed(loader)
     elif prefetch_mode == 'cuda':
