@@ -1,6 +1,6 @@
 """ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h,
 include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h, include/sr_hip_dcn.h, include/sr_hip_edvr.h, include/sr_hip_edvr_bf16.h,
-include/sr_hip_stylegan2.h, include/sr_hip_train_groups.h and include/sr_hip_degrade.h).
+include/sr_hip_stylegan2.h, include/sr_hip_train_groups.h, include/sr_hip_degrade.h and include/sr_hip_flow.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -484,6 +484,27 @@ DEGRADE_SIGNATURES = {
     'sr_degrade_finish_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
 }
 
+
+class Conv7x7Desc(C.Structure):
+    """struct sr_conv7x7_desc (include/sr_hip_flow.h)."""
+    _fields_ = [('in_', C.c_void_p), ('in_img_stride', C.c_longlong), ('cin', C.c_int), ('cout', C.c_int), ('n', C.c_int),
+                ('h', C.c_int), ('w', C.c_int), ('packed', C.c_void_p), ('out', C.c_void_p), ('out_img_stride', C.c_longlong),
+                ('relu', C.c_int), ('res1', C.c_void_p), ('res1_img_stride', C.c_longlong)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_flow.h declares
+FLOW_SIGNATURES = {
+    'sr_conv7x7_instance': (C.c_int, [_I, _I]),
+    'sr_conv7x7_packed_floats': (C.c_size_t, [_I, _I]),
+    'sr_conv7x7_pack_f32': (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    'sr_conv7x7_f32': (C.c_int, [C.POINTER(Conv7x7Desc), _P]),
+    'sr_flow_warp_f32': (C.c_int, [_P, _P, _P] + [_I] * 6 + [_P]),
+    'sr_flow_warp_bwd_f32': (C.c_int, [_P] * 5 + [_I] * 6 + [_P]),
+    'sr_spynet_level_input_f32': (C.c_int, [_P] * 5 + [_I] * 3 + [_P]),
+    'sr_spynet_preprocess_f32': (C.c_int, [_P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
+    'sr_avgpool2x2_f32': (C.c_int, [_P, _P, _I, _I, _I, _P]),
+}
+
 _lib = None
 
 
@@ -499,7 +520,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
-            + list(DEGRADE_SIGNATURES.items()):
+            + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

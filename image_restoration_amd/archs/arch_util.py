@@ -14,6 +14,7 @@ from torch.nn import init
 from .. import hip_autograd as A
 from .. import hip_ops as H
 from ..ops.dcn import ModulatedDeformConvPack
+from ..ops.flow_warp import flow_warp  # noqa: F401  (the reference's arch_util.flow_warp, :112-143)
 
 
 class Conv3x3Params(nn.Module):
@@ -75,6 +76,31 @@ def upscale_stages(upscale):
     if isinstance(upscale, int) and upscale >= 1 and upscale & (upscale - 1) == 0:
         return [2] * (int(upscale).bit_length() - 1)
     return None
+
+
+def resize_flow(flow, size_type, sizes, interp_mode='bilinear', align_corners=False):
+    """Resize a flow [N, 2, H, W] by a ratio or to a shape (reference arch_util.py:146-181): the x channel is scaled by
+    out_w / w and the y channel by out_h / h (sr_channel_affine_f32), then the map is resized (sr_resize_bilinear_f32, whose
+    half-pixel rule is F.interpolate's ``align_corners=False``).  ``sizes``: [ratio_h, ratio_w] or [out_h, out_w].  ValueError
+    for another ``size_type``, interpolation or ``align_corners=True``; device fp32 tensors only (no gradient)."""
+    if size_type not in ('ratio', 'shape'):
+        raise ValueError(f'Size type should be ratio or shape, but got type {size_type}.')
+    if interp_mode != 'bilinear' or align_corners:
+        raise ValueError(f"resize_flow: interp_mode '{interp_mode}', align_corners={align_corners} is not supported; supported: "
+                         "'bilinear', align_corners=False")
+    if flow.dim() != 4 or flow.size(1) != 2 or flow.dtype != torch.float32:
+        raise ValueError(f'resize_flow: expected an fp32 [N, 2, H, W] flow, got {flow.dtype} {tuple(flow.shape)}')
+    H._need_cuda(flow, 'resize_flow')
+    n, _, h, w = flow.shape
+    if size_type == 'ratio':
+        oh, ow = int(h * sizes[0]), int(w * sizes[1])
+    else:
+        oh, ow = int(sizes[0]), int(sizes[1])
+    flow = flow.detach().contiguous()
+    ratio = torch.tensor([ow / w, oh / h], dtype=torch.float32, device=flow.device)
+    scaled = torch.empty_like(flow)
+    H.launch('sr_channel_affine_f32', flow.device, flow.data_ptr(), scaled.data_ptr(), ratio.data_ptr(), None, n, 2, h * w)
+    return H.resize_bilinear(scaled, (oh, ow))
 
 
 class ResidualBlockNoBN(nn.Module):

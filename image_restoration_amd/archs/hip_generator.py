@@ -44,7 +44,8 @@ class HipGenerator(nn.Module):
 
     def packed(self, conv, mode=0, bf16=False):
         """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter):
-        sr_conv3x3_pack_f32 for 3x3 convs (every dilation), sr_convk_pack_f32 for any other kernel size; rebuilt when the
+        sr_conv3x3_pack_f32 for 3x3 convs (every dilation), sr_conv7x7_pack_f32 for SpyNet's 7x7 convs, sr_convk_pack_f32 for any
+        other kernel size; rebuilt when the
         parameter storage, its version, the FlatAdam epoch of the parameter or this net's generation (invalidate_packed) changed.
         Not hip_ops.cached_pack: that cache is keyed on the process-global epoch, so one net's invalidate_packed() would repack
         every other network's images (the discriminator's after each generator step)."""
@@ -56,7 +57,8 @@ class HipGenerator(nn.Module):
             return hit[1]
         if w.dtype != torch.float32 or b.dtype != torch.float32:
             raise _lib.SrHipError(f'{type(self).__name__} parameters must be fp32')
-        cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv if w.shape[2] == 3 else hip_ops.PackedConvK
+        cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv if w.shape[2] == 3 else \
+            hip_ops.PackedConv7x7 if w.shape[2] == 7 else hip_ops.PackedConvK
         pc = cls(w, b if mode == 0 else None, mode=mode)
         self._packs[key] = (sig, pc)
         return pc

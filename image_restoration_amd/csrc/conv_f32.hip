@@ -1064,5 +1064,12 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "diffjpeg_kernel", "diffjpeg_bwd_kernel",    "degrade_finish_kernel<*>"};
     return gnames[id - 141];
   }
+  if (id >= 148 && id < 158) {  // flow_ops.hip (include/sr_hip_flow.h); 147 stays unnamed
+    static const char* onames[10] = {"conv7x7_f32_kernelILi1ELi4EE", "conv7x7_f32_kernelILi2ELi2EE", "conv7x7_fewcout_f32_kernel",
+                                     "conv7x7_pack_kernel",          "flow_warp_kernel<*>",          "flow_warp_bwd_dx_kernel<*>",
+                                     "flow_warp_bwd_dflow_kernel<*>", "spynet_level_input_kernel",   "spynet_preprocess_kernel",
+                                     "avgpool2x2_kernel"};
+    return onames[id - 148];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

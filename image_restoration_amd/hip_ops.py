@@ -1470,3 +1470,143 @@ def degrade_finish(x, jitter=None, gray=None, mean=None, std=None, out=None):
     _arg(out.shape == x.shape and out.is_contiguous() and out.dtype == torch.float32, 'degrade_finish: output does not fit')
     _launch_arg('sr_degrade_finish_f32', x.device, x.data_ptr(), _p(jitter), _p(gray), out.data_ptr(), b, h, w, f3[0], f3[1])
     return out
+
+
+# ---- optical flow: the 7x7 conv, flow warping and SpyNet's pieces (include/sr_hip_flow.h) ----
+
+CONV7X7_SHAPES = ((8, 32), (32, 64), (64, 32), (32, 16), (16, 2))   # (cin, cout) of SpyNet's BasicModule
+FLOW_PADDING = {'zeros': 0, 'border': 1}
+
+
+def conv7x7_instance(cout, cin):
+    """The kernel instance sr_conv7x7_f32 runs a (cin, cout) pair on (sr_conv7x7_instance): 0 = 32 couts x 16 rows, 1 = 64 couts
+    x 8 rows, 2 = the few-cout form.  ValueError for a pair that is not served."""
+    inst = _lib.load().sr_conv7x7_instance(cout, cin)
+    _arg(inst >= 0, f'conv7x7: (cin, cout) = ({cin}, {cout}) is not supported; supported: {CONV7X7_SHAPES}')
+    return inst
+
+
+class PackedConv7x7:
+    """MFMA operand image (weights, then bias) of one 7x7 conv of SpyNet — sr_conv7x7_pack_f32."""
+
+    def __init__(self, weight, bias=None, mode=0):
+        _need_cuda(weight, 'PackedConv7x7')
+        _arg(mode == 0, 'PackedConv7x7: only the forward image exists')
+        _arg(weight.dim() == 4 and tuple(weight.shape[2:]) == (7, 7) and weight.dtype == torch.float32,
+             f'PackedConv7x7: needs an fp32 [cout, cin, 7, 7] weight, got {weight.dtype} {tuple(weight.shape)}')
+        _arg(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (weight.size(0),)), 'PackedConv7x7: bias does not fit')
+        weight = weight.detach().contiguous()
+        bias = None if bias is None else bias.detach().contiguous()
+        self.cout, self.cin = weight.shape[:2]
+        self.instance = conv7x7_instance(self.cout, self.cin)
+        self.w = torch.empty(_lib.load().sr_conv7x7_packed_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
+        _launch_arg('sr_conv7x7_pack_f32', weight.device, weight.data_ptr(), _p(bias), self.cout, self.cin, self.w.data_ptr())
+
+
+def conv7x7(src, pc, out=None, *, relu=False, res1=None):
+    """out = [relu](conv7x7(src) + bias) [+ res1] on CB8, stride 1, pad 3 — one sr_conv7x7_f32 launch.  ``pc``: PackedConv7x7."""
+    _arg(src.channels == pc.cin, f'conv7x7: source has {src.channels} channels, the weight image {pc.cin}')
+    if out is None:
+        out = CB8.empty(src.n, pc.cout, src.h, src.w, src.device)
+    cob = (pc.cout + 7) // 8
+    _arg((out.n, out.h, out.w) == (src.n, src.h, src.w) and out.cbn >= cob, 'conv7x7: output window does not fit')
+    _arg(res1 is None or ((res1.n, res1.h, res1.w) == (src.n, src.h, src.w) and res1.cbn >= cob), 'conv7x7: res1 does not fit')
+    d = _lib.Conv7x7Desc()
+    d.in_, d.in_img_stride, d.cin, d.cout, d.n, d.h, d.w = src.ptr, src.img_stride, pc.cin, pc.cout, src.n, src.h, src.w
+    d.packed, d.out, d.out_img_stride, d.relu = pc.w.data_ptr(), out.ptr, out.img_stride, int(bool(relu))
+    if res1 is not None:
+        d.res1, d.res1_img_stride = res1.ptr, res1.img_stride
+    _launch_arg('sr_conv7x7_f32', src.device, C.byref(d))
+    return out
+
+
+def _warp_operands(x, flow, channels, padding, what):
+    """(pointer source, n, c, h, w, layout) of a warp call: ``x`` an fp32 NCHW tensor, or a CB8 window that is its whole buffer
+    with ``channels`` real channels."""
+    _arg(padding in FLOW_PADDING, f"{what}: padding_mode '{padding}' is not supported; supported: 'zeros', 'border'")
+    if isinstance(x, CB8):
+        c = x.channels if channels is None else channels
+        _arg(x.cb0 == 0 and x.cbn == x.buf.size(1) == (c + 7) // 8, f'{what}: a CB8 source is a whole buffer of ceil({c} / 8) blocks')
+        n, h, w, layout, dev = x.n, x.h, x.w, 1, x.device
+    else:
+        _need_cuda(x, what)
+        _arg(x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32 and x.numel() > 0,
+             f'{what}: needs a non-empty contiguous fp32 [N, C, H, W] tensor, got {x.dtype} {tuple(x.shape)}')
+        (n, c, h, w), layout, dev = x.shape, 0, x.device
+    _arg(flow.dtype == torch.float32 and flow.is_contiguous() and flow.device == dev and tuple(flow.shape) == (n, h, w, 2),
+         f'{what}: flow must be a contiguous fp32 [{n}, {h}, {w}, 2] tensor on the device of x, got {flow.dtype} {tuple(flow.shape)}')
+    return n, c, h, w, layout
+
+
+def _like(x):
+    return CB8(torch.empty_like(x.buf)) if isinstance(x, CB8) else torch.empty_like(x)
+
+
+def _tp(t):
+    return t.ptr if isinstance(t, CB8) else t.data_ptr()
+
+
+def flow_warp(x, flow, padding='zeros', channels=None, out=None):
+    """grid_sample(x, pixel grid + flow, bilinear, ``padding``, align_corners=True) — one sr_flow_warp_f32 launch.  ``x``: NCHW
+    tensor or CB8 buffer (``channels`` real channels), ``flow`` [N, H, W, 2] in pixels; the result is laid out like ``x``."""
+    n, c, h, w, layout = _warp_operands(x, flow, channels, padding, 'flow_warp')
+    if out is None:
+        out = _like(x)
+    _arg(isinstance(out, CB8) == bool(layout) and (out.buf.shape == x.buf.shape if layout else (out.shape == x.shape and out.is_contiguous()
+                                                                                 and out.dtype == torch.float32)),
+         'flow_warp: output does not fit')
+    _launch_arg('sr_flow_warp_f32', flow.device, _tp(x), flow.data_ptr(), _tp(out), n, c, h, w, layout, FLOW_PADDING[padding])
+    return out
+
+
+def flow_warp_bwd(x, flow, g, padding='zeros', channels=None, want_dx=True, want_dflow=True):
+    """(dx, dflow) of flow_warp from ``g``, the gradient of its output (laid out like ``x``) — sr_flow_warp_bwd_f32.  dx is
+    accumulated with float atomics into a zeroed tensor; dflow is a gather."""
+    n, c, h, w, layout = _warp_operands(x, flow, channels, padding, 'flow_warp_bwd')
+    _arg(isinstance(g, CB8) == bool(layout) and (g.buf.shape == x.buf.shape if layout else (g.shape == x.shape and g.is_contiguous()
+                                                                           and g.dtype == torch.float32)),
+         'flow_warp_bwd: the output gradient does not fit')
+    dx = dflow = None
+    if want_dx:
+        dx = CB8(torch.zeros_like(x.buf)) if layout else torch.zeros_like(x)
+    if want_dflow:
+        dflow = torch.empty_like(flow)
+    if want_dx or want_dflow:
+        _launch_arg('sr_flow_warp_bwd_f32', flow.device, _tp(x), flow.data_ptr(), _tp(g), None if dx is None else _tp(dx), _p(dflow),
+                    n, c, h, w, layout, FLOW_PADDING[padding])
+    return dx, dflow
+
+
+def spynet_level_input(ref, supp, flow_prev=None):
+    """(the level's 8-channel CB8 input block [ref, warp(supp, up), up], up as a CB8 block) from the level's images [N, 3, H, W]
+    and the coarser level's flow (a one-block CB8 window at H / 2 x W / 2, None at the coarsest level: up = 0) — one
+    sr_spynet_level_input_f32 launch."""
+    n, _, h, w = _image_batch(ref, 'spynet_level_input', 3)
+    _arg(supp.shape == ref.shape and supp.is_contiguous() and supp.dtype == torch.float32 and supp.device == ref.device,
+         'spynet_level_input: supp does not fit ref')
+    _arg(flow_prev is None or (h % 2 == 0 and w % 2 == 0 and flow_prev.cb0 == 0 and tuple(flow_prev.buf.shape) == (n, 1, h // 2, w // 2, 8)),
+         f'spynet_level_input: flow_prev must be one CB8 block at {h // 2}x{w // 2}')
+    out, up = CB8.empty(n, 8, h, w, ref.device), CB8.empty(n, 8, h, w, ref.device)
+    _launch_arg('sr_spynet_level_input_f32', ref.device, ref.data_ptr(), supp.data_ptr(), None if flow_prev is None else flow_prev.ptr,
+                out.ptr, up.ptr, n, h, w)
+    return out, up
+
+
+def spynet_preprocess(x, mean, std, out=None):
+    """(x - mean[c]) / std[c] on an RGB batch [N, 3, H, W] — one sr_spynet_preprocess_f32 launch."""
+    n, _, h, w = _image_batch(x, 'spynet_preprocess', 3)
+    f3 = [(C.c_float * 3)(*[float(t) for t in v]) for v in (mean, std)]
+    if out is None:
+        out = torch.empty_like(x)
+    _arg(out.shape == x.shape and out.is_contiguous() and out.dtype == torch.float32, 'spynet_preprocess: output does not fit')
+    _launch_arg('sr_spynet_preprocess_f32', x.device, x.data_ptr(), out.data_ptr(), n, h, w, f3[0], f3[1])
+    return out
+
+
+def avgpool2x2(x):
+    """F.avg_pool2d(x, 2, 2) of a contiguous fp32 [N, C, H, W] tensor with even H and W — one sr_avgpool2x2_f32 launch."""
+    n, c, h, w = _image_batch(x, 'avgpool2x2')
+    _arg(h % 2 == 0 and w % 2 == 0, f'avgpool2x2: {h}x{w} is not even')
+    out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    _launch_arg('sr_avgpool2x2_f32', x.device, x.data_ptr(), out.data_ptr(), n * c, h, w)
+    return out
