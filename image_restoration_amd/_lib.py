@@ -505,6 +505,31 @@ FLOW_SIGNATURES = {
     'sr_avgpool2x2_f32': (C.c_int, [_P, _P, _I, _I, _I, _P]),
 }
 
+
+class VsrPropDesc(C.Structure):
+    """struct sr_vsr_prop_desc (include/sr_hip_vsr.h)."""
+    _fields_ = [('frame', C.c_void_p), ('frame_img_stride', C.c_longlong), ('prev', C.c_void_p), ('prev_img_stride', C.c_longlong),
+                ('flow', C.c_void_p), ('flow_img_stride', C.c_longlong), ('frame_out', C.c_void_p),
+                ('frame_out_img_stride', C.c_longlong), ('warp_out', C.c_void_p), ('warp_out_img_stride', C.c_longlong),
+                ('n', C.c_int), ('h', C.c_int), ('w', C.c_int), ('fb', C.c_int)]
+
+
+class VsrTrunkCfg(C.Structure):
+    """struct sr_vsr_trunk_cfg (include/sr_hip_vsr.h)."""
+    _fields_ = [('num_feat', C.c_int), ('num_block', C.c_int), ('cin_segs', C.c_int)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_vsr.h declares
+VSR_SIGNATURES = {
+    'sr_vsr_prop_input_f32': (C.c_int, [C.POINTER(VsrPropDesc), _P]),
+    'sr_vsr_trunk_num_params': (C.c_int, [C.POINTER(VsrTrunkCfg)]),
+    'sr_vsr_trunk_conv_wino': (C.c_int, [C.POINTER(VsrTrunkCfg), _I]),
+    'sr_vsr_trunk_packed_bytes': (C.c_size_t, [C.POINTER(VsrTrunkCfg)]),
+    'sr_vsr_trunk_pack_f32': (C.c_int, [C.POINTER(VsrTrunkCfg), C.POINTER(C.c_void_p), _P, _P]),
+    'sr_vsr_trunk_workspace_bytes': (C.c_size_t, [C.POINTER(VsrTrunkCfg), _I, _I, _I]),
+    'sr_vsr_trunk_f32': (C.c_int, [C.POINTER(VsrTrunkCfg), _P, _P, C.c_longlong, _P, C.c_longlong, _I, _I, _I, _P, C.c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -520,7 +545,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
-            + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()):
+            + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,363 @@
+"""BasicVSR, the recurrent video super-resolution network of the reference (``basicsr/archs/basicvsr_arch.py``), on libsr_hip.so.
+
+Same constructor, state_dict keys, order and shapes (``spynet.*``, ``backward_trunk.main.0.weight``,
+``backward_trunk.main.2.{i}.conv1.weight``, ``fusion.weight`` ...) and the same initialisation draws in the same order as the
+reference, so a checkpoint loads key for key and a seeded fresh network has the reference's parameters.  The modules only hold
+parameters; ``forward`` is a composition of launches:
+
+    flows               one batched SpyNet call for both directions (SpyNet is batch-independent bit for bit), chunked over pairs
+    per step of a branch    sr_vsr_prop_input_f32: the frame block and flow_warp(previous feature, flow) written where the trunk's
+                            first conv reads them; sr_vsr_trunk_f32: the 1 + 2 * num_block convs of ConvResidualBlocks in one C call,
+                            the last one writing into the step's window of the per-clip feature tensor
+    reconstruction      once, batched over frames: fusion 1x1, upconv1 / upconv2 + pixel shuffle (the LeakyReLU after a shuffle
+                        commutes with it and runs in the conv's epilogue), conv_hr, conv_last to NCHW, the x4 bilinear base added
+                        in place; chunked over frames by a byte budget
+
+The per-clip feature tensor is [n * b, 2 * num_feat / 8, h, w, 8], frame-major: blocks [0, fb) of image (i, batch) hold the
+backward branch's feature of frame i, blocks [fb, 2 fb) the forward branch's, so ``cat([out_l[i], feat_prop])`` is the image itself
+and is never copied.  The backward branch runs first, then the forward branch.
+
+Inference only, fp32, x4: outputs never carry a grad_fn, and a forward that would need a graph (train mode, grad enabled,
+something requiring grad) raises NotImplementedError — training (SpyNet's backward, the recurrent backward) is the follow-up.
+ValueError, before anything is launched, for: fewer than two frames (the reference's ``get_flow`` cannot reshape an empty batch),
+channels other than 3, a dtype other than fp32, a side of 32 pixels or fewer (SpyNet's rule), ``num_feat % 8 != 0``.
+"""
+import torch
+from torch import nn
+from torch.nn import functional as F
+
+from .. import _lib, hip_ops
+from ..utils.registry import ARCH_REGISTRY
+from .arch_util import Conv3x3Params, ResidualBlockNoBN, make_layer
+from .edvr_arch import _FP32, PCDAlignment, TSAFusion
+from .hip_driver import HipDriverNet
+from .hip_generator import HipGenerator
+from .spynet_arch import SpyNet
+
+_FLOW_BUDGET = 1 << 30      # bytes of SpyNet activations alive at once
+_RECON_BUDGET = 2 << 30     # bytes of high-resolution activations alive at once
+
+
+class ConvResidualBlocks(HipDriverNet):
+    """Parameters of the reference's ConvResidualBlocks: ``main`` = conv 3x3 (num_in_ch -> num_out_ch), LeakyReLU(0.1),
+    ``num_block`` ResidualBlockNoBN.  ``num_in_ch`` is 3 + k * num_out_ch (k = 1, 2): the frame, then k feature maps.  No forward:
+    ``run`` is one sr_vsr_trunk_f32 call on a prepared CB8 window."""
+
+    _num_params, _params_name = 'sr_vsr_trunk_num_params', 'ConvResidualBlocks'
+
+    def __init__(self, num_in_ch=3, num_out_ch=64, num_block=15):
+        super().__init__()
+        self.num_in_ch, self.num_out_ch, self.num_block = num_in_ch, num_out_ch, num_block
+        self.main = nn.Sequential(Conv3x3Params(num_in_ch, num_out_ch), nn.LeakyReLU(negative_slope=0.1, inplace=True),
+                                  make_layer(ResidualBlockNoBN, num_block, num_feat=num_out_ch))
+
+    def _param_ends(self):
+        last = self.main[2][-1].conv2.bias if self.num_block > 0 else self.main[0].bias
+        return self.main[0].weight, last
+
+    def cfg(self):
+        segs, rest = divmod(self.num_in_ch - 3, self.num_out_ch)
+        if rest or segs not in (1, 2) or self.num_out_ch % 8:
+            raise ValueError(f'ConvResidualBlocks: the HIP trunk needs num_in_ch = 3 + k * num_out_ch (k = 1, 2) and num_out_ch % 8 == 0, '
+                             f'got {self.num_in_ch} -> {self.num_out_ch}')
+        return _lib.VsrTrunkCfg(self.num_out_ch, self.num_block, segs)
+
+    def packed(self, dev):
+        """(config, blob of weight images) for the current parameters: looked up once per branch, not per step — the weights key
+        walks every parameter of the trunk."""
+        lib, cfg = _lib.load(), self.cfg()
+        with torch.cuda.device(dev):
+            blob = self._blob(('fwd', False), lib, cfg, torch.cuda.current_stream(dev).cuda_stream, 'sr_vsr_trunk_packed_bytes',
+                              'sr_vsr_trunk_pack')
+        return cfg, blob
+
+    def run(self, src, out, packed=None):
+        """``src``: CB8 window [frame block, feature windows]; ``out``: CB8 window of num_out_ch channels; ``packed``: what
+        ``packed(device)`` returned for the current parameters (looked up here when None)."""
+        cfg, blob = packed or self.packed(src.device)
+        return hip_ops.vsr_trunk(cfg, blob, src, out)
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError('ConvResidualBlocks is a parameter container; the video network launches the HIP kernels')
+
+
+@ARCH_REGISTRY.register()
+class BasicVSR(HipGenerator):
+    """A recurrent network for video SR, x4 only.
+
+    Args:
+        num_feat (int): Number of channels (a multiple of 8). Default: 64.
+        num_block (int): Number of residual blocks for each branch. Default: 15.
+        spynet_path (str): Path to the pretrained weights of SpyNet. Default: None.
+    """
+
+    _fuses = True
+
+    def __init__(self, num_feat=64, num_block=15, spynet_path=None):
+        super().__init__()
+        if num_feat <= 0 or num_feat % 8 != 0:
+            raise ValueError(f'BasicVSR: num_feat={num_feat} is not supported; supported: positive multiples of 8 (CB8 activations)')
+        self.num_feat = num_feat
+        # alignment
+        self.spynet = SpyNet(spynet_path)
+        # propagation
+        self.backward_trunk = ConvResidualBlocks(num_feat + 3, num_feat, num_block)
+        self.forward_trunk = ConvResidualBlocks(num_feat + 3, num_feat, num_block)
+        # reconstruction
+        self.fusion = Conv3x3Params(num_feat * 2, num_feat, ksize=1)
+        self.upconv1 = Conv3x3Params(num_feat, num_feat * 4)
+        self.upconv2 = Conv3x3Params(num_feat, 64 * 4)
+        self.conv_hr = Conv3x3Params(64, 64)
+        self.conv_last = Conv3x3Params(64, 3)
+
+    # ------------------------------------------------------------------------------------------------------ refusals
+    def _check(self, x, flows=()):
+        if x.dim() != 5 or x.size(2) != 3:
+            raise ValueError(f'{type(self).__name__}: expected a [b, n, 3, h, w] clip, got {tuple(x.shape)}')
+        if x.dtype != torch.float32 or any(f.dtype != torch.float32 for f in flows):
+            raise ValueError(f'{type(self).__name__}: {x.dtype} input is not supported; supported: fp32')
+        b, n, _, h, w = x.shape
+        if n < 2:
+            raise ValueError(f'{type(self).__name__}: a clip of {n} frame(s) is not supported; at least 2 are needed (the reference fails '
+                             'there too: its get_flow cannot reshape an empty batch)')
+        self._check_frames(n)
+        if b < 1 or min(h, w) <= 32:
+            raise ValueError(f'{type(self).__name__}: a {h}x{w} frame is too small; both sides must exceed 32 pixels (SpyNet)')
+        for f in flows:
+            if tuple(f.shape) != (b, n - 1, 2, h, w):
+                raise ValueError(f'{type(self).__name__}: flows must be [{b}, {n - 1}, 2, {h}, {w}], got {tuple(f.shape)}')
+        if not (x.is_cuda and all(f.is_cuda for f in flows)):
+            raise _lib.SrHipError(f'{type(self).__name__}.forward runs only on a HIP device (no CPU fallback): move the module and '
+                                  'inputs with .to("cuda")')
+        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(f.requires_grad for f in flows)
+                                                          or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(f'{type(self).__name__} runs inference only: call .eval() (or run under torch.no_grad()); '
+                                      'training (SpyNet\'s backward and the recurrent backward) is the follow-up')
+
+    def _check_frames(self, n):
+        """A subclass's own rule on the number of frames."""
+
+    # --------------------------------------------------------------------------------------------------------- flows
+    def get_flow(self, x):
+        """(flows_forward, flows_backward), each [b, n - 1, 2, h, w]: flows_backward[:, i] is SpyNet(x_i, x_{i+1}),
+        flows_forward[:, i] is SpyNet(x_{i+1}, x_i)."""
+        self._check(x)
+        with torch.no_grad():
+            x = x.contiguous()
+            b, n, c, h, w = x.shape
+            x_1 = x[:, :-1].reshape(-1, c, h, w)
+            x_2 = x[:, 1:].reshape(-1, c, h, w)
+            ref, supp = torch.cat([x_1, x_2]), torch.cat([x_2, x_1])
+            # per pair: the six levels' inputs and the widest activations of a level at 32-aligned size, about 1 KiB per pixel
+            hp, wp = -(-h // 32) * 32, -(-w // 32) * 32
+            chunk = max(1, _FLOW_BUDGET // (1024 * hp * wp))
+            flows = torch.cat([self.spynet(ref[s:s + chunk], supp[s:s + chunk]) for s in range(0, ref.size(0), chunk)])
+            pairs = b * (n - 1)
+            return flows[pairs:].view(b, n - 1, 2, h, w), flows[:pairs].view(b, n - 1, 2, h, w)
+
+    # --------------------------------------------------------------------------------------------------- propagation
+    def _branch(self, trunk, x, flows, feats, cb0, order, tin):
+        """One propagation branch over the frames in ``order``: per step one sr_vsr_prop_input_f32 and one sr_vsr_trunk_f32.
+        ``flows[:, j]`` warps the feature of the previous step onto frame ``order[k]``: j = i for the backward branch, i - 1 for
+        the forward branch."""
+        b, fb = x.size(0), self.num_feat // 8
+        frame_out, warp_out = hip_ops.CB8(tin, 0, 1), hip_ops.CB8(tin, 1, fb)
+        prev, packed, src = None, trunk.packed(x.device), hip_ops.CB8(tin)
+        for k, i in enumerate(order):
+            flow = None if prev is None else flows[:, min(i, order[k - 1])]
+            hip_ops.vsr_prop_input(x[:, i], prev, flow, warp_out, frame_out)
+            prev = trunk.run(src, hip_ops.CB8(feats[i * b:(i + 1) * b], cb0, fb), packed)
+
+    def _reconstruct(self, feats, frames, y):
+        """The upsampling head on images [s, e) of the frame-major clip tensors, into y[s:e]."""
+        out = hip_ops.CB8(feats)
+        if self._fuses:     # BasicVSR: fusion 1x1 of [backward, forward]; IconVSR reconstructs from the forward feature alone
+            out = hip_ops.convd(out, self.packed(self.fusion), act_slope=0.1)
+        out = hip_ops.pixel_shuffle(hip_ops.conv3x3(out, self.packed(self.upconv1), act_slope=0.1), self.num_feat, 2)
+        out = hip_ops.pixel_shuffle(hip_ops.conv3x3(out, self.packed(self.upconv2), act_slope=0.1), 64, 2)
+        out = hip_ops.conv3x3(out, self.packed(self.conv_hr), act_slope=0.1)
+        hip_ops.conv3x3(out, self.packed(self.conv_last), out_nchw=y)
+        hip_ops.bilinear_up(frames, 4, out=y)
+
+    def propagate(self, x, flows_forward, flows_backward):
+        """The network after ``get_flow``: x [b, n, 3, h, w], flows [b, n - 1, 2, h, w] -> [b, n, 3, 4h, 4w]."""
+        self._check(x, (flows_forward, flows_backward))
+        with torch.no_grad():
+            x, flows_forward, flows_backward = x.contiguous(), flows_forward.contiguous(), flows_backward.contiguous()
+            b, n, _, h, w = x.shape
+            fb, dev = self.num_feat // 8, x.device
+            feats = torch.empty((n * b, 2 * fb, h, w, 8), dtype=torch.float32, device=dev)
+            tin = torch.empty((b, 1 + fb, h, w, 8), dtype=torch.float32, device=dev)
+            self._branch(self.backward_trunk, x, flows_backward, feats, 0, list(range(n - 1, -1, -1)), tin)
+            self._branch(self.forward_trunk, x, flows_forward, feats, fb, list(range(n)), tin)
+            # reconstruction, frame-major: image i * b + k is frame i of clip k
+            frames = x.transpose(0, 1).reshape(n * b, 3, h, w)
+            y = torch.empty((n * b, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+            # per image: the 4 * num_feat / 256 / 64-channel maps at 2x / 4x size alive around a conv, about 4 maps of 64 x 16 h w floats
+            chunk = max(1, _RECON_BUDGET // (4 * 4 * 64 * 16 * h * w))
+            for s in range(0, n * b, chunk):
+                self._reconstruct(feats[s:s + chunk], frames[s:s + chunk], y[s:s + chunk])
+            return y.view(n, b, 3, 4 * h, 4 * w).transpose(0, 1).contiguous()
+
+    def forward(self, x):
+        return self.propagate(x, *self.get_flow(x))
+
+
+class EDVRFeatureExtractor(nn.Module):
+    """The keyframe branch of IconVSR (the reference's EDVRFeatureExtractor, basicvsr_arch.py:251-309): EDVR up to and including
+    the TSA fusion, on EDVR's fp32 ops table and modules (edvr_arch.py).  ``run(x)`` takes [b, t, 3, h, w] (h, w multiples of 4)
+    and returns the fused features as a raw CB8 tensor [b, num_feat / 8, h, w, 8].  The reference hard-codes 64 channels in its
+    residual blocks, so ``num_feat`` is 64."""
+
+    def __init__(self, num_input_frame, num_feat, load_path):
+        super().__init__()
+        self.center_frame_idx = num_input_frame // 2
+        self.conv_first = Conv3x3Params(3, num_feat)
+        self.feature_extraction = make_layer(ResidualBlockNoBN, 5, num_feat=64)
+        self.conv_l2_1 = Conv3x3Params(num_feat, num_feat)
+        self.conv_l2_2 = Conv3x3Params(num_feat, num_feat)
+        self.conv_l3_1 = Conv3x3Params(num_feat, num_feat)
+        self.conv_l3_2 = Conv3x3Params(num_feat, num_feat)
+        self.pcd_align = PCDAlignment(num_feat=num_feat, deformable_groups=8)
+        self.fusion = TSAFusion(num_feat=num_feat, num_frame=num_input_frame, center_frame_idx=self.center_frame_idx)
+        if load_path:
+            self.load_state_dict(torch.load(load_path, map_location='cpu')['params'])
+
+    def run(self, x):
+        ops = _FP32
+        b, t, c, h, w = x.shape
+        feat_l1 = ops.conv(self.conv_first, ops.enter(x.reshape(b * t, c, h, w)))
+        for blk in self.feature_extraction:
+            feat_l1 = ops.resblock(blk, feat_l1)
+        feat_l2 = ops.conv(self.conv_l2_2, ops.conv_s2(self.conv_l2_1, feat_l1))
+        feat_l3 = ops.conv(self.conv_l3_2, ops.conv_s2(self.conv_l3_1, feat_l2))
+        feat_l = [feat_l1, feat_l2, feat_l3]
+        ref_l = [ops.center_over_t(f, b, t, self.center_frame_idx) for f in feat_l]
+        return self.fusion._layers(ops, self.pcd_align._layers(ops, feat_l, ref_l), b, t)
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError('EDVRFeatureExtractor is run by IconVSR (run(x) on device clips)')
+
+
+@ARCH_REGISTRY.register()
+class IconVSR(BasicVSR):
+    """IconVSR (basicvsr_arch.py:108-248): BasicVSR's propagation with keyframe features from an EDVR extractor fused into both
+    branches at the frames ``range(0, n, keyframe_stride)`` plus the last one, and a forward trunk that also reads the backward
+    branch's feature.  Same constructor, state_dict keys and initialisation order as the reference.
+
+    The per-clip tensor is [n * b, 1 + 2 fb, h, w, 8], frame-major: block 0 the frame, blocks [1, 1 + fb) the backward branch's
+    feature, blocks [1 + fb, 1 + 2 fb) the forward branch's propagated (warped, at keyframes fused) feature — the image IS
+    ``cat([x_i, out_l[i], feat_prop])``, the 136-channel input of the forward trunk.  At a keyframe the step-input launch writes
+    the warped feature in front of the keyframe feature in that keyframe's own two-window buffer, which the fusion conv reads
+    whole.  The input is reflect-padded to multiples of 4 and the output cropped, as the reference.
+
+    ValueError: ``temporal_padding`` not in (2, 3), ``num_feat != 64`` (the reference hard-codes 64 in its extractor), fewer than
+    2 * temporal_padding + 1 frames, and BasicVSR's refusals."""
+
+    _fuses = False
+
+    def __init__(self, num_feat=64, num_block=15, keyframe_stride=5, temporal_padding=2, spynet_path=None, edvr_path=None):
+        HipGenerator.__init__(self)
+        if temporal_padding not in (2, 3):
+            raise ValueError(f'IconVSR: temporal_padding={temporal_padding} is not supported; supported: 2, 3 (the reference builds its '
+                             'mirrored clip for these two only)')
+        if num_feat != 64:
+            raise ValueError(f'IconVSR: num_feat={num_feat} is not supported; supported: 64 (the reference hard-codes 64 channels in '
+                             'its EDVR feature extractor)')
+        if keyframe_stride < 1:
+            raise ValueError(f'IconVSR: keyframe_stride={keyframe_stride} must be at least 1')
+        self.num_feat, self.temporal_padding, self.keyframe_stride = num_feat, temporal_padding, keyframe_stride
+        self.edvr = EDVRFeatureExtractor(temporal_padding * 2 + 1, num_feat, edvr_path)
+        self.spynet = SpyNet(spynet_path)
+        self.backward_fusion = Conv3x3Params(2 * num_feat, num_feat)
+        self.backward_trunk = ConvResidualBlocks(num_feat + 3, num_feat, num_block)
+        self.forward_fusion = Conv3x3Params(2 * num_feat, num_feat)
+        self.forward_trunk = ConvResidualBlocks(2 * num_feat + 3, num_feat, num_block)
+        self.upconv1 = Conv3x3Params(num_feat, num_feat * 4)
+        self.upconv2 = Conv3x3Params(num_feat, 64 * 4)
+        self.conv_hr = Conv3x3Params(64, 64)
+        self.conv_last = Conv3x3Params(64, 3)
+
+    def _check_frames(self, n):
+        need = 2 * self.temporal_padding + 1
+        if n < need:
+            raise ValueError(f'IconVSR: a clip of {n} frames is not supported; temporal_padding={self.temporal_padding} needs at '
+                             f'least {need} (the reference fails there too: its mirrored clip indexes frame {need - 1})')
+
+    def pad_spatial(self, x):
+        """Reflect padding at the bottom and the right to multiples of 4 (PCD alignment needs them)."""
+        b, n, c, h, w = x.shape
+        pad_h, pad_w = (4 - h % 4) % 4, (4 - w % 4) % 4
+        if not (pad_h or pad_w):
+            return x
+        return F.pad(x.reshape(-1, c, h, w), [0, pad_w, 0, pad_h], mode='reflect').view(b, n, c, h + pad_h, w + pad_w)
+
+    def keyframes(self, n):
+        idx = list(range(0, n, self.keyframe_stride))
+        if idx[-1] != n - 1:
+            idx.append(n - 1)
+        return idx
+
+    def get_keyframe_feature(self, x, keyframe_idx):
+        """{i: fused EDVR features of the window around keyframe i} on the (padded) clip x, each a raw CB8 tensor
+        [b, fb, h, w, 8]; the windows come from the reference's mirrored clip."""
+        self._check(x)
+        with torch.no_grad():
+            tp = self.temporal_padding
+            lead, tail = ([4, 3], [-4, -5]) if tp == 2 else ([6, 5, 4], [-5, -6, -7])
+            xm = torch.cat([x[:, lead], x, x[:, tail]], dim=1)
+            return {i: self.edvr.run(xm[:, i:i + 2 * tp + 1].contiguous()) for i in keyframe_idx}
+
+    def propagate(self, x, flows_forward, flows_backward, feats_keyframe=None, crop=None):
+        """The network after ``get_flow`` and ``get_keyframe_feature`` on a clip whose sides are multiples of 4; ``crop`` = (h, w)
+        of the unpadded input."""
+        if x.dim() == 5 and (x.size(3) % 4 or x.size(4) % 4):
+            raise ValueError(f'IconVSR.propagate: the sides must be multiples of 4 (pad_spatial), got {x.size(3)}x{x.size(4)}')
+        self._check(x, (flows_forward, flows_backward))
+        b, n, _, h, w = x.shape
+        with torch.no_grad():
+            x, flows_forward, flows_backward = x.contiguous(), flows_forward.contiguous(), flows_backward.contiguous()
+            keys = self.keyframes(n)
+            if feats_keyframe is None:
+                feats_keyframe = self.get_keyframe_feature(x, keys)
+            fb, dev, CB8 = self.num_feat // 8, x.device, hip_ops.CB8
+            clip = torch.empty((n * b, 1 + 2 * fb, h, w, 8), dtype=torch.float32, device=dev)
+            fwd = torch.empty((n * b, fb, h, w, 8), dtype=torch.float32, device=dev)
+            tin = torch.empty((b, 1 + fb, h, w, 8), dtype=torch.float32, device=dev)
+            pair = {}
+            for i in keys:      # [warped feature | keyframe feature]: what a fusion conv reads
+                pair[i] = torch.empty((b, 2 * fb, h, w, 8), dtype=torch.float32, device=dev)
+                pair[i][:, fb:].copy_(feats_keyframe[i])
+
+            def step(i, prev, flow, fusion, warp_out, frame_out):
+                if i in pair:
+                    hip_ops.vsr_prop_input(x[:, i], prev, flow, CB8(pair[i], 0, fb), frame_out)
+                    hip_ops.conv3x3(CB8(pair[i]), self.packed(fusion), warp_out)
+                else:
+                    hip_ops.vsr_prop_input(x[:, i], prev, flow, warp_out, frame_out)
+
+            prev, packed = None, self.backward_trunk.packed(dev)
+            for i in range(n - 1, -1, -1):
+                step(i, prev, None if prev is None else flows_backward[:, i], self.backward_fusion, CB8(tin, 1, fb), CB8(tin, 0, 1))
+                prev = self.backward_trunk.run(CB8(tin), CB8(clip[i * b:(i + 1) * b], 1, fb), packed)
+            prev, packed = None, self.forward_trunk.packed(dev)
+            for i in range(n):
+                img = clip[i * b:(i + 1) * b]
+                step(i, prev, None if prev is None else flows_forward[:, i - 1], self.forward_fusion, CB8(img, 1 + fb, fb), CB8(img, 0, 1))
+                prev = self.forward_trunk.run(CB8(img), CB8(fwd[i * b:(i + 1) * b]), packed)
+            frames = x.transpose(0, 1).reshape(n * b, 3, h, w)
+            y = torch.empty((n * b, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+            chunk = max(1, _RECON_BUDGET // (4 * 4 * 64 * 16 * h * w))
+            for s in range(0, n * b, chunk):
+                self._reconstruct(fwd[s:s + chunk], frames[s:s + chunk], y[s:s + chunk])
+            y = y.view(n, b, 3, 4 * h, 4 * w).transpose(0, 1)
+            if crop is not None:
+                y = y[..., :4 * crop[0], :4 * crop[1]]
+            return y.contiguous()
+
+    def forward(self, x):
+        self._check(x)
+        h_in, w_in = x.shape[3:]
+        with torch.no_grad():
+            xp = self.pad_spatial(x.contiguous())
+        return self.propagate(xp, *self.get_flow(xp), crop=(h_in, w_in))

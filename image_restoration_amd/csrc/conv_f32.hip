@@ -1071,5 +1071,6 @@ extern "C" const char* sr_kernel_name(int id) {
                                      "avgpool2x2_kernel"};
     return onames[id - 148];
   }
+  if (id == 159) return "vsr_prop_input_kernel";  // vsr_ops.hip (include/sr_hip_vsr.h); 158 stays unnamed
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -8,7 +8,7 @@ clips to use, first word of each line; otherwise every sub-folder of the roots, 
 of a clip) and ``lq_path`` of the centre frame.  ``data_info`` lists the same per frame, as VideoBaseModel.validation reads it.
 
 Deviations: any dataset name is taken (the reference refuses names other than Vid4 / REDS4 / REDSofficial although it treats them
-alike); PIL decodes instead of cv2.  The Vimeo90K, recurrent and DUF test datasets are not built."""
+alike); PIL decodes instead of cv2.  ``VideoRecurrentTestDataset`` below hands out whole folders; the Vimeo90K and DUF test datasets are not built."""
 import logging
 import os
 
@@ -88,3 +88,23 @@ class VideoTestDataset(ImageSource, Dataset):
             gt = self.read_sequence([self.imgs_gt[folder][idx]], 'gt')[0]
         return {'lq': lq, 'gt': gt, 'folder': folder, 'idx': self.data_info['idx'][index],
                 'border': self.data_info['border'][index], 'lq_path': self.data_info['lq_path'][index]}
+
+
+@DATASET_REGISTRY.register()
+class VideoRecurrentTestDataset(VideoTestDataset):
+    """The test set of the recurrent networks (behaviour of basicsr/data/video_test_dataset.py:255-287): an item is a whole
+    folder, ``lq`` [t, c, h, w] and ``gt`` [t, c, 4h, 4w] with ``folder``; ``len`` is the number of folders.  ``padding`` and
+    ``num_frame`` only shape ``data_info`` (``num_frame`` defaults to 1 here).  ``cache_data: true`` only, as the reference."""
+
+    def __init__(self, opt):
+        super().__init__(dict(opt, num_frame=opt.get('num_frame', 1)))
+        self.folders = sorted(set(self.data_info['folder']))
+
+    def __len__(self):
+        return len(self.folders)
+
+    def __getitem__(self, index):
+        if not self.cache_data:
+            raise NotImplementedError('Without cache_data is not implemented.')
+        folder = self.folders[index]
+        return {'lq': self.imgs_lq[folder], 'gt': self.imgs_gt[folder], 'folder': folder}

@@ -1610,3 +1610,75 @@ def avgpool2x2(x):
     out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
     _launch_arg('sr_avgpool2x2_f32', x.device, x.data_ptr(), out.data_ptr(), n * c, h, w)
     return out
+
+
+# ---- the recurrent video networks: propagation step input and trunk driver (include/sr_hip_vsr.h) ----
+
+def vsr_prop_input(frame, prev, flow, warp_out, frame_out=None):
+    """What one propagation step feeds its trunk — one sr_vsr_prop_input_f32 launch.  ``frame``: fp32 [N, 3, H, W] view whose
+    images are dense (``x[:, i]`` of a clip is read in place); ``prev``: CB8 window of the previous propagated feature or None;
+    ``flow``: fp32 [N, 2, H, W] view with dense images (what SpyNet returns), None iff ``prev`` is None.  Writes
+    flow_warp(prev, flow) (zeros for None) into the CB8 window ``warp_out`` and, when given, the frame into the one-block
+    window ``frame_out``."""
+    _need_cuda(frame, 'vsr_prop_input')
+    _arg(frame.dim() == 4 and frame.size(1) == 3 and frame.dtype == torch.float32 and frame.numel() > 0 and frame[0].is_contiguous(),
+         f'vsr_prop_input: needs an fp32 [N, 3, H, W] frame batch with dense images, got {frame.dtype} {tuple(frame.shape)}')
+    n, _, h, w = frame.shape
+    _arg((prev is None) == (flow is None), 'vsr_prop_input: prev and flow come together')
+    _arg(isinstance(warp_out, CB8) and (warp_out.n, warp_out.h, warp_out.w) == (n, h, w), 'vsr_prop_input: warp_out does not fit')
+    d = _lib.VsrPropDesc()
+    d.frame, d.frame_img_stride = frame.data_ptr(), frame.stride(0)
+    if prev is not None:
+        _arg(isinstance(prev, CB8) and (prev.n, prev.h, prev.w, prev.cbn) == (n, h, w, warp_out.cbn), 'vsr_prop_input: prev does not fit')
+        _arg(flow.dtype == torch.float32 and tuple(flow.shape) == (n, 2, h, w) and flow[0].is_contiguous() and flow.device == frame.device,
+             f'vsr_prop_input: flow must be an fp32 [{n}, 2, {h}, {w}] view with dense images, got {flow.dtype} {tuple(flow.shape)}')
+        d.prev, d.prev_img_stride, d.flow, d.flow_img_stride = prev.ptr, prev.img_stride, flow.data_ptr(), flow.stride(0)
+    if frame_out is not None:
+        _arg(isinstance(frame_out, CB8) and (frame_out.n, frame_out.h, frame_out.w, frame_out.cbn) == (n, h, w, 1),
+             'vsr_prop_input: frame_out must be a one-block window')
+        d.frame_out, d.frame_out_img_stride = frame_out.ptr, frame_out.img_stride
+    d.warp_out, d.warp_out_img_stride = warp_out.ptr, warp_out.img_stride
+    d.n, d.h, d.w, d.fb = n, h, w, warp_out.cbn
+    _launch_arg('sr_vsr_prop_input_f32', frame.device, C.byref(d))
+    return warp_out
+
+
+def vsr_trunk_cfg(num_feat, num_block, cin_segs=1):
+    return _lib.VsrTrunkCfg(int(num_feat), int(num_block), int(cin_segs))
+
+
+def vsr_trunk_wino_convs(cfg):
+    """Per conv of a trunk (the first conv, then conv1, conv2 of each block): whether the blob holds a Winograd image for it."""
+    lib = _lib.load()
+    n = lib.sr_vsr_trunk_num_params(C.byref(cfg))
+    _arg(n > 0, f'vsr_trunk: bad config num_feat={cfg.num_feat} num_block={cfg.num_block} cin_segs={cfg.cin_segs}')
+    return [bool(lib.sr_vsr_trunk_conv_wino(C.byref(cfg), i)) for i in range(n // 2)]
+
+
+def vsr_trunk_pack(cfg, params, blob=None):
+    """The packed blob of a trunk from its parameters in state_dict order (device fp32, contiguous) — sr_vsr_trunk_pack_f32."""
+    lib = _lib.load()
+    n = lib.sr_vsr_trunk_num_params(C.byref(cfg))
+    _arg(n > 0 and n == len(params), f'vsr_trunk_pack: {len(params)} parameters, the config has {n}')
+    for p in params:
+        _need_cuda(p, 'vsr_trunk_pack')
+        _arg(p.dtype == torch.float32 and p.is_contiguous(), 'vsr_trunk_pack: parameters must be contiguous fp32')
+    nbytes = lib.sr_vsr_trunk_packed_bytes(C.byref(cfg))
+    if blob is None:
+        blob = torch.empty(nbytes, dtype=torch.uint8, device=params[0].device)
+    _arg(blob.numel() >= nbytes and blob.dtype == torch.uint8, 'vsr_trunk_pack: blob too small')
+    ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in params])
+    _launch_arg('sr_vsr_trunk_pack_f32', blob.device, C.byref(cfg), ptrs, blob.data_ptr())
+    return blob
+
+
+def vsr_trunk(cfg, blob, src, out):
+    """ConvResidualBlocks on the CB8 window ``src`` (frame block + cin_segs feature windows) into the CB8 window ``out`` — one
+    sr_vsr_trunk_f32 call: 1 + 2 * num_block conv launches, no allocation beyond the grow-only scratch."""
+    _arg(isinstance(src, CB8) and isinstance(out, CB8) and src.cbn == 1 + cfg.cin_segs * cfg.num_feat // 8 and out.cbn == cfg.num_feat // 8
+         and (out.n, out.h, out.w) == (src.n, src.h, src.w), 'vsr_trunk: windows do not fit the config')
+    nbytes = _lib.load().sr_vsr_trunk_workspace_bytes(C.byref(cfg), src.n, src.h, src.w)
+    ws = scratch(src.device, nbytes, 'vsr_trunk')
+    _launch_arg('sr_vsr_trunk_f32', src.device, C.byref(cfg), blob.data_ptr(), src.ptr, src.img_stride, out.ptr, out.img_stride, src.n,
+                src.h, src.w, ws.data_ptr(), nbytes)
+    return out

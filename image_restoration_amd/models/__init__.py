@@ -6,6 +6,7 @@ from .srgan_model import SRGANModel  # noqa: F401
 from .esrgan_model import ESRGANModel  # noqa: F401
 from .video_base_model import VideoBaseModel  # noqa: F401
 from .edvr_model import EDVRModel  # noqa: F401
+from .video_recurrent_model import VideoRecurrentModel  # noqa: F401
 
 
 def build_model(opt):

@@ -1,0 +1,231 @@
+// Stand-alone driver for the host-side code of vsr_ops.hip: the argument checks of its entry points, the trunk plan (which convs
+// have a Winograd image, the blob and workspace sizes) and the pack table it builds, run with the host sanitizers on a machine
+// without a GPU.  Every call below returns before anything is launched.  The library services that translation unit uses are
+// stubbed here: the size queries restate the documented sizes closely enough for the plan arithmetic (the real ones are compared
+// in tests/test_vsr_host.py), the pack table runner only inspects the table it is handed.
+//
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//       image_restoration_amd/csrc/vsr_ops.hip tests/helpers/vsr_host_checks.cpp \
+//       -o vsr_host_checks && ./vsr_host_checks
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+#include "../../image_restoration_amd/csrc/sr_internal.h"
+#include "../../include/sr_hip_vsr.h"
+
+static char g_err[512];
+static size_t g_rows = 0, g_wino_rows = 0, g_image_bytes = 0;
+static bool g_rows_inside = true;
+namespace sr {
+void set_error(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
+}
+bool prof_on() { return false; }
+void prof_begin(hipStream_t, const sr_launch_record&) {}
+void prof_end(hipStream_t) {}
+int wino_f32_mode() { return 1; }
+bool wino_f32_weights_eligible(int cout, int cin) { return cin >= 8 && cout > 0 && cout % 32 == 0; }
+size_t wino_f32_image_floats(int cout, int cin_pad) { return (size_t)cout * cin_pad * 16; }
+int conv3x3_wino_f32(const sr_conv3x3_desc*, const float*, hipStream_t, bool) { return SR_ELAUNCH; }  // never reached
+size_t pack_table_bytes(size_t entries) { return align_up((entries + 1) * sizeof(PackEntry), 256); }
+int pack_table_run(std::vector<PackEntry>& entries, void* blob, size_t image_bytes, bool, hipStream_t) {
+  g_rows = entries.size();
+  g_wino_rows = 0;
+  g_image_bytes = image_bytes;
+  g_rows_inside = true;
+  for (const PackEntry& e : entries) {  // every image starts inside [blob, blob + image_bytes)
+    if (e.kind == 3) ++g_wino_rows;
+    if ((char*)e.out < (char*)blob || (char*)e.out >= (char*)blob + image_bytes) g_rows_inside = false;
+    if (e.kind == 0 && ((char*)e.bout < (char*)blob || (char*)e.bout >= (char*)blob + image_bytes)) g_rows_inside = false;
+  }
+  return SR_OK;
+}
+}  // namespace sr
+extern "C" int sr_conv3x3_cin_pad(int cin, int first_seg, int seg) {
+  if (seg <= 0) return cin == first_seg ? (cin + 7) / 8 * 8 : -1;
+  if (cin < first_seg || (cin - first_seg) % seg) return -1;
+  return (first_seg + 7) / 8 * 8 + (cin - first_seg) / seg * ((seg + 7) / 8 * 8);
+}
+extern "C" size_t sr_conv3x3_packed_weight_floats(int cout, int cin_pad) { return (size_t)((cout + 31) / 32 * 32) * cin_pad * 9; }
+extern "C" size_t sr_conv3x3_packed_bias_floats(int cout) { return (size_t)((cout + 31) / 32 * 32); }
+extern "C" int sr_conv3x3_f32(const sr_conv3x3_desc*, void*) { return SR_ELAUNCH; }  // never reached
+
+static int failures = 0;
+static int checks = 0;
+// the call must be refused with `code` and a message that names the entry point and contains `needle`
+#define REFUSED_AS(call, code, name, needle)                                                            \
+  do {                                                                                                  \
+    g_err[0] = 0;                                                                                       \
+    ++checks;                                                                                           \
+    const int rc__ = (call);                                                                            \
+    if (rc__ != (code) || !strstr(g_err, name) || !strstr(g_err, needle)) {                             \
+      printf("FAILED line %d: %s -> %d (last error: %s)\n", __LINE__, #call, rc__, g_err);              \
+      ++failures;                                                                                       \
+    }                                                                                                   \
+  } while (0)
+#define REFUSED(call, name, needle) REFUSED_AS(call, SR_EINVAL, name, needle)
+#define EXPECT(cond)                                    \
+  do {                                                  \
+    ++checks;                                           \
+    if (!(cond)) {                                      \
+      printf("FAILED line %d: %s\n", __LINE__, #cond);  \
+      ++failures;                                       \
+    }                                                   \
+  } while (0)
+
+static float* const P = (float*)256;
+static float* const Q = (float*)4096;
+static float* const ODD = (float*)260;  // 4-byte aligned only
+
+static sr_vsr_prop_desc good() {
+  sr_vsr_prop_desc d = {};
+  d.frame = ODD;
+  d.frame_img_stride = 3 * 20;
+  d.prev = P;
+  d.prev_img_stride = 8 * 20 * 4;
+  d.flow = ODD;
+  d.flow_img_stride = 2 * 20;
+  d.frame_out = Q;
+  d.frame_out_img_stride = 8 * 20 * 3;
+  d.warp_out = Q + 8 * 20;
+  d.warp_out_img_stride = 8 * 20 * 3;
+  d.n = 2;
+  d.h = 4;
+  d.w = 5;
+  d.fb = 2;
+  return d;
+}
+
+int main() {
+  const char* PI = "sr_vsr_prop_input_f32";
+  REFUSED(sr_vsr_prop_input_f32(nullptr, nullptr), PI, "null descriptor");
+  sr_vsr_prop_desc d = good();
+  d.frame = nullptr;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "null frame");
+  d = good();
+  d.warp_out = nullptr;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "null frame");
+  d = good();
+  d.flow = nullptr;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "both");
+  d = good();
+  d.prev = nullptr;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "both");
+  for (int which = 0; which < 6; ++which) {
+    d = good();
+    (which == 0 ? d.n : which == 1 ? d.h : which == 2 ? d.w : d.fb) = which < 4 ? 0 : which == 4 ? 65535 : -3;
+    REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "bad shape");
+  }
+  d = good();
+  d.n = 65536;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "bad shape");
+  d = good();
+  d.h = 1 << 14;
+  d.w = 1 << 14;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "too large");
+  d = good();
+  d.prev = ODD;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "16-byte aligned");
+  d = good();
+  d.frame_out = ODD;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "16-byte aligned");
+  d = good();
+  d.warp_out = ODD;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "16-byte aligned");
+  d = good();
+  d.frame = (float*)258;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "4-byte aligned");
+  d = good();
+  d.flow = (float*)257;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "4-byte aligned");
+  d = good();
+  d.prev_img_stride += 2;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "multiples of 4");
+  d = good();
+  d.warp_out_img_stride += 1;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "multiples of 4");
+  d = good();
+  d.frame_img_stride = 3 * 20 - 1;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "smaller than the image");
+  d = good();
+  d.flow_img_stride = 2 * 20 - 1;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "smaller than the image");
+  d = good();
+  d.prev_img_stride = 8 * 20 * 2 - 4;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "smaller than the image");
+  d = good();
+  d.warp_out_img_stride = 8 * 20;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "smaller than the image");
+  d = good();
+  d.frame_out_img_stride = 8 * 20 - 4;
+  REFUSED(sr_vsr_prop_input_f32(&d, nullptr), PI, "smaller than the image");
+
+  // ---- trunk configs and plans
+  const sr_vsr_trunk_cfg bad[] = {{0, 1, 1}, {-8, 1, 1}, {20, 1, 1}, {64, -1, 1}, {64, 1, 0}, {64, 1, 3}, {8192, 1, 1}, {64, 5000, 1}};
+  for (const sr_vsr_trunk_cfg& c : bad) {
+    REFUSED(sr_vsr_trunk_num_params(&c), "sr_vsr_trunk_num_params", "bad config");
+    REFUSED(sr_vsr_trunk_conv_wino(&c, 0), "sr_vsr_trunk_conv_wino", "bad config");
+    REFUSED(sr_vsr_trunk_pack_f32(&c, (const float* const*)P, Q, nullptr), "sr_vsr_trunk_pack_f32", "bad config");
+    REFUSED(sr_vsr_trunk_f32(&c, P, P, 0, Q, 0, 1, 8, 8, nullptr, 0, nullptr), "sr_vsr_trunk_f32", "bad config");
+    EXPECT(sr_vsr_trunk_packed_bytes(&c) == 0);
+    EXPECT(sr_vsr_trunk_workspace_bytes(&c, 1, 8, 8) == 0);
+  }
+  REFUSED(sr_vsr_trunk_num_params(nullptr), "sr_vsr_trunk_num_params", "bad config");
+  EXPECT(sr_vsr_trunk_packed_bytes(nullptr) == 0);
+  const int feats[] = {64, 32, 24, 8};
+  for (int nf : feats)
+    for (int segs = 1; segs <= 2; ++segs)
+      for (int nb = 0; nb <= 30; nb += 15) {
+        const sr_vsr_trunk_cfg c = {nf, nb, segs};
+        const int convs = 1 + 2 * nb;
+        EXPECT(sr_vsr_trunk_num_params(&c) == 2 * convs);
+        int wino = 0;
+        for (int i = 0; i < convs; ++i) wino += sr_vsr_trunk_conv_wino(&c, i);
+        EXPECT(wino == (nf % 32 == 0 ? convs : 0));
+        REFUSED(sr_vsr_trunk_conv_wino(&c, convs), "sr_vsr_trunk_conv_wino", "conv");
+        REFUSED(sr_vsr_trunk_conv_wino(&c, -1), "sr_vsr_trunk_conv_wino", "conv");
+        const size_t bytes = sr_vsr_trunk_packed_bytes(&c);
+        EXPECT(bytes > 0 && bytes % 256 == 0);
+        EXPECT(sr_vsr_trunk_workspace_bytes(&c, 2, 13, 37) == 3 * sr::align_up((size_t)2 * nf * 13 * 37 * 4, 256));
+        EXPECT(sr_vsr_trunk_workspace_bytes(&c, 0, 13, 37) == 0 && sr_vsr_trunk_workspace_bytes(&c, 1, -1, 37) == 0);
+        // the pack table: one row per conv and one per Winograd image, every image inside the blob
+        std::vector<const float*> params(2 * convs, P);
+        EXPECT(sr_vsr_trunk_pack_f32(&c, params.data(), (float*)(uintptr_t)(1 << 20), nullptr) == SR_OK);
+        EXPECT(g_rows == (size_t)(convs + wino) && g_wino_rows == (size_t)wino && g_rows_inside);
+        EXPECT(g_image_bytes + sr::pack_table_bytes(g_rows) == bytes);
+        params[2 * convs - 1] = nullptr;
+        REFUSED(sr_vsr_trunk_pack_f32(&c, params.data(), (float*)(uintptr_t)(1 << 20), nullptr), "sr_vsr_trunk_pack_f32", "null parameter");
+      }
+  const sr_vsr_trunk_cfg c = {64, 2, 1};
+  const float* two[10] = {P, P, P, P, P, P, P, P, P, P};
+  REFUSED(sr_vsr_trunk_pack_f32(&c, nullptr, Q, nullptr), "sr_vsr_trunk_pack_f32", "null argument");
+  REFUSED(sr_vsr_trunk_pack_f32(&c, two, nullptr, nullptr), "sr_vsr_trunk_pack_f32", "null argument");
+  REFUSED(sr_vsr_trunk_pack_f32(&c, two, ODD, nullptr), "sr_vsr_trunk_pack_f32", "256-byte aligned");
+
+  const char* TR = "sr_vsr_trunk_f32";
+  void* const WS = (void*)(uintptr_t)(1 << 20);
+  const size_t need = sr_vsr_trunk_workspace_bytes(&c, 2, 8, 8);
+  const long long in_ns = 72 * 64, out_ns = 64 * 64;
+  REFUSED(sr_vsr_trunk_f32(&c, nullptr, P, in_ns, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_vsr_trunk_f32(&c, P, nullptr, in_ns, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns, nullptr, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns, 0, 8, 8, WS, need, nullptr), TR, "bad shape");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns, 2, 8, -8, WS, need, nullptr), TR, "bad shape");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns, 1, 4096, 4096, WS, need, nullptr), TR, "too large");
+  REFUSED(sr_vsr_trunk_f32(&c, ODD, P, in_ns, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_vsr_trunk_f32(&c, P, ODD, in_ns, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns, ODD, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns, 2, 8, 8, (char*)WS + 16, need, nullptr), TR, "aligned");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns + 2, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "multiples of 4");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns - 8, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "smaller than the image");
+  REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns - 8, 2, 8, 8, WS, need, nullptr), TR, "smaller than the image");
+  REFUSED_AS(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns, 2, 8, 8, WS, need - 1, nullptr), SR_ENOSPACE, TR, "workspace");
+  REFUSED_AS(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns, 2, 8, 8, nullptr, need, nullptr), SR_ENOSPACE, TR, "workspace");
+
+  printf("vsr_host_checks: %d checks, %d failures\n", checks, failures);
+  return failures ? 1 : 0;
+}

@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""Times BasicVSR inference (archs/basicvsr_arch.py) on one GPU, in the manner of tools/spynet_bench.py.
+
+    python tools/basicvsr_bench.py [--num-block 30] [--reps 20] [--warmup 5] [--out results.json]
+
+Cases: one 180x320 clip of 15 frames, and one 64x112 clip of 7 frames (below the Winograd size rule: the trunks run on the direct
+kernels).  Three variants on the same parameters and input, the launch profiler off, each forward timed with device events;
+the variants alternate forward by forward in one process (--warmup rounds, then --reps rounds), the median over the rounds is
+reported:
+
+    product     the network as shipped: sr_vsr_prop_input_f32 + sr_vsr_trunk_f32 per step
+    per-layer   the same forward (the same step-input launch, the same windows) with every trunk conv issued through
+                hip_ops.conv3x3 from Python (written in this tool only); with --wino-off both variants run the direct kernels, so
+                the difference is the cost of issuing the convs from Python alone
+    torch       the same network from its definition in PyTorch-ROCm ops: nn.Conv2d, F.grid_sample, F.pixel_shuffle, F.interpolate
+                (written in this tool only; its SpyNet is tools/spynet_bench.py's)
+
+Also: one trunk call alone on one frame (ms, TFLOP/s on the algorithmic 2 * 9 * cin * cout FLOP per pixel, fraction of the 157.3
+TFLOP/s fp32 MFMA peak) and sr_vsr_prop_input_f32 alone (ms and bytes/s on 32 bytes per corner, pixel and block, plus the store,
+the frame and the flow), both from device events around 50 back-to-back calls.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from image_restoration_amd import hip_ops as H  # noqa: E402
+from image_restoration_amd.archs.basicvsr_arch import BasicVSR  # noqa: E402
+from spynet_bench import TorchSpyNet, timed, torch_warp  # noqa: E402
+
+PEAK_TFLOPS = 157.3
+
+
+def per_layer_trunk(net, trunk, src, out):
+    """ConvResidualBlocks with every conv issued through hip_ops.conv3x3; the last one writes the window ``out``."""
+    first = H.cached_pack('bench first', trunk.main[0].weight, trunk.main[0].bias,
+                          lambda: H.PackedConv(trunk.main[0].weight, trunk.main[0].bias, first_seg=3, seg=net.num_feat))
+    blocks = list(trunk.main[2])
+    x = H.conv3x3(src, first, out if not blocks else None, act_slope=0.1)
+    for k, blk in enumerate(blocks):
+        t = H.conv3x3(x, net.packed(blk.conv1), act_slope=0.0)
+        x = H.conv3x3(t, net.packed(blk.conv2), out if k + 1 == len(blocks) else None, res1=x, beta1=1.0)
+    return x
+
+
+def per_layer_forward(net, x):
+    """BasicVSR.forward as shipped (sr_vsr_prop_input_f32, windows of the per-clip tensor, the same reconstruction) except that
+    every trunk conv is issued from Python through hip_ops.conv3x3: only how the convs are issued differs from the product."""
+    ff, fb = net.get_flow(x)
+    b, n, _, h, w = x.shape
+    fbk = net.num_feat // 8
+    feats = torch.empty((n * b, 2 * fbk, h, w, 8), device=x.device)
+    tin = torch.empty((b, 1 + fbk, h, w, 8), device=x.device)
+    frame_out, warp_out, src = H.CB8(tin, 0, 1), H.CB8(tin, 1, fbk), H.CB8(tin)
+    for trunk, flows, cb0, order in ((net.backward_trunk, fb, 0, range(n - 1, -1, -1)), (net.forward_trunk, ff, fbk, range(n))):
+        prev, last = None, None
+        for i in order:
+            H.vsr_prop_input(x[:, i], prev, None if prev is None else flows[:, min(i, last)], warp_out, frame_out)
+            prev, last = per_layer_trunk(net, trunk, src, H.CB8(feats[i * b:(i + 1) * b], cb0, fbk)), i
+    frames = x.transpose(0, 1).reshape(n * b, 3, h, w)
+    y = torch.empty((n * b, 3, 4 * h, 4 * w), device=x.device)
+    net._reconstruct(feats, frames, y)
+    return y.view(n, b, 3, 4 * h, 4 * w).transpose(0, 1)
+
+
+class TorchBasicVSR(nn.Module):
+    """The same network as plain PyTorch modules, sharing the HIP network's parameters."""
+
+    def __init__(self, net):
+        super().__init__()
+        self.num_feat = net.num_feat
+        self.spynet = TorchSpyNet(net.spynet)
+
+        def conv(p, k=3):
+            c = nn.Conv2d(p.in_channels, p.out_channels, k, 1, k // 2)
+            c.weight, c.bias = p.weight, p.bias
+            return c
+
+        def trunk(t):
+            return conv(t.main[0]), nn.ModuleList(nn.ModuleList([conv(blk.conv1), conv(blk.conv2)]) for blk in t.main[2])
+        self.b_first, self.b_blocks = trunk(net.backward_trunk)
+        self.f_first, self.f_blocks = trunk(net.forward_trunk)
+        self.fusion, self.upconv1, self.upconv2 = conv(net.fusion, 1), conv(net.upconv1), conv(net.upconv2)
+        self.conv_hr, self.conv_last = conv(net.conv_hr), conv(net.conv_last)
+
+    @staticmethod
+    def run_trunk(first, blocks, x):
+        x = F.leaky_relu(first(x), 0.1)
+        for c1, c2 in blocks:
+            x = x + c2(F.relu(c1(x)))
+        return x
+
+    def forward(self, x):
+        b, n, c, h, w = x.shape
+        x_1, x_2 = x[:, :-1].reshape(-1, c, h, w), x[:, 1:].reshape(-1, c, h, w)
+        fb = self.spynet(x_1, x_2).view(b, n - 1, 2, h, w)
+        ff = self.spynet(x_2, x_1).view(b, n - 1, 2, h, w)
+        out_l, feat = [None] * n, x.new_zeros(b, self.num_feat, h, w)
+        for i in range(n - 1, -1, -1):
+            if i < n - 1:
+                feat = torch_warp(feat, fb[:, i].permute(0, 2, 3, 1), 'zeros')
+            feat = self.run_trunk(self.b_first, self.b_blocks, torch.cat([x[:, i], feat], 1))
+            out_l[i] = feat
+        feat = torch.zeros_like(feat)
+        for i in range(n):
+            if i > 0:
+                feat = torch_warp(feat, ff[:, i - 1].permute(0, 2, 3, 1), 'zeros')
+            feat = self.run_trunk(self.f_first, self.f_blocks, torch.cat([x[:, i], feat], 1))
+            out = F.leaky_relu(self.fusion(torch.cat([out_l[i], feat], 1)), 0.1)
+            out = F.leaky_relu(F.pixel_shuffle(self.upconv1(out), 2), 0.1)
+            out = F.leaky_relu(F.pixel_shuffle(self.upconv2(out), 2), 0.1)
+            out = self.conv_last(F.leaky_relu(self.conv_hr(out), 0.1))
+            out_l[i] = out + F.interpolate(x[:, i], scale_factor=4, mode='bilinear', align_corners=False)
+        return torch.stack(out_l, 1)
+
+
+def burst(fn, calls=50):
+    """Milliseconds per call of ``calls`` back-to-back calls between two device events (after a few warm-up calls)."""
+    for _ in range(5):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--num-block', type=int, default=30)
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--wino-off', action='store_true', help='sr_dev_set_wino_f32(0): the product path on the direct kernels too')
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('basicvsr_bench needs a GPU: timings are device timings')
+    dev = torch.device('cuda:0')
+    if args.wino_off:
+        from image_restoration_amd import _lib
+        _lib.load().sr_dev_set_wino_f32(0)
+    torch.manual_seed(0)
+    net = BasicVSR(num_feat=64, num_block=args.num_block).to(dev).eval()
+    ref = TorchBasicVSR(net).to(dev).eval()
+    nf, nb = 64, args.num_block
+    rows = []
+    with torch.no_grad():
+        for n, h, w in ((15, 180, 320), (7, 64, 112)):
+            x = torch.rand(1, n, 3, h, w, device=dev)
+            y = net(x)
+            d_layer, d_torch = float((per_layer_forward(net, x) - y).abs().max()), float((ref(x) - y).abs().max())
+            variants = (('product', lambda: net(x)), ('per-layer', lambda: per_layer_forward(net, x)), ('torch', lambda: ref(x)))
+            # interleaved at the level of single forwards: a round runs every variant once; median over the rounds
+            for _ in range(args.warmup):
+                for _, fn in variants:
+                    fn()
+            ms = {k: [] for k, _ in variants}
+            for _ in range(args.reps):
+                for k, fn in variants:
+                    ms[k].append(timed(fn, 1, 0))
+            r = dict(case=f'{n} frames {h}x{w}', frames=n, max_abs_diff_per_layer=d_layer, max_abs_diff_torch=d_torch)
+            for k, _ in variants:
+                r[k + '_ms'] = statistics.median(ms[k])
+                r[k + '_ms_per_frame'] = statistics.median(ms[k]) / n
+            # one trunk call and one step input alone
+            tin = torch.randn(1, 9, h, w, 8, device=dev)
+            tin[:, 0, :, :, 3:] = 0
+            out = H.CB8.empty(1, nf, h, w, dev)
+            t_trunk = burst(lambda: net.forward_trunk.run(H.CB8(tin), out))
+            flops = 2.0 * 9 * h * w * nf * ((3 + nf) + 2 * nb * nf)
+            prev, flow = H.CB8(torch.randn(1, 8, h, w, 8, device=dev)), torch.randn(1, 2, h, w, device=dev) * 4
+            t_prop = burst(lambda: H.vsr_prop_input(x[:, 0], prev, flow, H.CB8(tin, 1, 8), H.CB8(tin, 0, 1)))
+            nbytes = 4.0 * h * w * (5 * nf + 2 + 3 + 8)
+            r.update(trunk_ms=t_trunk, trunk_tflops=flops / t_trunk / 1e9, trunk_of_peak=flops / t_trunk / 1e9 / PEAK_TFLOPS,
+                     trunk_launches=1 + 2 * nb, prop_input_ms=t_prop, prop_input_gbytes_per_s=nbytes / t_prop / 1e6)
+            rows.append(r)
+    for r in rows:
+        print(f'{r["case"]}: product {r["product_ms"]:.2f} ms ({r["product_ms_per_frame"]:.2f} / frame), per-layer '
+              f'{r["per-layer_ms"]:.2f} ms ({r["per-layer_ms_per_frame"]:.2f}), torch {r["torch_ms"]:.2f} ms ({r["torch_ms_per_frame"]:.2f}); '
+              f'max|diff| per-layer {r["max_abs_diff_per_layer"]:.2e} torch {r["max_abs_diff_torch"]:.2e}')
+        print(f'    trunk call ({r["trunk_launches"]} launches) {r["trunk_ms"]:.3f} ms = {r["trunk_tflops"]:.1f} TFLOP/s '
+              f'({r["trunk_of_peak"]:.2f} of peak); prop input {1000 * r["prop_input_ms"]:.1f} us = {r["prop_input_gbytes_per_s"]:.0f} GB/s')
+    if args.out:
+        with open(args.out, 'w') as f:
+            json.dump(dict(num_block=nb, wino_off=args.wino_off, reps=args.reps, warmup=args.warmup, peak_tflops=PEAK_TFLOPS, rows=rows), f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
