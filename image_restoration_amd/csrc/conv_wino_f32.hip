@@ -23,8 +23,9 @@
 // Per chunk a lane (patch j, half h) reads the three raw rows its two transform rows need (d0 d1 d2 low, d1 d2 d3 high), four
 // columns of channels 4h..4h+3 (12 ds_read_b128), forms its 8 values of V = B^T d B in registers and issues 8 points x 4 K=2
 // steps = 32 MFMAs on its 8 U planes.  Behind the last chunk the column step of the output transform is per wave; the row step
-// needs one transform row of the other half, exchanged once per tile through the then-dead X buffers.  Low stores output row
-// dy = 0 of its patch row, high dy = 1.
+// needs one transform row of the other half, exchanged once per tile through the then-dead U buffers (NW = 4: X buffers).  Low
+// stores output row dy = 0 of its patch row, high dy = 1.  Residual 1 of the tile is brought into the X buffers by LDS-DMA under the
+// MFMAs of the last chunk (NW = 2, 1; two chunks or more), so that the epilogue reads it from the LDS, not by dependent global loads.
 //
 // Patches are anchored at EVEN image coordinates, chunks ascend, the order inside a chunk and every expression tree are fixed and
 // every variant (NW = 4, 2, 1) runs the same wave code: an output value depends on its image and its position only — not on tile
@@ -54,6 +55,7 @@ struct WinoParams {
   int tiles_x, tiles_y;
   int src_shift;
   int res_cb1;
+  int res_stage;  // residual 1 through the LDS (sr_dev_set_wino_res_stage)
   float slope, alpha, beta1, beta2;
 #ifdef SR_WINO_STAMP
   unsigned long long* stamps;  // diagnostic build only (tools/wino_phase.py): [workgroup][8] s_memtime values
@@ -61,7 +63,8 @@ struct WinoParams {
 };
 
 // Phase stamps of the diagnostic build (`make stamp`: its own library, never the product's): one lane per workgroup writes the clock
-// at entry, behind the first barrier, behind the last chunk's barrier, behind the exchange and behind its last store.
+// at entry, behind the first barrier, behind the last chunk's barrier, behind the exchange and behind its last store (0-4), and at
+// the head of the last chunk (5).
 #ifdef SR_WINO_STAMP
 #define WINO_STAMP(k)                                                                                               \
   do {                                                                                                              \
@@ -94,7 +97,14 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   constexpr int XBYTES = wino_x_bytes<NW>();
   constexpr int NXU = (XPIX * 32 + 1023) / 1024, NWU = 16;  // 1 KiB pieces of one X chunk / one U chunk
   constexpr int NXR = (NXU + NV - 1) / NV, NWR = NWU / NV;  // per wave; the last X round is guarded (piece < NXU)
-  static_assert(NV * 8192 <= 3 * XBYTES, "the exchange of the output transform lives in the X buffers");
+  // Behind the last chunk's barrier both U buffers are dead: at NW = 2, 1 the exchange of the output transform (8 KiB per wave) lives
+  // there, and the X region holds residual 1 of the output tile (2 NW rows x 4 channel blocks x 2 KiB).  At NW = 4 the exchange does
+  // not fit the U region: it stays in the X buffers and the residual stays a global load.
+  constexpr bool RES_LDS = NW <= 2;
+  constexpr int XCH = RES_LDS ? 3 * XBYTES : 0;  // byte offset of the exchange
+  static_assert(RES_LDS ? NV * 8192 <= 2 * NWU * 1024 : NV * 8192 <= 3 * XBYTES,
+                "the exchange of the output transform lives in the U buffers (NW = 2, 1) or in the X buffers (NW = 4)");
+  static_assert(!RES_LDS || NW * 16384 <= 3 * XBYTES, "the staged residual tile lives in the X buffers");
 
   // XCD-aware tile order (as conv_f32_kernel): each XCD gets a contiguous run of tiles
   int t;
@@ -163,6 +173,28 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
     }
   };
 
+  // Residual 1 of the workgroup's own output tile: wave w moves tile row w, 8 pieces of 1 KiB = 32 pixels of one channel-block plane
+  // (eight whole 128-byte lines), to LDS byte (row * 4 + g) * 2048 + pixel * 32 with the two 16-byte halves of a pixel swapped when
+  // bit 3 of the pixel is set (the epilogue's lanes stride 64 B, as the readers of X do).  Rows >= H, pixels >= W and planes that carry
+  // no residual get an out-of-range offset.
+  auto stage_res = [&]() {
+    const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(p.res1 + (long long)n * p.res1_ns), 0, (unsigned)((long long)min(p.cout_blocks, p.res_cb1) * p.H * p.W * 32), 0x00020000);
+    const int gy = y0 + wave, pp = lane >> 1;
+    const int hsw = (lane & 1) ^ ((pp >> 3) & 1);
+#pragma unroll
+    for (int hp = 0; hp < 2; ++hp) {
+      const int gx = x0 + hp * 32 + pp;
+      const unsigned vo = (gy < p.H && gx < p.W) ? (unsigned)((gy * p.W + gx) * 8 + hsw * 4) * 4u : 0xfffffff0u;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int cb = cog * 4 + g;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r_rs, (__attribute__((address_space(3))) void*)(smem + ((wave * 4 + g) * 2 + hp) * 1024), 16,
+                                                 cb < p.res_cb1 ? vo : 0xfffffff0u, (unsigned)cb * (unsigned)(p.H * p.W) * 32u, 0, 0);
+      }
+    }
+  };
+
   f32x16 acc[8];  // points 8 HF .. 8 HF + 7
 #pragma unroll
   for (int a = 0; a < 8; ++a)
@@ -203,6 +235,8 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   };
 
   const int nchunk = p.cin_blocks;
+  // With one chunk rows(0) is not separated from the chunk by a barrier (another wave may still read X buffer 0): no staging then
+  const bool res_lds = RES_LDS && p.res_stage && p.res1 != nullptr && nchunk >= 2;
   stage_x(0, 0);
   stage_u(0, 0);
   if (nchunk > 1) stage_x(1, 1);
@@ -213,9 +247,12 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   for (int r = 0; r < 2; ++r) cols(r);
   int xb2 = 2 % 3, xb1 = 1;  // X buffers of chunks c + 2 and c + 1
   // one chunk; MORE / MORE2: chunks c + 1 / c + 2 exist (compile-time, so that the body is one straight line the scheduler can
-  // interleave: the last two chunks are peeled)
-  auto chunk = [&](int c, auto more_t, auto more2_t) {
-    constexpr bool more = decltype(more_t)::value, more2 = decltype(more2_t)::value;
+  // interleave: the last two chunks are peeled).  RES: the last chunk of a tile whose residual goes through the LDS.  No wave reads a
+  // raw row in it (the rows of chunk nchunk - 1 were read before the barrier of chunk nchunk - 2), it stages neither X nor U, and no
+  // LDS read follows the staging point, so the pieces land under its MFMAs and its barrier drains them
+  auto chunk = [&](int c, auto more_t, auto more2_t, auto res_t) {
+    constexpr bool more = decltype(more_t)::value, more2 = decltype(more2_t)::value, res = decltype(res_t)::value;
+    static_assert(!res || (!more && RES_LDS), "the residual is staged in the last chunk only");
     const char* us = smem + 3 * XBYTES + (c & 1) * (NWU * 1024) + ulane;
     f32x4 a[2][4];  // U operands, read one group ahead
 #pragma unroll
@@ -227,6 +264,9 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
         for (int q = 0; q < 4; ++q) a[1][q] = *(const f32x4*)(us + (4 + q) * 1024);
         if constexpr (more2) stage_x(xb2, c + 2);
         if constexpr (more) stage_u((c + 1) & 1, c + 1);
+        if constexpr (res) {
+          if (res_lds) stage_res();
+        }
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s)
@@ -248,9 +288,10 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   };
   using yes = std::true_type;
   using no = std::false_type;
-  for (int c = 0; c + 2 < nchunk; ++c) chunk(c, yes{}, yes{});
-  if (nchunk > 1) chunk(nchunk - 2, yes{}, no{});
-  chunk(nchunk - 1, no{}, no{});
+  for (int c = 0; c + 2 < nchunk; ++c) chunk(c, yes{}, yes{}, no{});
+  if (nchunk > 1) chunk(nchunk - 2, yes{}, no{}, no{});
+  WINO_STAMP(5);
+  chunk(nchunk - 1, no{}, no{}, std::integral_constant<bool, RES_LDS>{});
   WINO_STAMP(2);
 
   // ---- output transform Y = A^T (M A), A^T = [1 1 1 0; 0 1 -1 -1]: columns first (per transform row: inside the wave), then rows,
@@ -262,12 +303,12 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
     ra[r][1] = (acc[r * 4 + 1] - acc[r * 4 + 2]) - acc[r * 4 + 3];
   }
 
-  // the row step needs one transform row of the other half: high sends row 2 to low, low sends row 1 to high, through the X buffers
-  // (dead behind the last chunk's barrier), 8 KiB per wave, each 16-byte store and load contiguous over the lanes
+  // the row step needs one transform row of the other half: high sends row 2 to low, low sends row 1 to high, through the U buffers
+  // (NW = 4: X buffers; dead behind the last chunk's barrier), 8 KiB per wave, each 16-byte store and load contiguous over the lanes
   f32x16 yv[2];  // [dx]
   {
-    char* mine = smem + wave * 8192 + lane * 16;
-    const char* theirs = smem + (HF ? wave - NW : wave + NW) * 8192 + lane * 16;
+    char* mine = smem + XCH + wave * 8192 + lane * 16;
+    const char* theirs = smem + XCH + (HF ? wave - NW : wave + NW) * 8192 + lane * 16;
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -295,30 +336,70 @@ __device__ __forceinline__ void conv_wino_tile_f32(const WinoParams p, char* sme
   WINO_STAMP(3);
 
   // ---- epilogue (that of conv_tile_f32): bias, LeakyReLU, alpha, residual scale-adds, 16-byte CB8 stores.  This half's output row
-  // is dy = HF
+  // is dy = HF.  STAGED: residual 1 comes from the tile stage_res() brought in (same value, same expression), and the loads of
+  // residual 2 (one conv5 in three has it; there is no room for a second tile) are all issued in front of the first store: they may
+  // alias the destination, so the compiler keeps each behind the store before it otherwise.  A lane loads only what it stores itself.
+  // The accumulators are dead here: the 32 registers are free
   const long long HW = (long long)p.H * p.W;
   const int y = y0 + 2 * prow + HF;
+  const int rlane = (2 * prow + HF) * 8192 + j * 64 + ((h ^ ((j >> 2) & 1)) * 16);
+  auto epilogue = [&](auto staged_t) {
+    constexpr bool staged = decltype(staged_t)::value;
+    f32x4 bv[4];  // read once in front of the stores: a load behind a store waits for the store with it (one counter)
+    if (p.bias) {
 #pragma unroll
-  for (int dx = 0; dx < 2; ++dx) {
-    const int x = x0 + 2 * j + dx;
-    if (y >= p.H || x >= p.W) continue;
-    const long long pixoff = (long long)y * p.W + x;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int cb = cog * 4 + g;
-      if (cb >= p.cout_blocks) continue;
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = yv[dx][g * 4 + e];
-      const long long off = (cb * HW + pixoff) * 8 + h * 4;
-      if (p.bias) o += *(const f32x4*)(p.bias + cb * 8 + h * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = o[e] > 0.f ? o[e] : o[e] * p.slope;
-      o *= p.alpha;
-      if (p.res1 && cb < p.res_cb1) o += p.beta1 * *(const f32x4*)(p.res1 + (long long)n * p.res1_ns + off);
-      if (p.res2 && cb < p.res_cb1) o += p.beta2 * *(const f32x4*)(p.res2 + (long long)n * p.res2_ns + off);
-      *(f32x4*)(p.out + (long long)n * p.out_ns + off) = o;
+      for (int g = 0; g < 4; ++g)
+        if (cog * 4 + g < p.cout_blocks) bv[g] = *(const f32x4*)(p.bias + (cog * 4 + g) * 8 + h * 4);
     }
+    f32x4 r2[2][4];
+    if constexpr (staged) {
+      if (p.res2) {
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          const int x = x0 + 2 * j + dx;
+          if (y >= p.H || x >= p.W) continue;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int cb = cog * 4 + g;
+            if (cb >= p.cout_blocks || cb >= p.res_cb1) continue;
+            r2[dx][g] = *(const f32x4*)(p.res2 + (long long)n * p.res2_ns + (cb * HW + (long long)y * p.W + x) * 8 + h * 4);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+      const int x = x0 + 2 * j + dx;
+      if (y >= p.H || x >= p.W) continue;
+      const long long pixoff = (long long)y * p.W + x;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int cb = cog * 4 + g;
+        if (cb >= p.cout_blocks) continue;
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = yv[dx][g * 4 + e];
+        const long long off = (cb * HW + pixoff) * 8 + h * 4;
+        if (p.bias) o += bv[g];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = o[e] > 0.f ? o[e] : o[e] * p.slope;
+        o *= p.alpha;
+        if constexpr (staged) {
+          if (cb < p.res_cb1) o += p.beta1 * *(const f32x4*)(smem + rlane + g * 2048 + dx * 32);
+          if (p.res2 && cb < p.res_cb1) o += p.beta2 * r2[dx][g];
+        } else {
+          if (p.res1 && cb < p.res_cb1) o += p.beta1 * *(const f32x4*)(p.res1 + (long long)n * p.res1_ns + off);
+          if (p.res2 && cb < p.res_cb1) o += p.beta2 * *(const f32x4*)(p.res2 + (long long)n * p.res2_ns + off);
+        }
+        *(f32x4*)(p.out + (long long)n * p.out_ns + off) = o;
+      }
+    }
+  };
+  if constexpr (RES_LDS) {
+    if (res_lds) epilogue(yes{});
+    else epilogue(no{});
+  } else {
+    epilogue(no{});
   }
   WINO_STAMP(4);
 }
@@ -375,6 +456,18 @@ int launch_wino(const WinoParams& p0, const sr_conv3x3_desc* d, hipStream_t stre
 // SR_F32_WINOGRAD in the environment, read once at first use, sets the initial value.
 int g_wino_mode = -1;
 
+// Residual 1 through the LDS (NW = 2, 1; two chunks or more): 1 = on (default), 0 = off: the epilogue loads it from memory.  Same
+// bits either way.  SR_F32_WINO_RES_STAGE in the environment, read once at first use, sets the initial value.
+int g_wino_res_stage = -1;
+
+int wino_res_stage() {
+  if (g_wino_res_stage < 0) {
+    const char* e = getenv("SR_F32_WINO_RES_STAGE");
+    g_wino_res_stage = (e && *e) ? (atoi(e) != 0) : 1;
+  }
+  return g_wino_res_stage;
+}
+
 }  // namespace
 
 namespace sr {
@@ -423,6 +516,7 @@ int conv3x3_wino_f32(const sr_conv3x3_desc* d, const float* image, hipStream_t s
   p.H = d->in_h << p.src_shift;
   p.W = d->in_w << p.src_shift;
   p.res_cb1 = d->res_cbn > 0 ? d->res_cbn : (1 << 30);
+  p.res_stage = wino_res_stage();
   p.slope = d->act_slope;
   p.alpha = d->alpha;
   p.beta1 = d->beta1;
@@ -451,6 +545,11 @@ int conv3x3_wino_f32(const sr_conv3x3_desc* d, const float* image, hipStream_t s
 
 extern "C" int sr_dev_set_wino_f32(int mode) {  // development switch (not in the ABI header)
   g_wino_mode = (mode >= 0 && mode <= 4) ? mode : 1;
+  return SR_OK;
+}
+
+extern "C" int sr_dev_set_wino_res_stage(int on) {  // development switch (not in the ABI header)
+  g_wino_res_stage = on != 0;
   return SR_OK;
 }
 

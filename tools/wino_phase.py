@@ -3,12 +3,13 @@ of 128x128).  Clock ticks of s_memtime: compare phases with one another, not wit
 
 Needs the diagnostic twin of the library (`make -C image_restoration_amd/csrc stamp`), selected with SR_HIP_LIB_PATH: the product
 library has no stamp and no sr_dev_set_wino_stamps.  One lane per workgroup stamps at entry (0), behind the first barrier (1), behind
-the last chunk's barrier (2), behind the exchange (3) and behind the last store (4):
+the last chunk's barrier (2), behind the exchange (3) and behind the last store (4), and at the head of the last chunk (5):
 
   prologue = 1 - 0   tile decoding, address work, the first chunks' DMAs land
   loop     = 2 - 1   all chunks
   exchange = 3 - 2   output transform and the exchange between the two halves
   epilogue = 4 - 3   bias, activation, residual reads, stores (issue only)
+  last chunk = 2 - 5 part of the loop: the chunk under whose MFMAs residual 1 is brought into the LDS
 The clocks of different XCDs are not aligned, and grouping the workgroups by blockIdx.x & 7 did not give groups with one clock
 each, so the spread between the first and the last workgroup's exit (the launch's drain) is NOT measured by this tool: what a launch
 costs beyond its workgroups' own timelines is the launch profiler's duration minus rounds x (the four phases).
@@ -90,6 +91,9 @@ def main():
         line = f'{name:22s}: {gx * gy:5d} workgroups = {gx * gy / (2 * cus):.0f} rounds, {int((~ok).sum())} without stamps'
         line += '\n    ' + ' | '.join(f'{nm} {float(x.median()):6.0f} [{float(x.min()):5.0f}..{float(x.max()):6.0f}]' for nm, x in zip(
             ('prologue', 'loop', 'exchange', 'epilogue'), [(t[:, k + 1] - t[:, k])[ok] for k in range(4)]))
+        if bool((t[:, 5] > 0)[ok].all()):   # stamp 5: head of the last chunk, whose barrier drains the residual pieces
+            x = (t[:, 2] - t[:, 5])[ok]
+            line += f' | last chunk {float(x.median()):6.0f} [{float(x.min()):5.0f}..{float(x.max()):6.0f}]'
         print(line, flush=True)
     lib.sr_dev_set_wino_f32(1)
 
