@@ -1072,5 +1072,10 @@ extern "C" const char* sr_kernel_name(int id) {
     return onames[id - 148];
   }
   if (id == 159) return "vsr_prop_input_kernel";  // vsr_ops.hip (include/sr_hip_vsr.h); 158 stays unnamed
+  if (id >= 161 && id < 166) {  // train_ops.hip, fp32 BatchNorm + LeakyReLU (bn_small.h below kBnSmallPixels); 160 stays unnamed
+    static const char* bnames[5] = {"bn_small_kernelIfLi8ELb0E", "bn_small_kernelIfLi8ELb1E", "bn_reduce_kernel", "bn_lrelu_fwd_kernel",
+                                    "bn_lrelu_bwd_kernel"};
+    return bnames[id - 161];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -622,7 +622,7 @@ struct BnRed16 {
   const float* invstd;
   float* part;  // [cblocks16][RED16][16][2]
   long long x_ns, dy_ns, y_ns;
-  int n, hw, mode;  // 0: sum x ; 1: sum (x-mean)^2 ; 2: sum dz, sum dz*xhat
+  int n, c, hw, mode;  // 0: sum x ; 1: sum (x-mean)^2 ; 2: sum dz, sum dz*xhat
   float slope;
 };
 // grid (cblocks16, RED16), block 256: thread t covers 8 channels (half = t & 1) of pixels t>>1, t>>1 + 128, ...
@@ -635,8 +635,9 @@ __global__ __launch_bounds__(256) void bn_reduce16_kernel(const BnRed16 p) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     a[e] = b[e] = 0.f;
-    mu[e] = p.mode >= 1 ? p.mean[cb * 16 + half * 8 + e] : 0.f;
-    is[e] = p.mode == 2 ? p.invstd[cb * 16 + half * 8 + e] : 1.f;
+    const bool live = cb * 16 + half * 8 + e < p.c;  // mean / invstd hold c floats; the sums of pad channels are never read
+    mu[e] = (p.mode >= 1 && live) ? p.mean[cb * 16 + half * 8 + e] : 0.f;
+    is[e] = (p.mode == 2 && live) ? p.invstd[cb * 16 + half * 8 + e] : 1.f;
   }
   for (long long i = (long long)sp * 128 + (threadIdx.x >> 1); i < total; i += 128 * RED16) {
     const int n = (int)(i / p.hw);
@@ -784,6 +785,7 @@ extern "C" int sr_bn_lrelu_fwd_bf16(const void* x, int64_t x_ns, void* y, int64_
     p.x = (const __bf16*)x;
     p.x_ns = x_ns;
     p.n = n;
+    p.c = c;
     p.hw = hw;
     p.part = part;
     p.mode = 0;
@@ -851,6 +853,7 @@ extern "C" int sr_bn_lrelu_bwd_bf16(const void* x, int64_t x_ns, const void* dy,
   p.mean = save_mean;
   p.invstd = save_invstd;
   p.n = n;
+  p.c = c;
   p.hw = hw;
   p.part = part;
   p.mode = 2;

@@ -33,7 +33,7 @@ struct BnRedParams {
   const float* invstd;
   float* part;  // [cblocks][RED_SPLITS][8][2]
   long long x_ns, dy_ns, y_ns;
-  int n, hw, mode;
+  int n, c, hw, mode;
   float slope;
 };
 
@@ -44,8 +44,18 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const BnRedParams p) {
   const long long total = (long long)p.n * p.hw;
   float a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
   float4 mu = make_float4(0, 0, 0, 0), is = make_float4(1, 1, 1, 1);
-  if (p.mode >= 1) mu = *(const float4*)(p.mean + cb * 8 + half * 4);
-  if (p.mode == 2) is = *(const float4*)(p.invstd + cb * 8 + half * 4);
+  {  // mean / invstd hold c floats: the pad channels of the last block keep 0 / 1 (their sums are never read)
+    const int ch0 = cb * 8 + half * 4;
+    float m4[4] = {0.f, 0.f, 0.f, 0.f}, i4[4] = {1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (ch0 + e >= p.c) continue;
+      if (p.mode >= 1) m4[e] = p.mean[ch0 + e];
+      if (p.mode == 2) i4[e] = p.invstd[ch0 + e];
+    }
+    mu = make_float4(m4[0], m4[1], m4[2], m4[3]);
+    is = make_float4(i4[0], i4[1], i4[2], i4[3]);
+  }
   for (long long i = (long long)sp * 128 + (threadIdx.x >> 1); i < total; i += 128 * RED_SPLITS) {
     const int n = (int)(i / p.hw);
     const long long off = ((long long)cb * p.hw + (i - (long long)n * p.hw)) * 8 + half * 4;
@@ -656,6 +666,23 @@ __global__ void lrelu_fwd_kernel(const float* __restrict__ x, float* __restrict_
 
 inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
 
+// Launch-profiler records of the fp32 BatchNorm paths (ids 161-165, sr_kernel_name): `tensors` = CB8 activations the bracketed
+// launches read or write once each (algorithmic bytes).  Returns whether a record was opened (the caller then closes it with
+// sr::prof_end after the launches).
+bool bn_prof_begin(hipStream_t stream, int id, int n, int c, int h, int w, int tensors) {
+  if (!sr::prof_on()) return false;
+  sr_launch_record r = {};
+  r.kernel_id = id;
+  r.cin = c;
+  r.cout = c;
+  r.n = n;
+  r.h = h;
+  r.w = w;
+  r.bytes = 4.0 * tensors * n * ((c + 7) / 8 * 8) * (double)h * w;
+  sr::prof_begin(stream, r);
+  return true;
+}
+
 }  // namespace
 
 // ===================================================================== C ABI
@@ -695,7 +722,9 @@ extern "C" int sr_bn_lrelu_fwd_f32(const float* x, int64_t x_ns, float* y, int64
     q.momentum = momentum;
     q.eps = eps;
     q.slope = slope;
+    const bool rec = bn_prof_begin(stream, 161, n, c, h, w, 2);
     bnsmall::launch<float, 8, false>(q, stream);
+    if (rec) sr::prof_end(stream);
     SR_CHECK_LAUNCH("bn_small fwd");
     return SR_OK;
   }
@@ -705,24 +734,31 @@ extern "C" int sr_bn_lrelu_fwd_f32(const float* x, int64_t x_ns, float* y, int64
     p.x = x;
     p.x_ns = x_ns;
     p.n = n;
+    p.c = c;
     p.hw = hw;
     p.part = part;
     p.mode = 0;
+    bool rec = bn_prof_begin(stream, 163, n, c, h, w, 1);  // reduce + finalise: the mean
     hipLaunchKernelGGL(bn_reduce_kernel, dim3(cblocks, RED_SPLITS), dim3(256), 0, stream, p);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(nblk(c)), dim3(256), 0, stream, part, c, 0, count, eps, momentum, save_mean,
                        save_invstd, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rec) sr::prof_end(stream);
     p.mode = 1;
     p.mean = save_mean;
+    rec = bn_prof_begin(stream, 163, n, c, h, w, 1);  // the centred second moment
     hipLaunchKernelGGL(bn_reduce_kernel, dim3(cblocks, RED_SPLITS), dim3(256), 0, stream, p);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(nblk(c)), dim3(256), 0, stream, part, c, 1, count, eps, momentum, save_mean,
                        save_invstd, running_mean, running_var, nullptr, nullptr, nullptr);
+    if (rec) sr::prof_end(stream);
   } else {
     hipLaunchKernelGGL(bn_eval_prep_kernel, dim3(nblk(c)), dim3(256), 0, stream, running_mean, running_var, eps, c,
                        save_mean, save_invstd);
   }
   const long long total = (long long)n * cblocks * hw * 2;
+  const bool rec = bn_prof_begin(stream, 164, n, c, h, w, 2);
   hipLaunchKernelGGL(bn_lrelu_fwd_kernel, dim3(nblk(total)), dim3(256), 0, stream, x, (long long)x_ns, y, (long long)y_ns,
                      save_mean, save_invstd, gamma, beta, slope, c, cblocks, hw, total);
+  if (rec) sr::prof_end(stream);
   SR_CHECK_LAUNCH("bn_lrelu_fwd");
   return SR_OK;
 }
@@ -756,7 +792,9 @@ extern "C" int sr_bn_lrelu_bwd_f32(const float* x, int64_t x_ns, const float* dy
     q.dgamma = dgamma;
     q.dbeta = dbeta;
     q.slope = slope;
+    const bool rec = bn_prof_begin(stream, 162, n, c, h, w, 4);
     bnsmall::launch<float, 8, true>(q, stream);
+    if (rec) sr::prof_end(stream);
     SR_CHECK_LAUNCH("bn_small bwd");
     return SR_OK;
   }
@@ -771,17 +809,22 @@ extern "C" int sr_bn_lrelu_bwd_f32(const float* x, int64_t x_ns, const float* dy
   p.mean = save_mean;
   p.invstd = save_invstd;
   p.n = n;
+  p.c = c;
   p.hw = hw;
   p.part = part;
   p.mode = 2;
   p.slope = slope;
+  bool rec = bn_prof_begin(stream, 163, n, c, h, w, 3);  // reduce + finalise: dbeta, dgamma
   hipLaunchKernelGGL(bn_reduce_kernel, dim3(cblocks, RED_SPLITS), dim3(256), 0, stream, p);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(nblk(c)), dim3(256), 0, stream, part, c, 2, count, 0.f, 0.f, nullptr,
                      nullptr, nullptr, nullptr, dgamma, dbeta, nullptr);
+  if (rec) sr::prof_end(stream);
   const long long total = (long long)n * cblocks * hw * 2;
+  rec = bn_prof_begin(stream, 165, n, c, h, w, 4);
   hipLaunchKernelGGL(bn_lrelu_bwd_kernel, dim3(nblk(total)), dim3(256), 0, stream, x, (long long)x_ns, dy, (long long)dy_ns,
                      y, (long long)y_ns, dx, (long long)dx_ns, save_mean, save_invstd, gamma, dgamma, dbeta, slope, train,
                      1.f / (float)count, c, cblocks, hw, total);
+  if (rec) sr::prof_end(stream);
   SR_CHECK_LAUNCH("bn_lrelu_bwd");
   return SR_OK;
 }

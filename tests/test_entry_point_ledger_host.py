@@ -37,6 +37,8 @@ PINNED = {
     'sr_bilinear2x_fwd_u2_bf16': _LAYOUT + 'test_bilinear2x_fwd_bf16',
     'sr_bilinear2x_bwd_bf16': _LAYOUT + 'test_bilinear2x_bwd_bf16',
     'sr_bilinear2x_bwd_lrelu_bf16': _LAYOUT + 'test_bilinear2x_bwd_bf16',
+    # one target per symbol: the eval mode; the train mode of these four (both kernels, the edge shapes) is pinned next to it in
+    # test_bn_lrelu_train_mode, and on the networks' own tensors in tests/test_f32_nets_opwise_gpu.py
     'sr_bn_lrelu_fwd_f32': _LAYOUT + 'test_bn_lrelu_eval_mode',
     'sr_bn_lrelu_bwd_f32': _LAYOUT + 'test_bn_lrelu_eval_mode',
     'sr_bn_lrelu_fwd_bf16': _LAYOUT + 'test_bn_lrelu_eval_mode',

@@ -1,7 +1,9 @@
 """The layout, resampling and bf16 helper kernels against float64 (and, where the kernel's arithmetic is a short fixed sequence,
 against a bit-exact float32 emulation of that sequence): sr_nchw_to_cb8_f32 / sr_cb8_to_nchw_f32 / sr_upsample2x_bwd_f32 /
-sr_cb8_axpby_f32 (layout.hip), their CB16 twins (layout_bf16.hip), the bf16 helpers of the discriminators (disc_bf16.hip) and the
-eval mode (train = 0) of sr_bn_lrelu_{fwd,bwd}_{f32,bf16}.
+sr_cb8_axpby_f32 (layout.hip), their CB16 twins (layout_bf16.hip), the bf16 helpers of the discriminators (disc_bf16.hip) and both
+modes of sr_bn_lrelu_{fwd,bwd}_{f32,bf16}: the eval mode (train = 0) in test_bn_lrelu_eval_mode, the train mode (batch statistics) on
+both of its kernels and at its edge shapes in test_bn_lrelu_train_mode, with the float64 formula and its derived bounds in
+tests/f32_opwise.py (bn_train_reference); tests/test_f32_nets_opwise_gpu.py holds the same kernels on the tensors of the networks.
 
 Comparison policy.
   - Pure data movement (the NCHW <-> CB conversions with their fused pixel (un)shuffle, sr_cb16_unshuffle2_bf16 both ways, the bf16
@@ -37,12 +39,18 @@ Negative controls: every check is also run once on a copy of the result with one
 checks, an error of 1.05 bounds for the float64 checks, one slack element overwritten for the sentinel checks) and must fail.
 """
 import ctypes as C
+import math
+import os
+import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from image_restoration_amd import _lib
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from f32_opwise import bn_train_reference, bn_tree_depth, worst  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -793,3 +801,122 @@ def test_bn_lrelu_eval_mode(cuda, lib, c, dt):
         _neg_within(got_v.cpu(), ref_v, bnd, what)
     assert bool((ws[wsb:] == 0xAB).all()), 'the reductions wrote past sr_reduce_workspace_bytes(c)'
 
+
+
+# ========================================================================= BatchNorm + LeakyReLU, train mode
+BN_TRAIN = {  # n, c, h, w, content, slope
+    'm1': (1, 8, 1, 1, 'randn', 0.2),               # M = 1: variance 0, unbiased = biased by the kernels' own rule, dx = 0
+    'c3': (2, 3, 1, 2, 'randn', 0.2),               # 3 live channels of 8: the second 4-channel group has no live channel
+    'c20': (3, 20, 7, 9, 'randn', 0.2),             # c % 8 = 4
+    'above': (1, 8, 1, 32769, 'randn', 0.2),        # one pixel above kBnSmallPixels: the two-stage kernels only
+    'at': (2, 8, 128, 128, 'randn', 0.2),           # exactly kBnSmallPixels
+    'offset': (2, 12, 5, 5, 'offset', 0.2),         # mean >> spread: the bound's dmu^2 term guards the centred second pass
+    'const': (2, 8, 4, 4, 'const', 0.2),            # one constant channel: invstd = rsqrt(eps), its dgamma 0 within the bound
+    'slope1': (3, 20, 7, 9, 'randn', 1.0),          # plain BatchNorm
+}
+BN_TRAIN_RUNS = [(k, kern) for k in BN_TRAIN for kern in ('one_launch', 'two_stage') if not (k == 'above' and kern == 'one_launch')]
+
+
+@pytest.fixture
+def bn_small_switch(lib):
+    """sr_dev_set_bn_small (development hook): 0 sends every size to the two-stage kernels; back to 1 afterwards."""
+    lib.sr_dev_set_bn_small.argtypes = [C.c_int]
+    lib.sr_dev_set_bn_small.restype = None
+    yield lib.sr_dev_set_bn_small
+    torch.cuda.synchronize()
+    lib.sr_dev_set_bn_small(1)
+
+
+def _nan_pads(vals, c):
+    """NaN in the pad channels (>= c) of a host tensor [n][blocks][h][w][blk]."""
+    n, blocks, h, w, blk = vals.shape
+    ch = (torch.arange(blocks).view(blocks, 1) * blk + torch.arange(blk).view(1, blk)).view(1, blocks, 1, 1, blk)
+    return torch.where(ch >= c, torch.full_like(vals, float('nan')), vals)
+
+
+@pytest.mark.parametrize('case,kern', BN_TRAIN_RUNS, ids=[f'{k}-{kern}' for k, kern in BN_TRAIN_RUNS])
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+def test_bn_lrelu_train_mode(cuda, lib, bn_small_switch, case, kern, dt):
+    """Train mode (batch statistics) of sr_bn_lrelu_{fwd,bwd}_{f32,bf16} on both of its kernels, the one-launch kernel of bn_small.h
+    and the two-stage reduce + finalise kernels, at the edges: y, mean, invstd, both running buffers from non-trivial starting values,
+    dx, dgamma, dbeta against the float64 formula written out in f32_opwise.bn_train_reference, within its derived bounds (K = L + 6
+    roundings, L the depth of the kernel's own reduction tree; a bf16 store adds EPS16 of the stored value).  Sources carry NaN in
+    their pad channels and the sentinel in their slack; pad channels of y / dx are +0, the slack stays, two runs are bit-identical."""
+    n, c, h, w, content, slope = BN_TRAIN[case]
+    eps = _f32(1e-5)
+    dtype = torch.float32 if dt == 'f32' else torch.bfloat16
+    blk = 8 if dt == 'f32' else 16
+    blocks = -(-c // blk)
+    M = n * h * w
+    general = kern == 'two_stage'
+    assert general or M <= 32768
+    torch.manual_seed(c * 131 + h + w)
+    if content == 'offset':
+        x = 100 + 0.01 * torch.randn(n, c, h, w)
+    else:
+        x = torch.randn(n, c, h, w) * 1.5 + 0.3
+        if content == 'const':
+            x[:, 1] = 0.75
+    x = x.to(dtype)
+    dy = torch.randn(n, c, h, w).to(dtype)
+    gamma, beta = (torch.rand(c) + 0.5) * torch.where(torch.arange(c) % 3 == 2, -1.0, 1.0), torch.rand(c) - 0.5
+    rm, rv = torch.randn(c) * 0.3, torch.rand(c) + 0.5
+    xb = Buf(n, blocks, h, w, dtype, pad=16, cuda=cuda)
+    xb.put(_nan_pads(_to_cb(x.float(), blk, blocks), c))
+    dyb = Buf(n, blocks, h, w, dtype, pad=48, cuda=cuda)
+    dyb.put(_nan_pads(_to_cb(dy.float(), blk, blocks), c))
+    gd, bd = gamma.to(cuda), beta.to(cuda)
+    wsb = lib.sr_reduce_workspace_bytes(c)
+    ws = torch.full((wsb + 4096,), 0xAB, dtype=torch.uint8, device=cuda)   # the tail must stay as it is
+    fwd = lib.sr_bn_lrelu_fwd_f32 if dt == 'f32' else lib.sr_bn_lrelu_fwd_bf16
+    bwd = lib.sr_bn_lrelu_bwd_f32 if dt == 'f32' else lib.sr_bn_lrelu_bwd_bf16
+    bn_small_switch(0 if general else 1)
+
+    def run():
+        yb = Buf(n, blocks, h, w, dtype, pad=32, cuda=cuda)
+        yb.mark()
+        dxb = Buf(n, blocks, h, w, dtype, pad=16, cuda=cuda)
+        dxb.mark()
+        o = dict(rm=rm.to(cuda), rv=rv.to(cuda), y=yb, dx=dxb)
+        for k in ('mean', 'invstd', 'dgamma', 'dbeta'):
+            o[k] = torch.full((c,), float('nan'), device=cuda)
+        _ok(fwd(xb.ptr(), xb.stride, yb.ptr(), yb.stride, n, c, h, w, gd.data_ptr(), bd.data_ptr(), o['rm'].data_ptr(), o['rv'].data_ptr(),
+                1, 0.1, eps, slope, o['mean'].data_ptr(), o['invstd'].data_ptr(), ws.data_ptr(), wsb, _st()), 'bn_lrelu_fwd train')
+        _ok(bwd(xb.ptr(), xb.stride, dyb.ptr(), dyb.stride, yb.ptr(), yb.stride, dxb.ptr(), dxb.stride, n, c, h, w, gd.data_ptr(),
+                o['mean'].data_ptr(), o['invstd'].data_ptr(), 1, slope, o['dgamma'].data_ptr(), o['dbeta'].data_ptr(), ws.data_ptr(), wsb,
+                _st()), 'bn_lrelu_bwd train')
+        return o
+    o, again = run(), run()
+    for k in ('rm', 'rv', 'mean', 'invstd', 'dgamma', 'dbeta'):
+        assert torch.equal(_ibits(o[k].cpu()), _ibits(again[k].cpu())), f'{k}: two runs differ'
+    for k in ('y', 'dx'):
+        assert torch.equal(_ibits(o[k].flat.cpu()), _ibits(again[k].flat.cpu())), f'{k}: two runs differ'
+        _checked_slack(o[k], f'bn_lrelu train {k}')
+    assert bool((ws[wsb:] == 0xAB).all()), 'the reductions wrote past sr_reduce_workspace_bytes(c)'
+    y = _from_cb(o['y'].win().cpu().float())
+    dx = _from_cb(o['dx'].win().cpu().float())
+    assert bool((_ibits(y[:, c:]) == 0).all()) and bool((_ibits(dx[:, c:]) == 0).all()), 'padding channels must be +0'
+    K = bn_tree_depth(M, general) + 6
+    args = (x.double(), gamma.double(), beta.double(), rm.double(), rv.double(), eps, _f32(slope), K, y[:, :c].double(), dy.double())
+    store = 0.0 if dt == 'f32' else EPS16
+    ref = bn_train_reference(*args, store=store)
+    got = dict(fwd=y[:, :c], dx=dx[:, :c], mean=o['mean'], invstd=o['invstd'], running_mean=o['rm'], running_var=o['rv'],
+               dgamma=o['dgamma'], dbeta=o['dbeta'])
+    assert set(got) == set(ref)
+    for k, g in got.items():
+        want, bound = ref[k]
+        print(f'{case} {kern} {dt} {k}: largest err / bound {worst(g.cpu().double(), want, bound + TINY):.3f}')
+        _within(g, want, bound + TINY, f'bn train {k}')
+        _neg_within(g, want, bound + TINY, f'bn train {k}')
+    if case == 'm1':
+        assert bool((ref['dx'][0] == 0).all()) and bool((ref['invstd'][0] == 1.0 / torch.sqrt(torch.tensor(eps, dtype=torch.float64))).all())
+        assert torch.equal(ref['running_var'][0], 0.9 * rv.double())      # unbiased = biased = 0
+    if content == 'const':
+        assert float(ref['invstd'][0][1]) == 1.0 / math.sqrt(eps) and float(ref['dgamma'][0][1]) == 0.0
+    if content == 'offset' and dt == 'f32':
+        # a one-pass E[x^2] - E[x]^2 in float32 loses the whole variance here (x^2 is near 1e4, where an fp32 ulp is 1e-3, against a
+        # variance of 1e-4): that reference must be outside the bound.  (In bf16 the input itself rounds to the constant 100.)
+        one_pass = bn_train_reference(*args, mutate='one_pass', store=store)
+        miss = worst(y[:, :c].double(), *one_pass['fwd'])
+        print(f'{case} {kern} {dt} one-pass variance reference: err / bound {miss:.3g}')
+        assert miss > 1.0, 'the bound cannot tell a one-pass variance from the centred second pass'

@@ -7,7 +7,8 @@ relative-L2 layer by layer, EXCEPT where one ReLU unit whose pre-activation is w
 than in the float64 oracle: that unit's whole receptive field at the input changes (observed: conv4_1 on 64x64, 1114 of
 24576 gradient elements, 3.6e-3 relative-L2; conv5_4 on 36x52, 1.2e-2; deterministic, and absent one layer deeper or
 shallower).  The bound is therefore 3e-2 relative-L2 (conv5_4's receptive field covers these small test images entirely, so no
-per-element statement is possible there)."""
+per-element statement is possible there).  The per-element statement is made op by op instead, where no branch can flip:
+tests/test_f32_nets_opwise_gpu.py replays every op of this extractor on its own recorded tensors against float64."""
 import numpy as np
 import pytest
 import torch
