@@ -530,6 +530,21 @@ VSR_SIGNATURES = {
     'sr_vsr_trunk_f32': (C.c_int, [C.POINTER(VsrTrunkCfg), _P, _P, C.c_longlong, _P, C.c_longlong, _I, _I, _I, _P, C.c_size_t, _P]),
 }
 
+
+class RvsrPropDesc(C.Structure):
+    """struct sr_rvsr_prop_desc (include/sr_hip_vsr_bf16.h)."""
+    _fields_ = VsrPropDesc._fields_
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_vsr_bf16.h declares
+VSR_BF16_SIGNATURES = {
+    'sr_rvsr_prop_input_bf16': (C.c_int, [C.POINTER(RvsrPropDesc), _P]),
+    'sr_rvsr_trunk_packed_bytes_bf16': (C.c_size_t, [C.POINTER(VsrTrunkCfg)]),
+    'sr_rvsr_trunk_pack_bf16': (C.c_int, [C.POINTER(VsrTrunkCfg), C.POINTER(C.c_void_p), _P, _P]),
+    'sr_rvsr_trunk_workspace_bytes_bf16': (C.c_size_t, [C.POINTER(VsrTrunkCfg), _I, _I, _I]),
+    'sr_rvsr_trunk_bf16': (C.c_int, [C.POINTER(VsrTrunkCfg), _P, _P, C.c_longlong, _P, C.c_longlong, _I, _I, _I, _P, C.c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -545,7 +560,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
-            + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()):
+            + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()) + list(VSR_BF16_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -17,7 +17,12 @@ The per-clip feature tensor is [n * b, 2 * num_feat / 8, h, w, 8], frame-major: 
 backward branch's feature of frame i, blocks [fb, 2 fb) the forward branch's, so ``cat([out_l[i], feat_prop])`` is the image itself
 and is never copied.  The backward branch runs first, then the forward branch.
 
-Inference only, fp32, x4: outputs never carry a grad_fn, and a forward that would need a graph (train mode, grad enabled,
+``set_compute_dtype('bf16')`` (or ``network_g.compute_dtype: bf16`` in an option file) runs propagation and reconstruction on
+CB16 bf16 activations: the clip tensor is [n * b, 2 * num_feat / 16, h, w, 16], a step is one
+sr_rvsr_prop_input_bf16 and one sr_rvsr_trunk_bf16, the head runs on the bf16 convs and ``conv_last`` stores fp32 NCHW.  The input
+clip, SpyNet and the flows stay fp32, so ``get_flow`` is the same bits in both modes; ``num_feat % 16 == 0`` is required.
+
+Inference only, x4: outputs never carry a grad_fn, and a forward that would need a graph (train mode, grad enabled,
 something requiring grad) raises NotImplementedError — training (SpyNet's backward, the recurrent backward) is the follow-up.
 ValueError, before anything is launched, for: fewer than two frames (the reference's ``get_flow`` cannot reshape an empty batch),
 channels other than 3, a dtype other than fp32, a side of 32 pixels or fewer (SpyNet's rule), ``num_feat % 8 != 0``.
@@ -29,7 +34,7 @@ from torch.nn import functional as F
 from .. import _lib, hip_ops
 from ..utils.registry import ARCH_REGISTRY
 from .arch_util import Conv3x3Params, ResidualBlockNoBN, make_layer
-from .edvr_arch import _FP32, PCDAlignment, TSAFusion
+from .edvr_arch import _BF16, _FP32, PCDAlignment, TSAFusion
 from .hip_driver import HipDriverNet
 from .hip_generator import HipGenerator
 from .spynet_arch import SpyNet
@@ -62,20 +67,25 @@ class ConvResidualBlocks(HipDriverNet):
                              f'got {self.num_in_ch} -> {self.num_out_ch}')
         return _lib.VsrTrunkCfg(self.num_out_ch, self.num_block, segs)
 
-    def packed(self, dev):
+    def packed(self, dev, bf16=False):
         """(config, blob of weight images) for the current parameters: looked up once per branch, not per step — the weights key
-        walks every parameter of the trunk."""
+        walks every parameter of the trunk.  ``bf16``: the blob of bf16 images and fp32 biases, kept as a second kind beside the
+        fp32 one under the same weights key."""
         lib, cfg = _lib.load(), self.cfg()
+        if bf16 and self.num_out_ch % 16:
+            raise ValueError(f'ConvResidualBlocks: the bf16 trunk needs num_out_ch % 16 == 0 (CB16), got {self.num_out_ch}')
+        stem = 'sr_rvsr_trunk' if bf16 else 'sr_vsr_trunk'
         with torch.cuda.device(dev):
-            blob = self._blob(('fwd', False), lib, cfg, torch.cuda.current_stream(dev).cuda_stream, 'sr_vsr_trunk_packed_bytes',
-                              'sr_vsr_trunk_pack')
+            blob = self._blob(('fwd', bool(bf16)), lib, cfg, torch.cuda.current_stream(dev).cuda_stream, stem + '_packed_bytes',
+                              stem + '_pack')
         return cfg, blob
 
     def run(self, src, out, packed=None):
-        """``src``: CB8 window [frame block, feature windows]; ``out``: CB8 window of num_out_ch channels; ``packed``: what
-        ``packed(device)`` returned for the current parameters (looked up here when None)."""
-        cfg, blob = packed or self.packed(src.device)
-        return hip_ops.vsr_trunk(cfg, blob, src, out)
+        """``src``: CB8 (fp32) or CB16 (bf16) window [frame block, feature windows]; ``out``: window of num_out_ch channels of the
+        same kind; ``packed``: what ``packed(device, bf16)`` returned for the current parameters (looked up here when None)."""
+        bf16 = isinstance(src, hip_ops.CB16)
+        cfg, blob = packed or self.packed(src.device, bf16)
+        return (hip_ops.vsr_trunk_bf16 if bf16 else hip_ops.vsr_trunk)(cfg, blob, src, out)
 
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError('ConvResidualBlocks is a parameter container; the video network launches the HIP kernels')
@@ -110,6 +120,24 @@ class BasicVSR(HipGenerator):
         self.conv_hr = Conv3x3Params(64, 64)
         self.conv_last = Conv3x3Params(64, 3)
 
+    # ------------------------------------------------------------------------------------------------- compute dtype
+    def set_compute_dtype(self, compute_dtype):
+        """'fp32' or 'bf16' for propagation and reconstruction (SpyNet and the flows stay fp32); returns ``self``.  Set after
+        construction: the constructor keeps the reference's signature."""
+        if compute_dtype not in ('fp32', 'bf16'):
+            raise ValueError(f"{type(self).__name__}: compute_dtype={compute_dtype!r} is not supported; supported: 'fp32', 'bf16'")
+        if compute_dtype == 'bf16' and self.num_feat % 16 != 0:
+            raise ValueError(f"{type(self).__name__}: compute_dtype='bf16' needs num_feat % 16 == 0 (CB16 activations), got "
+                             f'num_feat={self.num_feat}')
+        self.compute_dtype = compute_dtype
+        return self
+
+    def _layout(self):
+        """(window class, channels per block, element type, step-input launch) of the compute dtype."""
+        if self.compute_dtype == 'bf16':
+            return hip_ops.CB16, 16, torch.bfloat16, hip_ops.vsr_prop_input_bf16
+        return hip_ops.CB8, 8, torch.float32, hip_ops.vsr_prop_input
+
     # ------------------------------------------------------------------------------------------------------ refusals
     def _check(self, x, flows=()):
         if x.dim() != 5 or x.size(2) != 3:
@@ -126,11 +154,15 @@ class BasicVSR(HipGenerator):
         for f in flows:
             if tuple(f.shape) != (b, n - 1, 2, h, w):
                 raise ValueError(f'{type(self).__name__}: flows must be [{b}, {n - 1}, 2, {h}, {w}], got {tuple(f.shape)}')
+        needs_graph = self.training and torch.is_grad_enabled() and (x.requires_grad or any(f.requires_grad for f in flows)
+                                                                     or any(p.requires_grad for p in self.parameters()))
+        if needs_graph and self.compute_dtype == 'bf16':
+            raise NotImplementedError(f"{type(self).__name__} with compute_dtype='bf16' is forward only (eval mode or "
+                                      "torch.no_grad()); train with compute_dtype='fp32'")
         if not (x.is_cuda and all(f.is_cuda for f in flows)):
             raise _lib.SrHipError(f'{type(self).__name__}.forward runs only on a HIP device (no CPU fallback): move the module and '
                                   'inputs with .to("cuda")')
-        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(f.requires_grad for f in flows)
-                                                          or any(p.requires_grad for p in self.parameters())):
+        if needs_graph:
             raise NotImplementedError(f'{type(self).__name__} runs inference only: call .eval() (or run under torch.no_grad()); '
                                       'training (SpyNet\'s backward and the recurrent backward) is the follow-up')
 
@@ -157,19 +189,22 @@ class BasicVSR(HipGenerator):
 
     # --------------------------------------------------------------------------------------------------- propagation
     def _branch(self, trunk, x, flows, feats, cb0, order, tin):
-        """One propagation branch over the frames in ``order``: per step one sr_vsr_prop_input_f32 and one sr_vsr_trunk_f32.
-        ``flows[:, j]`` warps the feature of the previous step onto frame ``order[k]``: j = i for the backward branch, i - 1 for
-        the forward branch."""
-        b, fb = x.size(0), self.num_feat // 8
-        frame_out, warp_out = hip_ops.CB8(tin, 0, 1), hip_ops.CB8(tin, 1, fb)
-        prev, packed, src = None, trunk.packed(x.device), hip_ops.CB8(tin)
+        """One propagation branch over the frames in ``order``: per step one step-input launch (sr_vsr_prop_input_f32 /
+        sr_rvsr_prop_input_bf16) and one trunk call (sr_vsr_trunk_f32 / sr_rvsr_trunk_bf16).  ``flows[:, j]`` warps the feature of
+        the previous step onto frame ``order[k]``: j = i for the backward branch, i - 1 for the forward branch."""
+        CB, blk, _, prop_input = self._layout()
+        b, fb = x.size(0), self.num_feat // blk
+        frame_out, warp_out = CB(tin, 0, 1), CB(tin, 1, fb)
+        prev, packed, src = None, trunk.packed(x.device, blk == 16), CB(tin)
         for k, i in enumerate(order):
             flow = None if prev is None else flows[:, min(i, order[k - 1])]
-            hip_ops.vsr_prop_input(x[:, i], prev, flow, warp_out, frame_out)
-            prev = trunk.run(src, hip_ops.CB8(feats[i * b:(i + 1) * b], cb0, fb), packed)
+            prop_input(x[:, i], prev, flow, warp_out, frame_out)
+            prev = trunk.run(src, CB(feats[i * b:(i + 1) * b], cb0, fb), packed)
 
     def _reconstruct(self, feats, frames, y):
         """The upsampling head on images [s, e) of the frame-major clip tensors, into y[s:e]."""
+        if self.compute_dtype == 'bf16':
+            return self._reconstruct_bf16(feats, frames, y)
         out = hip_ops.CB8(feats)
         if self._fuses:     # BasicVSR: fusion 1x1 of [backward, forward]; IconVSR reconstructs from the forward feature alone
             out = hip_ops.convd(out, self.packed(self.fusion), act_slope=0.1)
@@ -179,15 +214,34 @@ class BasicVSR(HipGenerator):
         hip_ops.conv3x3(out, self.packed(self.conv_last), out_nchw=y)
         hip_ops.bilinear_up(frames, 4, out=y)
 
+    def _packed16(self, conv):
+        """The bf16 image of a head or fusion conv: 3x3 from this network's cache, the 1x1 fusion from hip_ops' (both keyed on the
+        parameter's version, so an in-place update is seen)."""
+        return self.packed(conv, 0, True) if conv.weight.shape[2] == 3 else hip_ops.packed_conv_bf16(conv)
+
+    def _reconstruct_bf16(self, feats, frames, y):
+        """The head on CB16: every activation is stored as bf16 once, after its epilogue; conv_last writes fp32 NCHW and the x4
+        bilinear base of the fp32 frames is added in fp32."""
+        H, P = hip_ops, self._packed16
+        out = H.CB16(feats)
+        if self._fuses:
+            out = H.conv1x1_bf16(out, P(self.fusion), act_slope=0.1)
+        out = H.pixel_shuffle_bf16(H.conv3x3_bf16(out, P(self.upconv1), act_slope=0.1), self.num_feat, 2)
+        out = H.pixel_shuffle_bf16(H.conv3x3_bf16(out, P(self.upconv2), act_slope=0.1), 64, 2)
+        out = H.conv3x3_bf16(out, P(self.conv_hr), act_slope=0.1)
+        H.conv3x3_bf16(out, P(self.conv_last), out_nchw=y)
+        H.bilinear_up(frames, 4, out=y)
+
     def propagate(self, x, flows_forward, flows_backward):
         """The network after ``get_flow``: x [b, n, 3, h, w], flows [b, n - 1, 2, h, w] -> [b, n, 3, 4h, 4w]."""
         self._check(x, (flows_forward, flows_backward))
         with torch.no_grad():
             x, flows_forward, flows_backward = x.contiguous(), flows_forward.contiguous(), flows_backward.contiguous()
             b, n, _, h, w = x.shape
-            fb, dev = self.num_feat // 8, x.device
-            feats = torch.empty((n * b, 2 * fb, h, w, 8), dtype=torch.float32, device=dev)
-            tin = torch.empty((b, 1 + fb, h, w, 8), dtype=torch.float32, device=dev)
+            _, blk, dtype, _ = self._layout()
+            fb, dev = self.num_feat // blk, x.device
+            feats = torch.empty((n * b, 2 * fb, h, w, blk), dtype=dtype, device=dev)
+            tin = torch.empty((b, 1 + fb, h, w, blk), dtype=dtype, device=dev)
             self._branch(self.backward_trunk, x, flows_backward, feats, 0, list(range(n - 1, -1, -1)), tin)
             self._branch(self.forward_trunk, x, flows_forward, feats, fb, list(range(n)), tin)
             # reconstruction, frame-major: image i * b + k is frame i of clip k
@@ -206,8 +260,8 @@ class BasicVSR(HipGenerator):
 class EDVRFeatureExtractor(nn.Module):
     """The keyframe branch of IconVSR (the reference's EDVRFeatureExtractor, basicvsr_arch.py:251-309): EDVR up to and including
     the TSA fusion, on EDVR's fp32 ops table and modules (edvr_arch.py).  ``run(x)`` takes [b, t, 3, h, w] (h, w multiples of 4)
-    and returns the fused features as a raw CB8 tensor [b, num_feat / 8, h, w, 8].  The reference hard-codes 64 channels in its
-    residual blocks, so ``num_feat`` is 64."""
+    and returns the fused features as a raw CB8 tensor [b, num_feat / 8, h, w, 8]; on the bf16 table (``ops=_BF16``) as a CB16
+    window.  The reference hard-codes 64 channels in its residual blocks, so ``num_feat`` is 64."""
 
     def __init__(self, num_input_frame, num_feat, load_path):
         super().__init__()
@@ -223,8 +277,7 @@ class EDVRFeatureExtractor(nn.Module):
         if load_path:
             self.load_state_dict(torch.load(load_path, map_location='cpu')['params'])
 
-    def run(self, x):
-        ops = _FP32
+    def run(self, x, ops=_FP32):
         b, t, c, h, w = x.shape
         feat_l1 = ops.conv(self.conv_first, ops.enter(x.reshape(b * t, c, h, w)))
         for blk in self.feature_extraction:
@@ -300,13 +353,15 @@ class IconVSR(BasicVSR):
 
     def get_keyframe_feature(self, x, keyframe_idx):
         """{i: fused EDVR features of the window around keyframe i} on the (padded) clip x, each a raw CB8 tensor
-        [b, fb, h, w, 8]; the windows come from the reference's mirrored clip."""
+        [b, fb, h, w, 8] (bf16: a raw CB16 tensor [b, fb, h, w, 16] from EDVR's bf16 ops table); the windows come from the
+        reference's mirrored clip."""
         self._check(x)
         with torch.no_grad():
             tp = self.temporal_padding
             lead, tail = ([4, 3], [-4, -5]) if tp == 2 else ([6, 5, 4], [-5, -6, -7])
             xm = torch.cat([x[:, lead], x, x[:, tail]], dim=1)
-            return {i: self.edvr.run(xm[:, i:i + 2 * tp + 1].contiguous()) for i in keyframe_idx}
+            ops = _BF16 if self.compute_dtype == 'bf16' else _FP32
+            return {i: ops.raw(self.edvr.run(xm[:, i:i + 2 * tp + 1].contiguous(), ops)) for i in keyframe_idx}
 
     def propagate(self, x, flows_forward, flows_backward, feats_keyframe=None, crop=None):
         """The network after ``get_flow`` and ``get_keyframe_feature`` on a clip whose sides are multiples of 4; ``crop`` = (h, w)
@@ -320,31 +375,36 @@ class IconVSR(BasicVSR):
             keys = self.keyframes(n)
             if feats_keyframe is None:
                 feats_keyframe = self.get_keyframe_feature(x, keys)
-            fb, dev, CB8 = self.num_feat // 8, x.device, hip_ops.CB8
-            clip = torch.empty((n * b, 1 + 2 * fb, h, w, 8), dtype=torch.float32, device=dev)
-            fwd = torch.empty((n * b, fb, h, w, 8), dtype=torch.float32, device=dev)
-            tin = torch.empty((b, 1 + fb, h, w, 8), dtype=torch.float32, device=dev)
+            CB, blk, dtype, prop_input = self._layout()
+            bf16 = blk == 16
+            fb, dev = self.num_feat // blk, x.device
+            clip = torch.empty((n * b, 1 + 2 * fb, h, w, blk), dtype=dtype, device=dev)
+            fwd = torch.empty((n * b, fb, h, w, blk), dtype=dtype, device=dev)
+            tin = torch.empty((b, 1 + fb, h, w, blk), dtype=dtype, device=dev)
             pair = {}
             for i in keys:      # [warped feature | keyframe feature]: what a fusion conv reads
-                pair[i] = torch.empty((b, 2 * fb, h, w, 8), dtype=torch.float32, device=dev)
+                pair[i] = torch.empty((b, 2 * fb, h, w, blk), dtype=dtype, device=dev)
                 pair[i][:, fb:].copy_(feats_keyframe[i])
 
             def step(i, prev, flow, fusion, warp_out, frame_out):
                 if i in pair:
-                    hip_ops.vsr_prop_input(x[:, i], prev, flow, CB8(pair[i], 0, fb), frame_out)
-                    hip_ops.conv3x3(CB8(pair[i]), self.packed(fusion), warp_out)
+                    prop_input(x[:, i], prev, flow, CB(pair[i], 0, fb), frame_out)
+                    if bf16:
+                        hip_ops.conv3x3_bf16(CB(pair[i]), self._packed16(fusion), warp_out)
+                    else:
+                        hip_ops.conv3x3(CB(pair[i]), self.packed(fusion), warp_out)
                 else:
-                    hip_ops.vsr_prop_input(x[:, i], prev, flow, warp_out, frame_out)
+                    prop_input(x[:, i], prev, flow, warp_out, frame_out)
 
-            prev, packed = None, self.backward_trunk.packed(dev)
+            prev, packed = None, self.backward_trunk.packed(dev, bf16)
             for i in range(n - 1, -1, -1):
-                step(i, prev, None if prev is None else flows_backward[:, i], self.backward_fusion, CB8(tin, 1, fb), CB8(tin, 0, 1))
-                prev = self.backward_trunk.run(CB8(tin), CB8(clip[i * b:(i + 1) * b], 1, fb), packed)
-            prev, packed = None, self.forward_trunk.packed(dev)
+                step(i, prev, None if prev is None else flows_backward[:, i], self.backward_fusion, CB(tin, 1, fb), CB(tin, 0, 1))
+                prev = self.backward_trunk.run(CB(tin), CB(clip[i * b:(i + 1) * b], 1, fb), packed)
+            prev, packed = None, self.forward_trunk.packed(dev, bf16)
             for i in range(n):
                 img = clip[i * b:(i + 1) * b]
-                step(i, prev, None if prev is None else flows_forward[:, i - 1], self.forward_fusion, CB8(img, 1 + fb, fb), CB8(img, 0, 1))
-                prev = self.forward_trunk.run(CB8(img), CB8(fwd[i * b:(i + 1) * b]), packed)
+                step(i, prev, None if prev is None else flows_forward[:, i - 1], self.forward_fusion, CB(img, 1 + fb, fb), CB(img, 0, 1))
+                prev = self.forward_trunk.run(CB(img), CB(fwd[i * b:(i + 1) * b]), packed)
             frames = x.transpose(0, 1).reshape(n * b, 3, h, w)
             y = torch.empty((n * b, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
             chunk = max(1, _RECON_BUDGET // (4 * 4 * 64 * 16 * h * w))

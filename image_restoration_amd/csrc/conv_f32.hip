@@ -1077,5 +1077,6 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "bn_lrelu_bwd_kernel"};
     return bnames[id - 161];
   }
+  if (id == 167) return "vsr_prop_input_bf16_kernel";  // vsr_ops_bf16.hip (include/sr_hip_vsr_bf16.h); 166 stays unnamed
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -7,6 +7,8 @@ one folder per ``dataset[idx]`` (strided over the ranks), scores every frame, an
 ``visualization/<dataset>/<folder>/<i:08d>_<suffix or experiment name>.png`` (with ``center_frame_only``:
 ``<folder>_<suffix or experiment name>.png``).  Metrics and the per-folder log are VideoBaseModel's.
 
+``network_g.compute_dtype: bf16`` (an extension; the reference is fp32 only) runs BasicVSR / IconVSR on their bf16 forward.
+
 Inference only: building it with ``is_train`` raises NotImplementedError — training the recurrent networks (SpyNet's backward,
 ``fix_flow`` / ``flow_lr_mul``, the recurrent REDS dataset) is the follow-up."""
 import os
@@ -16,7 +18,7 @@ from collections import Counter, OrderedDict
 import torch
 
 from .. import watchdog
-from ..utils.registry import MODEL_REGISTRY
+from ..utils.registry import ARCH_REGISTRY, MODEL_REGISTRY
 from .video_base_model import VideoBaseModel
 
 
@@ -27,7 +29,15 @@ class VideoRecurrentModel(VideoBaseModel):
         if opt['is_train']:
             raise NotImplementedError('VideoRecurrentModel tests only: training the recurrent video networks (SpyNet\'s backward, '
                                       'fix_flow / flow_lr_mul, the recurrent REDS dataset) is the follow-up')
+        # network_g.compute_dtype of a network that sets its dtype after construction (BasicVSR, IconVSR keep the reference's
+        # constructor): taken out of a copy, so build_network sees the reference's keys and the caller's dict stays as it is
+        net_opt, compute_dtype = dict(opt['network_g']), None
+        if 'compute_dtype' in net_opt and hasattr(ARCH_REGISTRY.get(net_opt['type']), 'set_compute_dtype'):
+            compute_dtype = net_opt.pop('compute_dtype')
+            opt = dict(opt, network_g=net_opt)
         super().__init__(opt)
+        if compute_dtype is not None:
+            self.net_g.set_compute_dtype(compute_dtype)
         self.center_frame_only = False
 
     def test(self):

@@ -1,0 +1,226 @@
+// Stand-alone driver for the host-side code of vsr_ops_bf16.hip: the argument checks of its entry points, the trunk plan (blob and
+// workspace sizes) and the pack table it builds, run with the host sanitizers on a machine without a GPU.  Every call below returns
+// before anything is launched.  The library services that translation unit uses are stubbed here: the size queries restate the
+// documented sizes closely enough for the plan arithmetic (the real ones are compared in tests/test_vsr_bf16_host.py), the pack
+// table runner only inspects the table it is handed.
+//
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//       image_restoration_amd/csrc/vsr_ops_bf16.hip tests/helpers/vsr_bf16_host_checks.cpp \
+//       -o vsr_bf16_host_checks && ./vsr_bf16_host_checks
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+#include "../../image_restoration_amd/csrc/sr_internal.h"
+#include "../../include/sr_hip_vsr_bf16.h"
+
+static char g_err[512];
+static size_t g_rows = 0, g_image_bytes = 0;
+static bool g_rows_inside = true, g_bf16 = false;
+namespace sr {
+void set_error(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
+}
+bool prof_on() { return false; }
+void prof_begin(hipStream_t, const sr_launch_record&) {}
+void prof_end(hipStream_t) {}
+size_t pack_table_bytes(size_t entries) { return align_up((entries + 1) * sizeof(PackEntry), 256); }
+int pack_table_run(std::vector<PackEntry>& entries, void* blob, size_t image_bytes, bool bf16, hipStream_t) {
+  g_rows = entries.size();
+  g_image_bytes = image_bytes;
+  g_rows_inside = true;
+  g_bf16 = bf16;
+  for (const PackEntry& e : entries) {  // every image and bias starts inside [blob, blob + image_bytes), 256-byte aligned
+    if (e.kind != 0 || e.seg <= 0) g_rows_inside = false;
+    if ((char*)e.out < (char*)blob || (char*)e.out >= (char*)blob + image_bytes || ((uintptr_t)e.out & 255u)) g_rows_inside = false;
+    if ((char*)e.bout < (char*)blob || (char*)e.bout >= (char*)blob + image_bytes || ((uintptr_t)e.bout & 255u)) g_rows_inside = false;
+  }
+  return SR_OK;
+}
+}  // namespace sr
+static int r16(int v) { return (v + 15) / 16 * 16; }
+extern "C" int sr_conv3x3_cin_pad16(int cin, int first_seg, int seg) {
+  if (seg <= 0) return cin == first_seg ? r16(cin) : -1;
+  if (cin < first_seg || (cin - first_seg) % seg) return -1;
+  return r16(first_seg) + (cin - first_seg) / seg * r16(seg);
+}
+extern "C" size_t sr_conv3x3_packed_weight_elems_bf16(int cout, int cin, int first_seg, int seg, int) {
+  return (size_t)((cout + 31) / 32 * 32) * sr_conv3x3_cin_pad16(cin, first_seg, seg) * 9;
+}
+extern "C" size_t sr_conv3x3_packed_bias_floats(int cout) { return (size_t)((cout + 31) / 32 * 32); }
+extern "C" int sr_conv3x3_bf16(const sr_conv3x3_desc*, void*) { return SR_ELAUNCH; }  // never reached
+
+static int failures = 0;
+static int checks = 0;
+// the call must be refused with `code` and a message that names the entry point and contains `needle`
+#define REFUSED_AS(call, code, name, needle)                                                            \
+  do {                                                                                                  \
+    g_err[0] = 0;                                                                                       \
+    ++checks;                                                                                           \
+    const int rc__ = (call);                                                                            \
+    if (rc__ != (code) || !strstr(g_err, name) || !strstr(g_err, needle)) {                             \
+      printf("FAILED line %d: %s -> %d (last error: %s)\n", __LINE__, #call, rc__, g_err);              \
+      ++failures;                                                                                       \
+    }                                                                                                   \
+  } while (0)
+#define REFUSED(call, name, needle) REFUSED_AS(call, SR_EINVAL, name, needle)
+#define EXPECT(cond)                                    \
+  do {                                                  \
+    ++checks;                                           \
+    if (!(cond)) {                                      \
+      printf("FAILED line %d: %s\n", __LINE__, #cond);  \
+      ++failures;                                       \
+    }                                                   \
+  } while (0)
+
+static char* const P = (char*)256;
+static char* const Q = (char*)4096;
+static char* const ODD = (char*)260;  // 4-byte aligned only
+
+static sr_rvsr_prop_desc good() {
+  sr_rvsr_prop_desc d = {};
+  d.frame = (const float*)ODD;
+  d.frame_img_stride = 3 * 20;
+  d.prev = P;
+  d.prev_img_stride = 16 * 20 * 4;
+  d.flow = (const float*)ODD;
+  d.flow_img_stride = 2 * 20;
+  d.frame_out = Q;
+  d.frame_out_img_stride = 16 * 20 * 3;
+  d.warp_out = Q + 2 * 16 * 20;
+  d.warp_out_img_stride = 16 * 20 * 3;
+  d.n = 2;
+  d.h = 4;
+  d.w = 5;
+  d.fb = 2;
+  return d;
+}
+
+int main() {
+  const char* PI = "sr_rvsr_prop_input_bf16";
+  REFUSED(sr_rvsr_prop_input_bf16(nullptr, nullptr), PI, "null descriptor");
+  sr_rvsr_prop_desc d = good();
+  d.frame = nullptr;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "null frame");
+  d = good();
+  d.warp_out = nullptr;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "null frame");
+  d = good();
+  d.flow = nullptr;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "both");
+  d = good();
+  d.prev = nullptr;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "both");
+  for (int which = 0; which < 6; ++which) {
+    d = good();
+    (which == 0 ? d.n : which == 1 ? d.h : which == 2 ? d.w : d.fb) = which < 4 ? 0 : which == 4 ? 65535 : -3;
+    REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "bad shape");
+  }
+  d = good();
+  d.n = 65536;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "bad shape");
+  d = good();
+  d.h = 1 << 14;
+  d.w = 1 << 14;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "too large");
+  d = good();
+  d.prev = ODD;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "16-byte aligned");
+  d = good();
+  d.frame_out = ODD;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "16-byte aligned");
+  d = good();
+  d.warp_out = ODD;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "16-byte aligned");
+  d = good();
+  d.frame = (const float*)258;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "4-byte aligned");
+  d = good();
+  d.flow = (const float*)257;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "4-byte aligned");
+  d = good();
+  d.prev_img_stride += 4;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "multiples of 8");
+  d = good();
+  d.warp_out_img_stride += 1;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "multiples of 8");
+  d = good();
+  d.frame_out_img_stride += 12;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "multiples of 8");
+  d = good();
+  d.frame_img_stride = 3 * 20 - 1;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+  d = good();
+  d.flow_img_stride = 2 * 20 - 1;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+  d = good();
+  d.prev_img_stride = 16 * 20 * 2 - 8;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+  d = good();
+  d.warp_out_img_stride = 16 * 20;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+  d = good();
+  d.frame_out_img_stride = 16 * 20 - 8;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+
+  // ---- trunk configs and plans
+  const sr_vsr_trunk_cfg bad[] = {{0, 1, 1}, {-16, 1, 1}, {8, 1, 1}, {24, 1, 1}, {64, -1, 1}, {64, 1, 0}, {64, 1, 3}, {8192, 1, 1}, {64, 5000, 1}};
+  for (const sr_vsr_trunk_cfg& c : bad) {
+    REFUSED(sr_rvsr_trunk_pack_bf16(&c, (const float* const*)P, Q, nullptr), "sr_rvsr_trunk_pack_bf16", "bad config");
+    REFUSED(sr_rvsr_trunk_bf16(&c, P, P, 0, Q, 0, 1, 8, 8, nullptr, 0, nullptr), "sr_rvsr_trunk_bf16", "bad config");
+    EXPECT(sr_rvsr_trunk_packed_bytes_bf16(&c) == 0);
+    EXPECT(sr_rvsr_trunk_workspace_bytes_bf16(&c, 1, 8, 8) == 0);
+  }
+  EXPECT(sr_rvsr_trunk_packed_bytes_bf16(nullptr) == 0);
+  EXPECT(sr_rvsr_trunk_workspace_bytes_bf16(nullptr, 1, 8, 8) == 0);
+  const int feats[] = {64, 48, 16};
+  for (int nf : feats)
+    for (int segs = 1; segs <= 2; ++segs)
+      for (int nb = 0; nb <= 30; nb += 15) {
+        const sr_vsr_trunk_cfg c = {nf, nb, segs};
+        const int convs = 1 + 2 * nb;
+        const size_t bytes = sr_rvsr_trunk_packed_bytes_bf16(&c);
+        EXPECT(bytes > 0 && bytes % 256 == 0);
+        EXPECT(sr_rvsr_trunk_workspace_bytes_bf16(&c, 2, 13, 37) == 3 * sr::align_up((size_t)2 * nf * 13 * 37 * 2, 256));
+        EXPECT(sr_rvsr_trunk_workspace_bytes_bf16(&c, 0, 13, 37) == 0 && sr_rvsr_trunk_workspace_bytes_bf16(&c, 1, -1, 37) == 0);
+        // the pack table: one bf16 row per conv, every image and bias inside the blob
+        std::vector<const float*> params(2 * convs, (const float*)P);
+        EXPECT(sr_rvsr_trunk_pack_bf16(&c, params.data(), (void*)(uintptr_t)(1 << 20), nullptr) == SR_OK);
+        EXPECT(g_rows == (size_t)convs && g_rows_inside && g_bf16);
+        EXPECT(g_image_bytes + sr::pack_table_bytes(g_rows) == bytes);
+        params[2 * convs - 1] = nullptr;
+        REFUSED(sr_rvsr_trunk_pack_bf16(&c, params.data(), (void*)(uintptr_t)(1 << 20), nullptr), "sr_rvsr_trunk_pack_bf16", "null parameter");
+      }
+  const sr_vsr_trunk_cfg c = {64, 2, 1};
+  const float* two[10];
+  for (const float*& p : two) p = (const float*)P;
+  REFUSED(sr_rvsr_trunk_pack_bf16(&c, nullptr, Q, nullptr), "sr_rvsr_trunk_pack_bf16", "null argument");
+  REFUSED(sr_rvsr_trunk_pack_bf16(&c, two, nullptr, nullptr), "sr_rvsr_trunk_pack_bf16", "null argument");
+  REFUSED(sr_rvsr_trunk_pack_bf16(&c, two, ODD, nullptr), "sr_rvsr_trunk_pack_bf16", "256-byte aligned");
+
+  const char* TR = "sr_rvsr_trunk_bf16";
+  void* const WS = (void*)(uintptr_t)(1 << 20);
+  const size_t need = sr_rvsr_trunk_workspace_bytes_bf16(&c, 2, 8, 8);
+  const long long in_ns = 80 * 64, out_ns = 64 * 64;
+  REFUSED(sr_rvsr_trunk_bf16(&c, nullptr, P, in_ns, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, nullptr, in_ns, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns, nullptr, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns, Q, out_ns, 0, 8, 8, WS, need, nullptr), TR, "bad shape");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns, Q, out_ns, 2, 8, -8, WS, need, nullptr), TR, "bad shape");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns, Q, out_ns, 1, 4096, 4096, WS, need, nullptr), TR, "too large");
+  REFUSED(sr_rvsr_trunk_bf16(&c, ODD, P, in_ns, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, ODD, in_ns, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns, ODD, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns, Q, out_ns, 2, 8, 8, (char*)WS + 16, need, nullptr), TR, "aligned");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns + 4, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "multiples of 8");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns - 8, Q, out_ns, 2, 8, 8, WS, need, nullptr), TR, "smaller than the image");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P, P, in_ns, Q, out_ns - 8, 2, 8, 8, WS, need, nullptr), TR, "smaller than the image");
+  REFUSED_AS(sr_rvsr_trunk_bf16(&c, P, P, in_ns, Q, out_ns, 2, 8, 8, WS, need - 1, nullptr), SR_ENOSPACE, TR, "workspace");
+  REFUSED_AS(sr_rvsr_trunk_bf16(&c, P, P, in_ns, Q, out_ns, 2, 8, 8, nullptr, need, nullptr), SR_ENOSPACE, TR, "workspace");
+
+  printf("vsr_bf16_host_checks: %d checks, %d failures\n", checks, failures);
+  return failures ? 1 : 0;
+}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times BasicVSR inference (archs/basicvsr_arch.py) on one GPU, in the manner of tools/spynet_bench.py.
 
-    python tools/basicvsr_bench.py [--num-block 30] [--reps 20] [--warmup 5] [--out results.json]
+    python tools/basicvsr_bench.py [--num-block 30] [--reps 20] [--warmup 5] [--other-tree DIR] [--out results.json]
 
 Cases: one 180x320 clip of 15 frames, and one 64x112 clip of 7 frames (below the Winograd size rule: the trunks run on the direct
 kernels).  Three variants on the same parameters and input, the launch profiler off, each forward timed with device events;
@@ -15,11 +15,18 @@ reported:
     torch       the same network from its definition in PyTorch-ROCm ops: nn.Conv2d, F.grid_sample, F.pixel_shuffle, F.interpolate
                 (written in this tool only; its SpyNet is tools/spynet_bench.py's)
 
-Also: one trunk call alone on one frame (ms, TFLOP/s on the algorithmic 2 * 9 * cin * cout FLOP per pixel, fraction of the 157.3
+    bf16        the product with set_compute_dtype('bf16'): sr_rvsr_prop_input_bf16 + sr_rvsr_trunk_bf16 per step and the head on the
+                bf16 convs; SpyNet stays fp32 (same parameters, its own module)
+    other fp32  with --other-tree: the product of another built checkout of this project (the parent commit, say), imported as a
+                second copy of the package under another name so that it runs on its own libsr_hip.so in the same process
+
+Per variant the median and the spread (min, max) of the rounds are reported.  Also: one trunk call alone on one frame (ms, TFLOP/s on the algorithmic 2 * 9 * cin * cout FLOP per pixel, fraction of the 157.3
 TFLOP/s fp32 MFMA peak) and sr_vsr_prop_input_f32 alone (ms and bytes/s on 32 bytes per corner, pixel and block, plus the store,
-the frame and the flow), both from device events around 50 back-to-back calls.
+the frame and the flow), both from device events around 50 back-to-back calls; the same two for the bf16 entry points (fraction of
+the 2500.0 TFLOP/s dense bf16 MFMA peak).
 """
 import argparse
+import importlib.util
 import json
 import os
 import statistics
@@ -37,6 +44,21 @@ from image_restoration_amd.archs.basicvsr_arch import BasicVSR  # noqa: E402
 from spynet_bench import TorchSpyNet, timed, torch_warp  # noqa: E402
 
 PEAK_TFLOPS = 157.3
+PEAK_TFLOPS_BF16 = 2500.0
+
+
+def other_basicvsr(tree):
+    """BasicVSR of another checkout of this project, from a second copy of the package under the name ``sr_other_tree`` (relative
+    imports keep it on its own modules and its own library)."""
+    pkg = os.path.join(tree, 'image_restoration_amd')
+    spec = importlib.util.spec_from_file_location('sr_other_tree', os.path.join(pkg, '__init__.py'), submodule_search_locations=[pkg])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules['sr_other_tree'] = mod
+    spec.loader.exec_module(mod)
+    arch = importlib.import_module('sr_other_tree.archs.basicvsr_arch')
+    lib = importlib.import_module('sr_other_tree._lib')
+    assert os.path.realpath(lib.LIB_PATH).startswith(os.path.realpath(tree)), lib.LIB_PATH
+    return arch.BasicVSR
 
 
 def per_layer_trunk(net, trunk, src, out):
@@ -142,6 +164,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--out', default=None)
     ap.add_argument('--wino-off', action='store_true', help='sr_dev_set_wino_f32(0): the product path on the direct kernels too')
+    ap.add_argument('--other-tree', default=None, help='root of another built checkout of this project: its fp32 product as a further row')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('basicvsr_bench needs a GPU: timings are device timings')
@@ -152,6 +175,12 @@ def main():
     torch.manual_seed(0)
     net = BasicVSR(num_feat=64, num_block=args.num_block).to(dev).eval()
     ref = TorchBasicVSR(net).to(dev).eval()
+    net16 = BasicVSR(num_feat=64, num_block=args.num_block).to(dev).eval().set_compute_dtype('bf16')
+    net16.load_state_dict(net.state_dict())
+    other = None
+    if args.other_tree:
+        other = other_basicvsr(args.other_tree)(num_feat=64, num_block=args.num_block).to(dev).eval()
+        other.load_state_dict(net.state_dict())
     nf, nb = 64, args.num_block
     rows = []
     with torch.no_grad():
@@ -159,7 +188,12 @@ def main():
             x = torch.rand(1, n, 3, h, w, device=dev)
             y = net(x)
             d_layer, d_torch = float((per_layer_forward(net, x) - y).abs().max()), float((ref(x) - y).abs().max())
-            variants = (('product', lambda: net(x)), ('per-layer', lambda: per_layer_forward(net, x)), ('torch', lambda: ref(x)))
+            variants = (('product', lambda: net(x)), ('per-layer', lambda: per_layer_forward(net, x)), ('torch', lambda: ref(x)),
+                        ('bf16', lambda: net16(x)))
+            d_bf16, d_other = float((net16(x) - y).abs().max()), None
+            if other is not None:
+                variants += (('other fp32', lambda: other(x)),)
+                d_other = float((other(x) - y).abs().max())
             # interleaved at the level of single forwards: a round runs every variant once; median over the rounds
             for _ in range(args.warmup):
                 for _, fn in variants:
@@ -168,10 +202,12 @@ def main():
             for _ in range(args.reps):
                 for k, fn in variants:
                     ms[k].append(timed(fn, 1, 0))
-            r = dict(case=f'{n} frames {h}x{w}', frames=n, max_abs_diff_per_layer=d_layer, max_abs_diff_torch=d_torch)
+            r = dict(case=f'{n} frames {h}x{w}', frames=n, max_abs_diff_per_layer=d_layer, max_abs_diff_torch=d_torch,
+                     max_abs_diff_bf16=d_bf16, max_abs_diff_other=d_other)
             for k, _ in variants:
                 r[k + '_ms'] = statistics.median(ms[k])
                 r[k + '_ms_per_frame'] = statistics.median(ms[k]) / n
+                r[k + '_ms_min'], r[k + '_ms_max'] = min(ms[k]), max(ms[k])
             # one trunk call and one step input alone
             tin = torch.randn(1, 9, h, w, 8, device=dev)
             tin[:, 0, :, :, 3:] = 0
@@ -183,6 +219,17 @@ def main():
             nbytes = 4.0 * h * w * (5 * nf + 2 + 3 + 8)
             r.update(trunk_ms=t_trunk, trunk_tflops=flops / t_trunk / 1e9, trunk_of_peak=flops / t_trunk / 1e9 / PEAK_TFLOPS,
                      trunk_launches=1 + 2 * nb, prop_input_ms=t_prop, prop_input_gbytes_per_s=nbytes / t_prop / 1e6)
+            # the same two on the bf16 entry points
+            tin16 = torch.randn(1, 5, h, w, 16, device=dev).bfloat16()
+            tin16[:, 0, :, :, 3:] = 0
+            out16 = H.CB16.empty(1, nf, h, w, dev)
+            t_trunk16 = burst(lambda: net16.forward_trunk.run(H.CB16(tin16), out16))
+            prev16 = H.CB16(torch.randn(1, 4, h, w, 16, device=dev).bfloat16())
+            t_prop16 = burst(lambda: H.vsr_prop_input_bf16(x[:, 0], prev16, flow, H.CB16(tin16, 1, 4), H.CB16(tin16, 0, 1)))
+            nbytes16 = 1.0 * h * w * (5 * 2 * nf + 8 + 12 + 32)
+            r.update(trunk_bf16_ms=t_trunk16, trunk_bf16_tflops=flops / t_trunk16 / 1e9,
+                     trunk_bf16_of_peak=flops / t_trunk16 / 1e9 / PEAK_TFLOPS_BF16, prop_input_bf16_ms=t_prop16,
+                     prop_input_bf16_gbytes_per_s=nbytes16 / t_prop16 / 1e6)
             rows.append(r)
     for r in rows:
         print(f'{r["case"]}: product {r["product_ms"]:.2f} ms ({r["product_ms_per_frame"]:.2f} / frame), per-layer '
@@ -190,6 +237,13 @@ def main():
               f'max|diff| per-layer {r["max_abs_diff_per_layer"]:.2e} torch {r["max_abs_diff_torch"]:.2e}')
         print(f'    trunk call ({r["trunk_launches"]} launches) {r["trunk_ms"]:.3f} ms = {r["trunk_tflops"]:.1f} TFLOP/s '
               f'({r["trunk_of_peak"]:.2f} of peak); prop input {1000 * r["prop_input_ms"]:.1f} us = {r["prop_input_gbytes_per_s"]:.0f} GB/s')
+        print(f'    bf16 {r["bf16_ms"]:.2f} ms ({r["bf16_ms_per_frame"]:.2f} / frame) [{r["bf16_ms_min"]:.2f}, {r["bf16_ms_max"]:.2f}]; product '
+              f'rounds [{r["product_ms_min"]:.2f}, {r["product_ms_max"]:.2f}]; max|bf16 - fp32| {r["max_abs_diff_bf16"]:.2e}')
+        if 'other fp32_ms' in r:
+            print(f'    other fp32 {r["other fp32_ms"]:.2f} ms [{r["other fp32_ms_min"]:.2f}, {r["other fp32_ms_max"]:.2f}]; max|other - '
+                  f'product| {r["max_abs_diff_other"]:.2e}')
+        print(f'    bf16 trunk call {r["trunk_bf16_ms"]:.3f} ms = {r["trunk_bf16_tflops"]:.1f} TFLOP/s ({r["trunk_bf16_of_peak"]:.3f} of the bf16 '
+              f'peak); bf16 prop input {1000 * r["prop_input_bf16_ms"]:.1f} us = {r["prop_input_bf16_gbytes_per_s"]:.0f} GB/s')
     if args.out:
         with open(args.out, 'w') as f:
             json.dump(dict(num_block=nb, wino_off=args.wino_off, reps=args.reps, warmup=args.warmup, peak_tflops=PEAK_TFLOPS, rows=rows), f, indent=1)
