@@ -1,6 +1,7 @@
 """ctypes binding of libsr_hip.so (C ABI declared in include/sr_hip.h, include/sr_hip_ridnet.h, include/sr_hip_gfpgan.h,
 include/sr_hip_edsr.h, include/sr_hip_ca_bf16.h, include/sr_hip_dcn.h, include/sr_hip_edvr.h, include/sr_hip_edvr_bf16.h,
-include/sr_hip_stylegan2.h, include/sr_hip_train_groups.h, include/sr_hip_degrade.h and include/sr_hip_flow.h).
+include/sr_hip_stylegan2.h, include/sr_hip_train_groups.h, include/sr_hip_degrade.h, include/sr_hip_flow.h and
+include/sr_hip_flow_bwd.h).
 
 There is deliberately NO fallback: if the HIP library is missing or a call fails the
 caller gets an exception.  The product path never routes through ``oracle/`` or
@@ -506,6 +507,34 @@ FLOW_SIGNATURES = {
 }
 
 
+class Conv7x7DgradDesc(C.Structure):
+    """struct sr_conv7x7_dgrad_desc (include/sr_hip_flow_bwd.h)."""
+    _fields_ = [('dy', C.c_void_p), ('dy_img_stride', C.c_longlong), ('cin', C.c_int), ('cout', C.c_int), ('n', C.c_int),
+                ('h', C.c_int), ('w', C.c_int), ('packed', C.c_void_p), ('dx', C.c_void_p), ('dx_img_stride', C.c_longlong),
+                ('mask', C.c_void_p), ('mask_img_stride', C.c_longlong)]
+
+
+class Conv7x7WgradDesc(C.Structure):
+    """struct sr_conv7x7_wgrad_desc (include/sr_hip_flow_bwd.h)."""
+    _fields_ = [('x', C.c_void_p), ('x_img_stride', C.c_longlong), ('dy', C.c_void_p), ('dy_img_stride', C.c_longlong),
+                ('cin', C.c_int), ('cout', C.c_int), ('n', C.c_int), ('h', C.c_int), ('w', C.c_int), ('scale', C.c_float),
+                ('dweight', C.c_void_p), ('dbias', C.c_void_p), ('accumulate', C.c_int), ('slab', C.c_void_p),
+                ('slab_bytes', C.c_size_t)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_flow_bwd.h declares
+FLOW_BWD_SIGNATURES = {
+    'sr_conv7x7_dgrad_instance': (C.c_int, [_I, _I]),
+    'sr_conv7x7_dgrad_packed_floats': (C.c_size_t, [_I, _I]),
+    'sr_conv7x7_dgrad_pack_f32': (C.c_int, [_P, _I, _I, _P, _P]),
+    'sr_conv7x7_dgrad_f32': (C.c_int, [C.POINTER(Conv7x7DgradDesc), _P]),
+    'sr_conv7x7_wgrad_slab_bytes': (C.c_size_t, [_I] * 5),
+    'sr_conv7x7_wgrad_f32': (C.c_int, [C.POINTER(Conv7x7WgradDesc), _P]),
+    'sr_spynet_level_input_bwd_f32': (C.c_int, [_P] * 6 + [_I] * 3 + [_P]),
+    'sr_resize_bilinear_adjoint_f32': (C.c_int, [_P, _P] + [_I] * 5 + [_P]),
+}
+
+
 class VsrPropDesc(C.Structure):
     """struct sr_vsr_prop_desc (include/sr_hip_vsr.h)."""
     _fields_ = [('frame', C.c_void_p), ('frame_img_stride', C.c_longlong), ('prev', C.c_void_p), ('prev_img_stride', C.c_longlong),
@@ -560,7 +589,8 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(RIDNET_SIGNATURES.items()) + list(GFPGAN_SIGNATURES.items()) \
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
-            + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()) + list(VSR_BF16_SIGNATURES.items()):
+            + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()) + list(VSR_BF16_SIGNATURES.items()) \
+            + list(FLOW_BWD_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

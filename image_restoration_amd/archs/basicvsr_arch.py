@@ -23,7 +23,8 @@ sr_rvsr_prop_input_bf16 and one sr_rvsr_trunk_bf16, the head runs on the bf16 co
 clip, SpyNet and the flows stay fp32, so ``get_flow`` is the same bits in both modes; ``num_feat % 16 == 0`` is required.
 
 Inference only, x4: outputs never carry a grad_fn, and a forward that would need a graph (train mode, grad enabled,
-something requiring grad) raises NotImplementedError — training (SpyNet's backward, the recurrent backward) is the follow-up.
+something requiring grad) raises NotImplementedError — training (the recurrent backward, on top of SpyNet's backward in
+archs/spynet_autograd.py) is the follow-up.
 ValueError, before anything is launched, for: fewer than two frames (the reference's ``get_flow`` cannot reshape an empty batch),
 channels other than 3, a dtype other than fp32, a side of 32 pixels or fewer (SpyNet's rule), ``num_feat % 8 != 0``.
 """

@@ -44,7 +44,7 @@ class HipGenerator(nn.Module):
 
     def packed(self, conv, mode=0, bf16=False):
         """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter):
-        sr_conv3x3_pack_f32 for 3x3 convs (every dilation), sr_conv7x7_pack_f32 for SpyNet's 7x7 convs, sr_convk_pack_f32 for any
+        sr_conv3x3_pack_f32 for 3x3 convs (every dilation), sr_conv7x7_pack_f32 / sr_conv7x7_dgrad_pack_f32 for SpyNet's 7x7 convs, sr_convk_pack_f32 for any
         other kernel size; rebuilt when the
         parameter storage, its version, the FlatAdam epoch of the parameter or this net's generation (invalidate_packed) changed.
         Not hip_ops.cached_pack: that cache is keyed on the process-global epoch, so one net's invalidate_packed() would repack
@@ -138,7 +138,8 @@ class GradRouter:
 
     def wgrad(self, conv, src, d, scale=1.0, dilation=None):
         """weight / bias gradient of ``conv`` from its source and its pre-activation output gradient: the dense 3x3 path of
-        sr_conv3x3_wgrad_f32, or sr_convd_wgrad_f32 for a dilated or 1x1 conv.  No launch when neither is wanted."""
+        sr_conv3x3_wgrad_f32, sr_conv7x7_wgrad_f32 for SpyNet's 7x7 convs, or sr_convd_wgrad_f32 for a dilated or 1x1 conv.  No
+        launch when neither is wanted."""
         iw, ib = self.index[id(conv.weight)], self.index[id(conv.bias)]
         if not (self.to_sink or self.need_p[iw] or self.need_p[ib]):
             return
@@ -146,6 +147,8 @@ class GradRouter:
         k = conv.weight.shape[2]
         if dilation is None and k == 3:
             res = hip_ops.conv3x3_wgrad(src, d, conv.out_channels, conv.in_channels, scale=scale, out=out)
+        elif dilation is None and k == 7:
+            res = hip_ops.conv7x7_wgrad(src, d, conv.out_channels, conv.in_channels, scale=scale, out=out)
         else:
             res = hip_ops.convd_wgrad(src, d, conv.out_channels, conv.in_channels, k, dilation or 1, scale=scale, out=out)
         if not self.to_sink:

@@ -17,10 +17,13 @@ The coarsest level's incoming flow is zero by construction, and the reference's 
 pads that zero flow (every finer level is exactly twice the size of the one before): level 0 is ``up = 0``, ``warp = supp``, and
 there is no pad kernel.
 
-Inference only: outputs never carry a grad_fn, and a forward that would need a graph (train mode, grad enabled, something
-requiring grad) raises NotImplementedError — SpyNet's backward (7x7 weight and data gradients through the levels) is the
-follow-up.  fp32 only.  ValueError for ``ref`` and ``supp`` of different sizes, channels other than 3, and a side of 32 pixels or
-fewer (the reference fails there: its level-0 flow is empty).
+Inference is the default: outputs carry no grad_fn, and a forward that would need a graph (train mode, grad enabled, a parameter
+requiring grad) raises NotImplementedError naming ``set_autograd(True)``.  After ``net.set_autograd(True)`` such a forward goes
+through ``archs/spynet_autograd.py`` and returns a flow with a grad_fn: the backward walks the levels from fine to coarse with the
+7x7 weight and data gradients, the level-input adjoint and the resize adjoint of include/sr_hip_flow_bwd.h.
+Gradients with respect to the frames are not computed: ``ref`` or ``supp`` requiring grad raises NotImplementedError.  fp32 only.
+ValueError for ``ref`` and ``supp`` of different sizes, channels other than 3, and a side of 32 pixels or fewer (the reference
+fails there: its level-0 flow is empty).
 """
 import math
 
@@ -71,6 +74,14 @@ class SpyNet(HipGenerator):
         for name, values in (('mean', _MEAN), ('std', _STD)):
             self.register_buffer(name, torch.tensor(values, dtype=torch.float32).view(1, 3, 1, 1))
         self._norm = None
+        self._autograd = False
+
+    def set_autograd(self, enabled=True):
+        """Whether a forward that needs a graph (train mode, grad enabled, a parameter requiring grad) builds one
+        (archs/spynet_autograd.py) instead of being refused.  Off by default; set after construction, like set_compute_dtype.
+        Returns self."""
+        self._autograd = bool(enabled)
+        return self
 
     def _drop_device_caches(self):
         self._norm = None
@@ -82,9 +93,10 @@ class SpyNet(HipGenerator):
             self._norm = (sig, self.mean.flatten().tolist(), self.std.flatten().tolist())
         return self._norm[1], self._norm[2]
 
-    def process(self, ref, supp, levels=None):
+    def process(self, ref, supp, levels=None, keep=None):
         """The pyramid on a batch whose sides are multiples of 32: the flow [N, 2, H, W]; ``levels`` (a list) receives the flow
-        after each level."""
+        after each level; ``keep`` (a list) receives per level what the backward reads: the level's ``supp``, its input block
+        ``x0``, the four post-ReLU activations ``acts`` and ``up``."""
         n = ref.size(0)
         mean, std = self._norm_host()
         both = hip_ops.spynet_preprocess(torch.cat([ref, supp], 0), mean, std)
@@ -95,20 +107,28 @@ class SpyNet(HipGenerator):
         for level, imgs in enumerate(pyramid):
             x, up = hip_ops.spynet_level_input(imgs[:n], imgs[n:], flow)
             convs = self.basic_module[level].convs()
+            if keep is not None:   # without it an activation is freed as soon as the next conv has read it
+                keep.append(dict(supp=imgs[n:], x0=x, acts=[], up=up))
             for conv in convs[:-1]:
                 x = hip_ops.conv7x7(x, self.packed(conv), relu=True)
+                if keep is not None:
+                    keep[-1]['acts'].append(x)
             flow = hip_ops.conv7x7(x, self.packed(convs[-1]), res1=up)
             if levels is not None:
                 levels.append(hip_ops.cb_to_nchw(flow, 2))
         return hip_ops.cb_to_nchw(flow, 2)
 
-    def run_forward(self, ref, supp, levels=None):
+    def run_forward(self, ref, supp, levels=None, keep=None):
+        """The whole forward on device tensors.  ``keep``: a dict that receives ``size`` = (h, w, h_floor, w_floor) and ``levels``,
+        the per-level tensors ``process`` saves for the backward."""
         h, w = ref.size(2), ref.size(3)
         h_floor, w_floor = 32 * math.ceil(h / 32), 32 * math.ceil(w / 32)
         if (h_floor, w_floor) != (h, w):
             both = hip_ops.resize_bilinear(torch.cat([ref, supp], 0), (h_floor, w_floor))
             ref, supp = both[:ref.size(0)], both[ref.size(0):]
-        flow = self.process(ref, supp, levels)
+        if keep is not None:
+            keep['size'], keep['levels'] = (h, w, h_floor, w_floor), []
+        flow = self.process(ref, supp, levels, None if keep is None else keep['levels'])
         if (h_floor, w_floor) != (h, w):
             flow = hip_ops.resize_bilinear(flow, (h, w))
             ratio = torch.tensor([float(w) / float(w_floor), float(h) / float(h_floor)], dtype=torch.float32, device=flow.device)
@@ -130,7 +150,14 @@ class SpyNet(HipGenerator):
                                   '.to("cuda")')
         if self.training and torch.is_grad_enabled() and (ref.requires_grad or supp.requires_grad
                                                           or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError('SpyNet runs inference only: call .eval() (or run under torch.no_grad()); its backward (the '
-                                      '7x7 weight and data gradients through the pyramid levels) is the follow-up')
+            if not self._autograd:
+                raise NotImplementedError('SpyNet runs inference only by default: call .eval() (or run under torch.no_grad()), or '
+                                          'enable its backward (the 7x7 weight and data gradients through the pyramid levels) with '
+                                          'set_autograd(True)')
+            if ref.requires_grad or supp.requires_grad:
+                raise NotImplementedError('SpyNet computes no image gradients: ref and supp must not require grad (the frames are '
+                                          'data; only the parameters are differentiated)')
+            from .spynet_autograd import spynet_apply
+            return spynet_apply(self, ref.contiguous(), supp.contiguous())
         with torch.no_grad():
             return self.run_forward(ref.contiguous(), supp.contiguous())

@@ -1078,5 +1078,11 @@ extern "C" const char* sr_kernel_name(int id) {
     return bnames[id - 161];
   }
   if (id == 167) return "vsr_prop_input_bf16_kernel";  // vsr_ops_bf16.hip (include/sr_hip_vsr_bf16.h); 166 stays unnamed
+  if (id >= 169 && id < 177) {  // flow_bwd_ops.hip (include/sr_hip_flow_bwd.h); 168 stays unnamed
+    static const char* qnames[8] = {"conv7x7_dgrad_f32_kernelILi1ELi4EE", "conv7x7_dgrad_f32_kernelILi2ELi2EE", "conv7x7_dgrad_pack_kernel",
+                                    "conv7x7_wgrad_f32_kernel",           "conv7x7_wgrad_reduce_kernel",        "spynet_level_dup_kernel",
+                                    "spynet_level_upT_kernel",            "resize_bilinear_adjoint_kernel"};
+    return qnames[id - 169];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

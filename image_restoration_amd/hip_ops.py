@@ -1487,24 +1487,33 @@ def conv7x7_instance(cout, cin):
 
 
 class PackedConv7x7:
-    """MFMA operand image (weights, then bias) of one 7x7 conv of SpyNet — sr_conv7x7_pack_f32."""
+    """MFMA operand image of one 7x7 conv of SpyNet: mode 0 the forward image (weights, then bias) — sr_conv7x7_pack_f32;
+    mode 1 the data-gradient image (the weights flipped and transposed, no bias) — sr_conv7x7_dgrad_pack_f32."""
 
     def __init__(self, weight, bias=None, mode=0):
         _need_cuda(weight, 'PackedConv7x7')
-        _arg(mode == 0, 'PackedConv7x7: only the forward image exists')
+        _arg(mode in (0, 1), f'PackedConv7x7: mode {mode} is not supported; supported: 0 (forward), 1 (data gradient)')
+        _arg(mode == 0 or bias is None, 'PackedConv7x7: the data-gradient image has no bias')
+        self.mode = mode
         _arg(weight.dim() == 4 and tuple(weight.shape[2:]) == (7, 7) and weight.dtype == torch.float32,
              f'PackedConv7x7: needs an fp32 [cout, cin, 7, 7] weight, got {weight.dtype} {tuple(weight.shape)}')
         _arg(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (weight.size(0),)), 'PackedConv7x7: bias does not fit')
         weight = weight.detach().contiguous()
         bias = None if bias is None else bias.detach().contiguous()
         self.cout, self.cin = weight.shape[:2]
-        self.instance = conv7x7_instance(self.cout, self.cin)
+        self.instance = conv7x7_instance(self.cout, self.cin)     # refuses a pair that is not served
+        if mode == 1:
+            self.instance = _lib.load().sr_conv7x7_dgrad_instance(self.cout, self.cin)
+            self.w = torch.empty(_lib.load().sr_conv7x7_dgrad_packed_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
+            _launch_arg('sr_conv7x7_dgrad_pack_f32', weight.device, weight.data_ptr(), self.cout, self.cin, self.w.data_ptr())
+            return
         self.w = torch.empty(_lib.load().sr_conv7x7_packed_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
         _launch_arg('sr_conv7x7_pack_f32', weight.device, weight.data_ptr(), _p(bias), self.cout, self.cin, self.w.data_ptr())
 
 
 def conv7x7(src, pc, out=None, *, relu=False, res1=None):
     """out = [relu](conv7x7(src) + bias) [+ res1] on CB8, stride 1, pad 3 — one sr_conv7x7_f32 launch.  ``pc``: PackedConv7x7."""
+    _arg(getattr(pc, 'mode', 0) == 0, 'conv7x7: needs the forward image (mode 0)')
     _arg(src.channels == pc.cin, f'conv7x7: source has {src.channels} channels, the weight image {pc.cin}')
     if out is None:
         out = CB8.empty(src.n, pc.cout, src.h, src.w, src.device)
@@ -1610,6 +1619,73 @@ def avgpool2x2(x):
     out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
     _launch_arg('sr_avgpool2x2_f32', x.device, x.data_ptr(), out.data_ptr(), n * c, h, w)
     return out
+
+
+# ---- SpyNet's backward: 7x7 data and weight gradients, level-input and resize adjoints (include/sr_hip_flow_bwd.h) ----
+
+def conv7x7_dgrad(dy, pc, out=None, *, mask=None):
+    """dx = (7x7 data gradient of ``dy``) * (mask > 0) on CB8 — one sr_conv7x7_dgrad_f32 launch.  ``pc``: PackedConv7x7(mode=1);
+    ``dy`` holds the conv's output gradient (ceil(cout / 8) blocks), ``mask`` the post-ReLU activation that fed the conv."""
+    _arg(getattr(pc, 'mode', 0) == 1, 'conv7x7_dgrad: needs the data-gradient image (mode 1)')
+    dyb = (pc.cout + 7) // 8
+    _arg(dy.cbn == dyb, f'conv7x7_dgrad: dy has {dy.cbn} channel blocks, the weight image {dyb}')
+    if out is None:
+        out = CB8.empty(dy.n, pc.cin, dy.h, dy.w, dy.device)
+    _arg((out.n, out.h, out.w) == (dy.n, dy.h, dy.w) and out.cbn == pc.cin // 8, 'conv7x7_dgrad: output window does not fit')
+    _arg(mask is None or ((mask.n, mask.h, mask.w) == (dy.n, dy.h, dy.w) and mask.cbn == pc.cin // 8), 'conv7x7_dgrad: mask does not fit')
+    d = _lib.Conv7x7DgradDesc()
+    d.dy, d.dy_img_stride, d.cin, d.cout, d.n, d.h, d.w = dy.ptr, dy.img_stride, pc.cin, pc.cout, dy.n, dy.h, dy.w
+    d.packed, d.dx, d.dx_img_stride = pc.w.data_ptr(), out.ptr, out.img_stride
+    if mask is not None:
+        d.mask, d.mask_img_stride = mask.ptr, mask.img_stride
+    _launch_arg('sr_conv7x7_dgrad_f32', dy.device, C.byref(d))
+    return out
+
+
+def conv7x7_wgrad(src, dy, cout, cin, *, scale=1.0, want_bias=True, out=None):
+    """(dweight [cout, cin, 7, 7], dbias [cout]) of a 7x7 conv of SpyNet whose source was ``src`` (CB8) and whose pre-activation
+    output gradient is ``dy`` (CB8) — one sr_conv7x7_wgrad_f32 call (tiles + fixed-order reduction).  ``out`` = (dweight, dbias
+    or None): device pointers (ints) the gradients are ADDED into (accumulate = 1, e.g. a FlatAdam gradient arena) instead."""
+    _arg((cin, cout) in CONV7X7_SHAPES, f'conv7x7_wgrad: (cin, cout) = ({cin}, {cout}) is not supported; supported: {CONV7X7_SHAPES}')
+    _arg(src.cbn == cin // 8 and dy.cbn == (cout + 7) // 8 and (dy.n, dy.h, dy.w) == (src.n, src.h, src.w),
+         'conv7x7_wgrad: src / dy do not fit the pair')
+    nbytes = _lib.load().sr_conv7x7_wgrad_slab_bytes(src.n, src.h, src.w, cout, cin)
+    slab = scratch(src.device, nbytes, 'slab7')
+    dw, db, target = _wgrad_targets(out, (cout, cin, 7, 7), want_bias, src.device)
+    d = _lib.Conv7x7WgradDesc()
+    d.x, d.x_img_stride, d.dy, d.dy_img_stride = src.ptr, src.img_stride, dy.ptr, dy.img_stride
+    d.cin, d.cout, d.n, d.h, d.w, d.scale = cin, cout, src.n, src.h, src.w, scale
+    d.dweight, d.dbias, d.accumulate = target
+    d.slab, d.slab_bytes = slab.data_ptr(), nbytes
+    _launch_arg('sr_conv7x7_wgrad_f32', src.device, C.byref(d))
+    return None if out is not None else (dw, db)
+
+
+def spynet_level_input_bwd(supp, up, g_in, g_res):
+    """The gradient of the coarser level's flow (a one-block CB8 tensor at H / 2 x W / 2) from a level's ``supp`` [N, 3, H, W],
+    its saved ``up`` block, the gradient ``g_in`` of its input block and the gradient ``g_res`` of its output flow (one-block CB8
+    windows at H x W) — one sr_spynet_level_input_bwd_f32 call (two launches)."""
+    n, _, h, w = _image_batch(supp, 'spynet_level_input_bwd', 3)
+    _arg(h % 2 == 0 and w % 2 == 0, f'spynet_level_input_bwd: {h}x{w} is not even')
+    for t, name in ((up, 'up'), (g_in, 'g_in'), (g_res, 'g_res')):
+        _arg(isinstance(t, CB8) and t.cb0 == 0 and tuple(t.buf.shape) == (n, 1, h, w, 8) and t.device == supp.device,
+             f'spynet_level_input_bwd: {name} must be one CB8 block at {h}x{w}')
+    d_up = torch.empty((n, h, w, 2), dtype=torch.float32, device=supp.device)
+    g_prev = CB8.empty(n, 8, h // 2, w // 2, supp.device)
+    _launch_arg('sr_spynet_level_input_bwd_f32', supp.device, supp.data_ptr(), up.ptr, g_in.ptr, g_res.ptr, d_up.data_ptr(),
+                g_prev.ptr, n, h, w)
+    return g_prev
+
+
+def resize_bilinear_adjoint(dy, size):
+    """The transpose of F.interpolate(size=dy.shape[2:], mode='bilinear', align_corners=False) applied to ``dy`` [N, C, Hd, Wd]:
+    the gradient [N, C, *size] of the resize's input — one sr_resize_bilinear_adjoint_f32 launch."""
+    n, c, hd, wd = _image_batch(dy, 'resize_bilinear_adjoint')
+    hs, ws = int(size[0]), int(size[1])
+    _arg(hs > 0 and ws > 0, f'resize_bilinear_adjoint: bad size {size}')
+    dx = torch.empty((n, c, hs, ws), dtype=torch.float32, device=dy.device)
+    _launch_arg('sr_resize_bilinear_adjoint_f32', dy.device, dy.data_ptr(), dx.data_ptr(), n * c, hs, ws, hd, wd)
+    return dx
 
 
 # ---- the recurrent video networks: propagation step input and trunk driver (include/sr_hip_vsr.h) ----

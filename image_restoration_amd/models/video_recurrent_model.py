@@ -9,8 +9,9 @@ one folder per ``dataset[idx]`` (strided over the ranks), scores every frame, an
 
 ``network_g.compute_dtype: bf16`` (an extension; the reference is fp32 only) runs BasicVSR / IconVSR on their bf16 forward.
 
-Inference only: building it with ``is_train`` raises NotImplementedError — training the recurrent networks (SpyNet's backward,
-``fix_flow`` / ``flow_lr_mul``, the recurrent REDS dataset) is the follow-up."""
+Inference only: building it with ``is_train`` raises NotImplementedError — training the recurrent networks (the recurrent backward,
+``fix_flow`` / ``flow_lr_mul``, the recurrent REDS dataset; SpyNet's own backward exists: ``SpyNet.set_autograd``) is the
+follow-up."""
 import os
 import os.path as osp
 from collections import Counter, OrderedDict

@@ -86,12 +86,52 @@ class TorchSpyNet(nn.Module):
         return flow * flow.new_tensor([w / wf, h / hf]).view(1, 2, 1, 1)
 
 
+def backward_rows(net, ref_net, n, dev, row):
+    """--backward: per conv of a basic module the masked data gradient (sr_conv7x7_dgrad_f32 against torch.nn.grad.conv2d_input
+    and the mask product) and the weight + bias gradient (sr_conv7x7_wgrad_f32 against torch.nn.grad.conv2d_weight and a sum) on
+    --pairs maps of 192x320; then forward + backward of the whole network, HIP autograd against PyTorch autograd of the same ops
+    on the same parameters, at 180x320 and at 64x64."""
+    for p in net.basic_module[5].convs():
+        cin, cout = p.in_channels, p.out_channels
+        x, dy = torch.randn(n, cin, 192, 320, device=dev), torch.randn(n, cout, 192, 320, device=dev)
+        src, d, pc = H.nchw_to_cb8(x), H.nchw_to_cb8(dy), net.packed(p, 1)
+        flops = 2.0 * 49 * cin * cout * n * 192 * 320
+        w = p.weight.detach()
+        row(f'dgrad7x7 {cout}->{cin} {n}x192x320', lambda: H.conv7x7_dgrad(d, pc, mask=src),
+            lambda: torch.nn.grad.conv2d_input(x.shape, w, dy, padding=3) * (x > 0), flops, instance=pc.instance)
+        row(f'wgrad7x7 {cin}->{cout} {n}x192x320', lambda: H.conv7x7_wgrad(src, d, cout, cin),
+            lambda: (torch.nn.grad.conv2d_weight(x, w.shape, dy, padding=3), dy.sum((0, 2, 3))), flops)
+        del x, dy, src, d
+    net.train().set_autograd(True)
+    ref_net.train()
+    params = list(net.parameters())
+    for h, w in ((180, 320), (64, 64)):
+        a, b = torch.rand(n, 3, h, w, device=dev), torch.rand(n, 3, h, w, device=dev)
+        g = torch.randn(n, 2, h, w, device=dev)
+
+        def step(model):
+            for q in params:
+                q.grad = None
+            (model(a, b) * g).sum().backward()
+        step(net)
+        mine = [q.grad.clone() for q in params]
+        step(ref_net)
+        diff = max(float((m - q.grad).norm() / q.grad.norm()) for m, q in zip(mine, params))
+        hf, wf = math.ceil(h / 32) * 32, math.ceil(w / 32) * 32
+        flops = 3 * 479808.0 * n * sum((hf >> k) * (wf >> k) for k in range(6))
+        row(f'SpyNet fwd+bwd {n} pairs {h}x{w}', lambda: step(net), lambda: step(ref_net), flops, max_rel_l2_diff=diff)
+    net.eval().set_autograd(False)
+    ref_net.eval()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=8)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--backward', action='store_true', help='time the backward rows instead: each data and weight gradient, '
+                    'and forward + backward of the whole network')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('spynet_bench needs a GPU: timings are device timings')
@@ -111,14 +151,16 @@ def main():
                      hip_of_peak=flops / t_hip / 1e9 / PEAK_TFLOPS)
         rows.append(r)
 
+    if args.backward:
+        backward_rows(net, ref_net, n, dev, row)
     with torch.no_grad():
-        for h, w in ((180, 320), (64, 64)):
+        for h, w in (() if args.backward else ((180, 320), (64, 64))):
             a, b = torch.rand(n, 3, h, w, device=dev), torch.rand(n, 3, h, w, device=dev)
             diff = float((net(a, b) - ref_net(a, b)).abs().max())
             hf, wf = math.ceil(h / 32) * 32, math.ceil(w / 32) * 32
             flops = 479808.0 * n * sum((hf >> k) * (wf >> k) for k in range(6))
             row(f'SpyNet {n} pairs {h}x{w}', lambda: net(a, b), lambda: ref_net(a, b), flops, max_abs_diff=diff)
-        for lv_conv, p in enumerate(net.basic_module[5].convs()):
+        for lv_conv, p in enumerate(() if args.backward else net.basic_module[5].convs()):
             cin, cout = p.in_channels, p.out_channels
             x = torch.randn(n, cin, 192, 320, device=dev)
             src, pc = H.nchw_to_cb8(x), net.packed(p)
@@ -131,7 +173,7 @@ def main():
             row(f'conv7x7 {cin}->{cout} {n}x192x320', hip, ref, 2.0 * 49 * cin * cout * n * 192 * 320, instance=pc.instance)
             del x, src
         x, flow = torch.randn(n, 64, 180, 320, device=dev), torch.randn(n, 180, 320, 2, device=dev) * 4
-        for pm in ('zeros', 'border'):
+        for pm in (() if args.backward else ('zeros', 'border')):
             row(f'flow_warp {n}x64x180x320 {pm}', lambda: flow_warp(x, flow, padding_mode=pm), lambda: torch_warp(x, flow, pm))
     print(f'{"case":36s} {"HIP ms":>9s} {"torch ms":>9s} {"HIP TFLOP/s":>12s} {"of peak":>8s} {"torch TFLOP/s":>14s}')
     for r in rows:
