@@ -44,6 +44,28 @@ _FLOW_BUDGET = 1 << 30      # bytes of SpyNet activations alive at once
 _RECON_BUDGET = 2 << 30     # bytes of high-resolution activations alive at once
 
 
+class _Layout:
+    """What the compute dtype decides, in one record: whether it is bf16, the window class, its channels per block and element
+    type, the step-input launch, the trunk call and the stem of its pack symbols, the convs and the pixel shuffle of the head, and
+    ``packed(net, conv)``, the weight image of a head or fusion conv."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+_LAYOUTS = {
+    'fp32': _Layout(bf16=False, CB=hip_ops.CB8, lanes=8, dtype=torch.float32, prop_input=hip_ops.vsr_prop_input, trunk=hip_ops.vsr_trunk,
+                    trunk_stem='sr_vsr_trunk', conv3x3=hip_ops.conv3x3, conv1x1=hip_ops.convd, pixel_shuffle=hip_ops.pixel_shuffle,
+                    packed=lambda net, conv: net.packed(conv)),
+    # bf16 images: 3x3 from the network's cache, the 1x1 fusion from hip_ops' (both keyed on the parameter's version, so an in-place
+    # update is seen)
+    'bf16': _Layout(bf16=True, CB=hip_ops.CB16, lanes=16, dtype=torch.bfloat16, prop_input=hip_ops.vsr_prop_input_bf16,
+                    trunk=hip_ops.vsr_trunk_bf16, trunk_stem='sr_rvsr_trunk', conv3x3=hip_ops.conv3x3_bf16,
+                    conv1x1=hip_ops.conv1x1_bf16, pixel_shuffle=hip_ops.pixel_shuffle_bf16,
+                    packed=lambda net, conv: net.packed(conv, 0, True) if conv.weight.shape[2] == 3 else hip_ops.packed_conv_bf16(conv)),
+}
+
+
 class ConvResidualBlocks(HipDriverNet):
     """Parameters of the reference's ConvResidualBlocks: ``main`` = conv 3x3 (num_in_ch -> num_out_ch), LeakyReLU(0.1),
     ``num_block`` ResidualBlockNoBN.  ``num_in_ch`` is 3 + k * num_out_ch (k = 1, 2): the frame, then k feature maps.  No forward:
@@ -75,7 +97,7 @@ class ConvResidualBlocks(HipDriverNet):
         lib, cfg = _lib.load(), self.cfg()
         if bf16 and self.num_out_ch % 16:
             raise ValueError(f'ConvResidualBlocks: the bf16 trunk needs num_out_ch % 16 == 0 (CB16), got {self.num_out_ch}')
-        stem = 'sr_rvsr_trunk' if bf16 else 'sr_vsr_trunk'
+        stem = _LAYOUTS['bf16' if bf16 else 'fp32'].trunk_stem
         with torch.cuda.device(dev):
             blob = self._blob(('fwd', bool(bf16)), lib, cfg, torch.cuda.current_stream(dev).cuda_stream, stem + '_packed_bytes',
                               stem + '_pack')
@@ -86,7 +108,7 @@ class ConvResidualBlocks(HipDriverNet):
         same kind; ``packed``: what ``packed(device, bf16)`` returned for the current parameters (looked up here when None)."""
         bf16 = isinstance(src, hip_ops.CB16)
         cfg, blob = packed or self.packed(src.device, bf16)
-        return (hip_ops.vsr_trunk_bf16 if bf16 else hip_ops.vsr_trunk)(cfg, blob, src, out)
+        return _LAYOUTS['bf16' if bf16 else 'fp32'].trunk(cfg, blob, src, out)
 
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError('ConvResidualBlocks is a parameter container; the video network launches the HIP kernels')
@@ -134,10 +156,8 @@ class BasicVSR(HipGenerator):
         return self
 
     def _layout(self):
-        """(window class, channels per block, element type, step-input launch) of the compute dtype."""
-        if self.compute_dtype == 'bf16':
-            return hip_ops.CB16, 16, torch.bfloat16, hip_ops.vsr_prop_input_bf16
-        return hip_ops.CB8, 8, torch.float32, hip_ops.vsr_prop_input
+        """The _Layout record of the compute dtype."""
+        return _LAYOUTS[self.compute_dtype]
 
     # ------------------------------------------------------------------------------------------------------ refusals
     def _check(self, x, flows=()):
@@ -193,45 +213,28 @@ class BasicVSR(HipGenerator):
         """One propagation branch over the frames in ``order``: per step one step-input launch (sr_vsr_prop_input_f32 /
         sr_rvsr_prop_input_bf16) and one trunk call (sr_vsr_trunk_f32 / sr_rvsr_trunk_bf16).  ``flows[:, j]`` warps the feature of
         the previous step onto frame ``order[k]``: j = i for the backward branch, i - 1 for the forward branch."""
-        CB, blk, _, prop_input = self._layout()
-        b, fb = x.size(0), self.num_feat // blk
+        L = self._layout()
+        CB, b, fb = L.CB, x.size(0), self.num_feat // L.lanes
         frame_out, warp_out = CB(tin, 0, 1), CB(tin, 1, fb)
-        prev, packed, src = None, trunk.packed(x.device, blk == 16), CB(tin)
+        prev, packed, src = None, trunk.packed(x.device, L.bf16), CB(tin)
         for k, i in enumerate(order):
             flow = None if prev is None else flows[:, min(i, order[k - 1])]
-            prop_input(x[:, i], prev, flow, warp_out, frame_out)
+            L.prop_input(x[:, i], prev, flow, warp_out, frame_out)
             prev = trunk.run(src, CB(feats[i * b:(i + 1) * b], cb0, fb), packed)
 
     def _reconstruct(self, feats, frames, y):
-        """The upsampling head on images [s, e) of the frame-major clip tensors, into y[s:e]."""
-        if self.compute_dtype == 'bf16':
-            return self._reconstruct_bf16(feats, frames, y)
-        out = hip_ops.CB8(feats)
+        """The upsampling head on images [s, e) of the frame-major clip tensors, into y[s:e].  In bf16 every activation is stored
+        as bf16 once, after its epilogue; conv_last writes fp32 NCHW and the x4 bilinear base of the fp32 frames is added in fp32
+        in both modes."""
+        L = self._layout()
+        out = L.CB(feats)
         if self._fuses:     # BasicVSR: fusion 1x1 of [backward, forward]; IconVSR reconstructs from the forward feature alone
-            out = hip_ops.convd(out, self.packed(self.fusion), act_slope=0.1)
-        out = hip_ops.pixel_shuffle(hip_ops.conv3x3(out, self.packed(self.upconv1), act_slope=0.1), self.num_feat, 2)
-        out = hip_ops.pixel_shuffle(hip_ops.conv3x3(out, self.packed(self.upconv2), act_slope=0.1), 64, 2)
-        out = hip_ops.conv3x3(out, self.packed(self.conv_hr), act_slope=0.1)
-        hip_ops.conv3x3(out, self.packed(self.conv_last), out_nchw=y)
+            out = L.conv1x1(out, L.packed(self, self.fusion), act_slope=0.1)
+        out = L.pixel_shuffle(L.conv3x3(out, L.packed(self, self.upconv1), act_slope=0.1), self.num_feat, 2)
+        out = L.pixel_shuffle(L.conv3x3(out, L.packed(self, self.upconv2), act_slope=0.1), 64, 2)
+        out = L.conv3x3(out, L.packed(self, self.conv_hr), act_slope=0.1)
+        L.conv3x3(out, L.packed(self, self.conv_last), out_nchw=y)
         hip_ops.bilinear_up(frames, 4, out=y)
-
-    def _packed16(self, conv):
-        """The bf16 image of a head or fusion conv: 3x3 from this network's cache, the 1x1 fusion from hip_ops' (both keyed on the
-        parameter's version, so an in-place update is seen)."""
-        return self.packed(conv, 0, True) if conv.weight.shape[2] == 3 else hip_ops.packed_conv_bf16(conv)
-
-    def _reconstruct_bf16(self, feats, frames, y):
-        """The head on CB16: every activation is stored as bf16 once, after its epilogue; conv_last writes fp32 NCHW and the x4
-        bilinear base of the fp32 frames is added in fp32."""
-        H, P = hip_ops, self._packed16
-        out = H.CB16(feats)
-        if self._fuses:
-            out = H.conv1x1_bf16(out, P(self.fusion), act_slope=0.1)
-        out = H.pixel_shuffle_bf16(H.conv3x3_bf16(out, P(self.upconv1), act_slope=0.1), self.num_feat, 2)
-        out = H.pixel_shuffle_bf16(H.conv3x3_bf16(out, P(self.upconv2), act_slope=0.1), 64, 2)
-        out = H.conv3x3_bf16(out, P(self.conv_hr), act_slope=0.1)
-        H.conv3x3_bf16(out, P(self.conv_last), out_nchw=y)
-        H.bilinear_up(frames, 4, out=y)
 
     def propagate(self, x, flows_forward, flows_backward):
         """The network after ``get_flow``: x [b, n, 3, h, w], flows [b, n - 1, 2, h, w] -> [b, n, 3, 4h, 4w]."""
@@ -239,8 +242,8 @@ class BasicVSR(HipGenerator):
         with torch.no_grad():
             x, flows_forward, flows_backward = x.contiguous(), flows_forward.contiguous(), flows_backward.contiguous()
             b, n, _, h, w = x.shape
-            _, blk, dtype, _ = self._layout()
-            fb, dev = self.num_feat // blk, x.device
+            L = self._layout()
+            blk, dtype, fb, dev = L.lanes, L.dtype, self.num_feat // L.lanes, x.device
             feats = torch.empty((n * b, 2 * fb, h, w, blk), dtype=dtype, device=dev)
             tin = torch.empty((b, 1 + fb, h, w, blk), dtype=dtype, device=dev)
             self._branch(self.backward_trunk, x, flows_backward, feats, 0, list(range(n - 1, -1, -1)), tin)
@@ -376,8 +379,8 @@ class IconVSR(BasicVSR):
             keys = self.keyframes(n)
             if feats_keyframe is None:
                 feats_keyframe = self.get_keyframe_feature(x, keys)
-            CB, blk, dtype, prop_input = self._layout()
-            bf16 = blk == 16
+            L = self._layout()
+            CB, blk, dtype, bf16 = L.CB, L.lanes, L.dtype, L.bf16
             fb, dev = self.num_feat // blk, x.device
             clip = torch.empty((n * b, 1 + 2 * fb, h, w, blk), dtype=dtype, device=dev)
             fwd = torch.empty((n * b, fb, h, w, blk), dtype=dtype, device=dev)
@@ -389,13 +392,10 @@ class IconVSR(BasicVSR):
 
             def step(i, prev, flow, fusion, warp_out, frame_out):
                 if i in pair:
-                    prop_input(x[:, i], prev, flow, CB(pair[i], 0, fb), frame_out)
-                    if bf16:
-                        hip_ops.conv3x3_bf16(CB(pair[i]), self._packed16(fusion), warp_out)
-                    else:
-                        hip_ops.conv3x3(CB(pair[i]), self.packed(fusion), warp_out)
+                    L.prop_input(x[:, i], prev, flow, CB(pair[i], 0, fb), frame_out)
+                    L.conv3x3(CB(pair[i]), L.packed(self, fusion), warp_out)
                 else:
-                    prop_input(x[:, i], prev, flow, warp_out, frame_out)
+                    L.prop_input(x[:, i], prev, flow, warp_out, frame_out)
 
             prev, packed = None, self.backward_trunk.packed(dev, bf16)
             for i in range(n - 1, -1, -1):

@@ -63,8 +63,6 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p,
   ((f32x4*)p)[i] = po;
 }
 
-bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-
 // checks the classes and derives the table; the bias corrections in double, as sr_adam_step_f32 has them
 int build_table(const char* who, const sr_adam_class* classes, int n_classes, float beta1, float beta2, ClassTable* tab) {
   SR_CHECK_ARG(classes, "%s: null classes", who);
@@ -111,7 +109,7 @@ extern "C" int sr_adam_step_groups_f32(float* param, const float* grad, float* e
                                        int32_t* skipped, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SR_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && class_of_chunk, "sr_adam_step_groups_f32: null pointer");
-  SR_CHECK_ARG(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq),
+  SR_CHECK_ARG(sr::aligned16(param) && sr::aligned16(grad) && sr::aligned16(exp_avg) && sr::aligned16(exp_avg_sq),
                "sr_adam_step_groups_f32: arrays must be 16-byte aligned");
   SR_CHECK_ARG(n > 0 && n % SR_ADAM_CHUNK == 0, "sr_adam_step_groups_f32: n = %lld is not a positive multiple of %d", (long long)n,
                SR_ADAM_CHUNK);

@@ -1077,7 +1077,7 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "bn_lrelu_bwd_kernel"};
     return bnames[id - 161];
   }
-  if (id == 167) return "vsr_prop_input_bf16_kernel";  // vsr_ops_bf16.hip (include/sr_hip_vsr_bf16.h); 166 stays unnamed
+  if (id == 167) return "vsr_prop_input_bf16_kernel";  // vsr_ops.hip (include/sr_hip_vsr_bf16.h); 166 stays unnamed
   if (id >= 169 && id < 177) {  // flow_bwd_ops.hip (include/sr_hip_flow_bwd.h); 168 stays unnamed
     static const char* qnames[8] = {"conv7x7_dgrad_f32_kernelILi1ELi4EE", "conv7x7_dgrad_f32_kernelILi2ELi2EE", "conv7x7_dgrad_pack_kernel",
                                     "conv7x7_wgrad_f32_kernel",           "conv7x7_wgrad_reduce_kernel",        "spynet_level_dup_kernel",

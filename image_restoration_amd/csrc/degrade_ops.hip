@@ -37,8 +37,6 @@ __device__ __forceinline__ void sample_size(const int* sizes, int b, int hmax, i
   }
 }
 
-__host__ __device__ __forceinline__ bool aligned16(const void* p) { return ((unsigned long long)p & 15ull) == 0; }
-
 // --------------------------------------------------------------------------------------------------------------- filter2d
 constexpr int kFTileW = 64, kFTileH = 16, kFMaxK = 21;
 constexpr int kFRows = kFTileH + kFMaxK - 1, kFPitch = kFTileW + kFMaxK - 1 + 1;
@@ -477,7 +475,7 @@ extern "C" int sr_add_gaussian_noise_f32(const float* x, const float* noise, con
   SR_CHECK_ARG(plane_shape_ok(B, C, H, W) && B <= 65535 && C <= 65535,
                "sr_add_gaussian_noise_f32: bad shape [%d, %d, %d, %d] (B * C at most 65535)", B, C, H, W);
   const long long hw = (long long)H * W;
-  const bool v4 = hw % 4 == 0 && aligned16(x) && aligned16(noise) && aligned16(out) && (!gray || aligned16(noise_gray));
+  const bool v4 = hw % 4 == 0 && sr::aligned16(x) && sr::aligned16(noise) && sr::aligned16(out) && (!gray || sr::aligned16(noise_gray));
   const bool prof = sr::prof_on();
   if (prof) prof_rec(stream, 143, C, B, H, W, 4.0 * B * C * hw, 12.0 * B * C * hw);
   const dim3 grid((unsigned)((hw + (v4 ? 1023 : 255)) / (v4 ? 1024 : 256)), C, B);
@@ -537,7 +535,7 @@ extern "C" int sr_degrade_finish_f32(const float* x, const float* jitter, const 
     p.mean[c] = mean3 ? mean3[c] : 0.f;
     p.stdv[c] = std3 ? std3[c] : 1.f;
   }
-  const bool v4 = p.hw % 4 == 0 && aligned16(x) && aligned16(out);
+  const bool v4 = p.hw % 4 == 0 && sr::aligned16(x) && sr::aligned16(out);
   const bool prof = sr::prof_on();
   if (prof) prof_rec(stream, 146, 3, B, H, W, 12.0 * B * p.hw, 24.0 * B * p.hw);
   const dim3 grid((unsigned)((p.hw + (v4 ? 1023 : 255)) / (v4 ? 1024 : 256)), 1, B);

@@ -36,8 +36,6 @@ void prof_rec(hipStream_t stream, int id, int cin, int cout, int n, int h, int w
   sr::prof_begin(stream, r);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 bool served(int cout, int cin) {
   return (cin == 8 && cout == 32) || (cin == 32 && cout == 64) || (cin == 64 && cout == 32) || (cin == 32 && cout == 16) ||
          (cin == 16 && cout == 2);
@@ -421,7 +419,7 @@ extern "C" int sr_conv7x7_dgrad_pack_f32(const float* weight, int cout, int cin,
   hipStream_t stream = (hipStream_t)stream_;
   SR_CHECK_ARG(served(cout, cin), "sr_conv7x7_dgrad_pack_f32: (cin, cout) = (%d, %d) is not supported; supported: " SR_PAIRS, cin, cout);
   SR_CHECK_ARG(weight && packed, "sr_conv7x7_dgrad_pack_f32: null weight / packed");
-  SR_CHECK_ARG(aligned16(packed), "sr_conv7x7_dgrad_pack_f32: packed must be 16-byte aligned");
+  SR_CHECK_ARG(sr::aligned16(packed), "sr_conv7x7_dgrad_pack_f32: packed must be 16-byte aligned");
   const long long wf = dgrad_weight_floats(cout, cin), total = wf + dgrad_zero_floats(cin);
   const bool prof = sr::prof_on();
   if (prof) prof_rec(stream, 171, cin, cout, 1, 7, 7, 0.0, 4.0 * (total + 49.0 * cin * cout));
@@ -439,7 +437,7 @@ extern "C" int sr_conv7x7_dgrad_f32(const sr_conv7x7_dgrad_desc* d, void* stream
                d->cout);
   SR_CHECK_ARG(d->dy && d->packed && d->dx, "sr_conv7x7_dgrad_f32: null dy / packed / dx");
   SR_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0, "sr_conv7x7_dgrad_f32: bad shape n=%d h=%d w=%d", d->n, d->h, d->w);
-  SR_CHECK_ARG(aligned16(d->dy) && aligned16(d->packed) && aligned16(d->dx) && aligned16(d->mask),
+  SR_CHECK_ARG(sr::aligned16(d->dy) && sr::aligned16(d->packed) && sr::aligned16(d->dx) && sr::aligned16(d->mask),
                "sr_conv7x7_dgrad_f32: pointers must be 16-byte aligned");
   SR_CHECK_ARG(d->dy_img_stride % 4 == 0 && d->dx_img_stride % 4 == 0 && d->mask_img_stride % 4 == 0,
                "sr_conv7x7_dgrad_f32: image strides must be multiples of 4 floats");
@@ -499,7 +497,8 @@ extern "C" int sr_conv7x7_wgrad_f32(const sr_conv7x7_wgrad_desc* d, void* stream
                d->cout);
   SR_CHECK_ARG(d->x && d->dy && d->dweight && d->slab, "sr_conv7x7_wgrad_f32: null x / dy / dweight / slab");
   SR_CHECK_ARG(d->n > 0 && d->n <= 65535 && d->h > 0 && d->w > 0, "sr_conv7x7_wgrad_f32: bad shape n=%d h=%d w=%d", d->n, d->h, d->w);
-  SR_CHECK_ARG(aligned16(d->x) && aligned16(d->dy) && aligned16(d->slab), "sr_conv7x7_wgrad_f32: x, dy and slab must be 16-byte aligned");
+  SR_CHECK_ARG(sr::aligned16(d->x) && sr::aligned16(d->dy) && sr::aligned16(d->slab),
+               "sr_conv7x7_wgrad_f32: x, dy and slab must be 16-byte aligned");
   SR_CHECK_ARG(((uintptr_t)d->dweight & 3u) == 0 && ((uintptr_t)d->dbias & 3u) == 0, "sr_conv7x7_wgrad_f32: dweight / dbias must be 4-byte aligned");
   SR_CHECK_ARG(d->x_img_stride % 4 == 0 && d->dy_img_stride % 4 == 0, "sr_conv7x7_wgrad_f32: image strides must be multiples of 4 floats");
   SR_CHECK_ARG(d->accumulate == 0 || d->accumulate == 1, "sr_conv7x7_wgrad_f32: accumulate must be 0 or 1");
@@ -550,7 +549,7 @@ extern "C" int sr_spynet_level_input_bwd_f32(const float* supp, const float* up,
   SR_CHECK_ARG(N > 0 && N <= 65535 && H > 0 && W > 0, "sr_spynet_level_input_bwd_f32: bad shape N=%d H=%d W=%d", N, H, W);
   SR_CHECK_ARG(H % 2 == 0 && W % 2 == 0, "sr_spynet_level_input_bwd_f32: H=%d, W=%d must be even (the coarsest level has no incoming flow)", H, W);
   SR_CHECK_ARG((long long)H * W < (1ll << 28), "sr_spynet_level_input_bwd_f32: image too large for 32-bit plane offsets");
-  SR_CHECK_ARG(aligned16(up) && aligned16(g_in) && aligned16(g_res) && aligned16(g_prev),
+  SR_CHECK_ARG(sr::aligned16(up) && sr::aligned16(g_in) && sr::aligned16(g_res) && sr::aligned16(g_prev),
                "sr_spynet_level_input_bwd_f32: CB8 tensors must be 16-byte aligned");
   SR_CHECK_ARG(((uintptr_t)d_up & 7u) == 0, "sr_spynet_level_input_bwd_f32: d_up must be 8-byte aligned");
   SR_CHECK_ARG(g_prev != g_res && g_prev != g_in && g_prev != up, "sr_spynet_level_input_bwd_f32: g_prev must not be an input");

@@ -196,8 +196,6 @@ long long conv7x7_bias_floats(int cout, int inst) { return inst == 2 ? 32 : (lon
 
 constexpr int kFewLds = 2 * (((((16 + kKS - 1) * kXRow * 32 + 1023) / 1024) * 1024) + ((49 * 128 + 1023) / 1024) * 1024);
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // -------------------------------------------------------------------------------------------------------- flow warping
 // grid (ceil(HW / 256), ceil(C / 8), N): a thread warps up to 8 channels of one pixel
 template <bool CB8>
@@ -390,7 +388,7 @@ int check_warp_args(const char* who, const void* x, const void* flow, int N, int
   SR_CHECK_ARG((long long)H * W < (1ll << 28), "%s: image too large for 32-bit plane offsets", who);
   SR_CHECK_ARG(N <= 65535 && (C + 7) / 8 <= 65535, "%s: N and C / 8 must fit the grid (65535)", who);
   SR_CHECK_ARG(((uintptr_t)flow & 7u) == 0, "%s: flow must be 8-byte aligned", who);
-  SR_CHECK_ARG(layout == SR_FLOW_NCHW || aligned16(x), "%s: a CB8 tensor must be 16-byte aligned", who);
+  SR_CHECK_ARG(layout == SR_FLOW_NCHW || sr::aligned16(x), "%s: a CB8 tensor must be 16-byte aligned", who);
   return SR_OK;
 }
 
@@ -415,7 +413,7 @@ extern "C" int sr_conv7x7_pack_f32(const float* weight, const float* bias, int c
   SR_CHECK_ARG(inst >= 0, "sr_conv7x7_pack_f32: (cin, cout) = (%d, %d) is not supported; supported: (8, 32), (32, 64), (64, 32), "
                "(32, 16), (16, 2)", cin, cout);
   SR_CHECK_ARG(weight && packed, "sr_conv7x7_pack_f32: null weight / packed");
-  SR_CHECK_ARG(aligned16(packed), "sr_conv7x7_pack_f32: packed must be 16-byte aligned");
+  SR_CHECK_ARG(sr::aligned16(packed), "sr_conv7x7_pack_f32: packed must be 16-byte aligned");
   const long long wf = conv7x7_weight_floats(cout, cin, inst), total = wf + conv7x7_bias_floats(cout, inst);
   const bool prof = sr::prof_on();
   if (prof) prof_rec(stream, 151, cin, cout, 1, 7, 7, 0.0, 4.0 * (total + 49.0 * cin * cout));
@@ -434,7 +432,7 @@ extern "C" int sr_conv7x7_f32(const sr_conv7x7_desc* d, void* stream_) {
                "(32, 16), (16, 2)", d->cin, d->cout);
   SR_CHECK_ARG(d->in && d->packed && d->out, "sr_conv7x7_f32: null in / packed / out");
   SR_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0, "sr_conv7x7_f32: bad shape n=%d h=%d w=%d", d->n, d->h, d->w);
-  SR_CHECK_ARG(aligned16(d->in) && aligned16(d->packed) && aligned16(d->out) && aligned16(d->res1),
+  SR_CHECK_ARG(sr::aligned16(d->in) && sr::aligned16(d->packed) && sr::aligned16(d->out) && sr::aligned16(d->res1),
                "sr_conv7x7_f32: pointers must be 16-byte aligned");
   SR_CHECK_ARG(d->in_img_stride % 4 == 0 && d->out_img_stride % 4 == 0 && d->res1_img_stride % 4 == 0,
                "sr_conv7x7_f32: image strides must be multiples of 4 floats");
@@ -490,7 +488,7 @@ extern "C" int sr_flow_warp_f32(const float* x, const float* flow, float* out, i
   hipStream_t stream = (hipStream_t)stream_;
   if (int rc = check_warp_args("sr_flow_warp_f32", x, flow, N, C, H, W, layout, padding)) return rc;
   SR_CHECK_ARG(out != nullptr, "sr_flow_warp_f32: null out");
-  SR_CHECK_ARG(layout == SR_FLOW_NCHW || aligned16(out), "sr_flow_warp_f32: a CB8 tensor must be 16-byte aligned");
+  SR_CHECK_ARG(layout == SR_FLOW_NCHW || sr::aligned16(out), "sr_flow_warp_f32: a CB8 tensor must be 16-byte aligned");
   const dim3 grid((unsigned)sr::cdiv(H * W, 256), (unsigned)((C + 7) / 8), (unsigned)N);
   const bool prof = sr::prof_on();
   if (prof) prof_rec(stream, 152, C, C, N, H, W, 8.0 * N * C * H * W, 4.0 * N * H * W * (5.0 * C + 2.0));
@@ -541,7 +539,8 @@ extern "C" int sr_spynet_level_input_f32(const float* ref, const float* supp, co
   SR_CHECK_ARG(!flow_prev || (H % 2 == 0 && W % 2 == 0), "sr_spynet_level_input_f32: H=%d, W=%d must be even above the coarsest level",
                H, W);
   SR_CHECK_ARG((long long)H * W < (1ll << 28), "sr_spynet_level_input_f32: image too large for 32-bit plane offsets");
-  SR_CHECK_ARG(aligned16(out) && aligned16(up_out) && aligned16(flow_prev), "sr_spynet_level_input_f32: CB8 tensors must be 16-byte aligned");
+  SR_CHECK_ARG(sr::aligned16(out) && sr::aligned16(up_out) && sr::aligned16(flow_prev),
+               "sr_spynet_level_input_f32: CB8 tensors must be 16-byte aligned");
   const bool prof = sr::prof_on();
   if (prof) prof_rec(stream, 155, 8, 8, N, H, W, 40.0 * N * H * W, 4.0 * N * H * W * (3.0 + 12.0 + 2.0 + 16.0));
   hipLaunchKernelGGL(spynet_level_input_kernel, dim3((unsigned)sr::cdiv(H * W, 256), 1, (unsigned)N), dim3(256), 0, stream, ref, supp,

@@ -1688,7 +1688,33 @@ def resize_bilinear_adjoint(dy, size):
     return dx
 
 
-# ---- the recurrent video networks: propagation step input and trunk driver (include/sr_hip_vsr.h) ----
+# ---- the recurrent video networks: propagation step input and trunk driver, fp32 on CB8 (include/sr_hip_vsr.h) and bf16 on
+# CB16 (include/sr_hip_vsr_bf16.h).  One implementation each, told the window class and the symbols; the public wrappers keep the
+# literal _launch_arg call of their entry point ----
+
+def _vsr_prop_desc(who, CB, Desc, frame, prev, flow, warp_out, frame_out):
+    """The checked and filled descriptor of a step-input launch on windows of class ``CB``."""
+    _need_cuda(frame, who)
+    _arg(frame.dim() == 4 and frame.size(1) == 3 and frame.dtype == torch.float32 and frame.numel() > 0 and frame[0].is_contiguous(),
+         f'{who}: needs an fp32 [N, 3, H, W] frame batch with dense images, got {frame.dtype} {tuple(frame.shape)}')
+    n, _, h, w = frame.shape
+    _arg((prev is None) == (flow is None), f'{who}: prev and flow come together')
+    _arg(isinstance(warp_out, CB) and (warp_out.n, warp_out.h, warp_out.w) == (n, h, w), f'{who}: warp_out does not fit')
+    d = Desc()
+    d.frame, d.frame_img_stride = frame.data_ptr(), frame.stride(0)
+    if prev is not None:
+        _arg(isinstance(prev, CB) and (prev.n, prev.h, prev.w, prev.cbn) == (n, h, w, warp_out.cbn), f'{who}: prev does not fit')
+        _arg(flow.dtype == torch.float32 and tuple(flow.shape) == (n, 2, h, w) and flow[0].is_contiguous() and flow.device == frame.device,
+             f'{who}: flow must be an fp32 [{n}, 2, {h}, {w}] view with dense images, got {flow.dtype} {tuple(flow.shape)}')
+        d.prev, d.prev_img_stride, d.flow, d.flow_img_stride = prev.ptr, prev.img_stride, flow.data_ptr(), flow.stride(0)
+    if frame_out is not None:
+        _arg(isinstance(frame_out, CB) and (frame_out.n, frame_out.h, frame_out.w, frame_out.cbn) == (n, h, w, 1),
+             f'{who}: frame_out must be a one-block window')
+        d.frame_out, d.frame_out_img_stride = frame_out.ptr, frame_out.img_stride
+    d.warp_out, d.warp_out_img_stride = warp_out.ptr, warp_out.img_stride
+    d.n, d.h, d.w, d.fb = n, h, w, warp_out.cbn
+    return d
+
 
 def vsr_prop_input(frame, prev, flow, warp_out, frame_out=None):
     """What one propagation step feeds its trunk — one sr_vsr_prop_input_f32 launch.  ``frame``: fp32 [N, 3, H, W] view whose
@@ -1696,26 +1722,17 @@ def vsr_prop_input(frame, prev, flow, warp_out, frame_out=None):
     ``flow``: fp32 [N, 2, H, W] view with dense images (what SpyNet returns), None iff ``prev`` is None.  Writes
     flow_warp(prev, flow) (zeros for None) into the CB8 window ``warp_out`` and, when given, the frame into the one-block
     window ``frame_out``."""
-    _need_cuda(frame, 'vsr_prop_input')
-    _arg(frame.dim() == 4 and frame.size(1) == 3 and frame.dtype == torch.float32 and frame.numel() > 0 and frame[0].is_contiguous(),
-         f'vsr_prop_input: needs an fp32 [N, 3, H, W] frame batch with dense images, got {frame.dtype} {tuple(frame.shape)}')
-    n, _, h, w = frame.shape
-    _arg((prev is None) == (flow is None), 'vsr_prop_input: prev and flow come together')
-    _arg(isinstance(warp_out, CB8) and (warp_out.n, warp_out.h, warp_out.w) == (n, h, w), 'vsr_prop_input: warp_out does not fit')
-    d = _lib.VsrPropDesc()
-    d.frame, d.frame_img_stride = frame.data_ptr(), frame.stride(0)
-    if prev is not None:
-        _arg(isinstance(prev, CB8) and (prev.n, prev.h, prev.w, prev.cbn) == (n, h, w, warp_out.cbn), 'vsr_prop_input: prev does not fit')
-        _arg(flow.dtype == torch.float32 and tuple(flow.shape) == (n, 2, h, w) and flow[0].is_contiguous() and flow.device == frame.device,
-             f'vsr_prop_input: flow must be an fp32 [{n}, 2, {h}, {w}] view with dense images, got {flow.dtype} {tuple(flow.shape)}')
-        d.prev, d.prev_img_stride, d.flow, d.flow_img_stride = prev.ptr, prev.img_stride, flow.data_ptr(), flow.stride(0)
-    if frame_out is not None:
-        _arg(isinstance(frame_out, CB8) and (frame_out.n, frame_out.h, frame_out.w, frame_out.cbn) == (n, h, w, 1),
-             'vsr_prop_input: frame_out must be a one-block window')
-        d.frame_out, d.frame_out_img_stride = frame_out.ptr, frame_out.img_stride
-    d.warp_out, d.warp_out_img_stride = warp_out.ptr, warp_out.img_stride
-    d.n, d.h, d.w, d.fb = n, h, w, warp_out.cbn
+    d = _vsr_prop_desc('vsr_prop_input', CB8, _lib.VsrPropDesc, frame, prev, flow, warp_out, frame_out)
     _launch_arg('sr_vsr_prop_input_f32', frame.device, C.byref(d))
+    return warp_out
+
+
+def vsr_prop_input_bf16(frame, prev, flow, warp_out, frame_out=None):
+    """The CB16 twin of vsr_prop_input — one sr_rvsr_prop_input_bf16 launch.  ``frame`` and ``flow`` stay fp32 views with dense
+    images ([N, 3, H, W], [N, 2, H, W]); ``prev``, ``warp_out`` and the one-block ``frame_out`` are CB16 windows.  Writes
+    bf16(flow_warp(widened prev, flow)) (zeros for None) into ``warp_out`` and bf16(frame) with 13 zero channels into ``frame_out``."""
+    d = _vsr_prop_desc('vsr_prop_input_bf16', CB16, _lib.RvsrPropDesc, frame, prev, flow, warp_out, frame_out)
+    _launch_arg('sr_rvsr_prop_input_bf16', frame.device, C.byref(d))
     return warp_out
 
 
@@ -1731,91 +1748,59 @@ def vsr_trunk_wino_convs(cfg):
     return [bool(lib.sr_vsr_trunk_conv_wino(C.byref(cfg), i)) for i in range(n // 2)]
 
 
-def vsr_trunk_pack(cfg, params, blob=None):
-    """The packed blob of a trunk from its parameters in state_dict order (device fp32, contiguous) — sr_vsr_trunk_pack_f32."""
+def _vsr_trunk_pack_args(who, bytes_query, cfg, params, blob):
+    """(blob, parameter pointer array) of a trunk pack call; the parameter count is sr_vsr_trunk_num_params for both kinds."""
     lib = _lib.load()
     n = lib.sr_vsr_trunk_num_params(C.byref(cfg))
-    _arg(n > 0 and n == len(params), f'vsr_trunk_pack: {len(params)} parameters, the config has {n}')
+    _arg(n > 0 and n == len(params), f'{who}: {len(params)} parameters, the config has {n}')
     for p in params:
-        _need_cuda(p, 'vsr_trunk_pack')
-        _arg(p.dtype == torch.float32 and p.is_contiguous(), 'vsr_trunk_pack: parameters must be contiguous fp32')
-    nbytes = lib.sr_vsr_trunk_packed_bytes(C.byref(cfg))
+        _need_cuda(p, who)
+        _arg(p.dtype == torch.float32 and p.is_contiguous(), f'{who}: parameters must be contiguous fp32')
+    nbytes = getattr(lib, bytes_query)(C.byref(cfg))
     if blob is None:
         blob = torch.empty(nbytes, dtype=torch.uint8, device=params[0].device)
-    _arg(blob.numel() >= nbytes and blob.dtype == torch.uint8, 'vsr_trunk_pack: blob too small')
-    ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in params])
+    _arg(blob.numel() >= nbytes and blob.dtype == torch.uint8, f'{who}: blob too small')
+    return blob, (C.c_void_p * n)(*[p.data_ptr() for p in params])
+
+
+def vsr_trunk_pack(cfg, params, blob=None):
+    """The packed blob of a trunk from its parameters in state_dict order (device fp32, contiguous) — sr_vsr_trunk_pack_f32."""
+    blob, ptrs = _vsr_trunk_pack_args('vsr_trunk_pack', 'sr_vsr_trunk_packed_bytes', cfg, params, blob)
     _launch_arg('sr_vsr_trunk_pack_f32', blob.device, C.byref(cfg), ptrs, blob.data_ptr())
     return blob
-
-
-def vsr_trunk(cfg, blob, src, out):
-    """ConvResidualBlocks on the CB8 window ``src`` (frame block + cin_segs feature windows) into the CB8 window ``out`` — one
-    sr_vsr_trunk_f32 call: 1 + 2 * num_block conv launches, no allocation beyond the grow-only scratch."""
-    _arg(isinstance(src, CB8) and isinstance(out, CB8) and src.cbn == 1 + cfg.cin_segs * cfg.num_feat // 8 and out.cbn == cfg.num_feat // 8
-         and (out.n, out.h, out.w) == (src.n, src.h, src.w), 'vsr_trunk: windows do not fit the config')
-    nbytes = _lib.load().sr_vsr_trunk_workspace_bytes(C.byref(cfg), src.n, src.h, src.w)
-    ws = scratch(src.device, nbytes, 'vsr_trunk')
-    _launch_arg('sr_vsr_trunk_f32', src.device, C.byref(cfg), blob.data_ptr(), src.ptr, src.img_stride, out.ptr, out.img_stride, src.n,
-                src.h, src.w, ws.data_ptr(), nbytes)
-    return out
-
-
-# ---- the recurrent video networks in bf16: step input and trunk driver on CB16 (include/sr_hip_vsr_bf16.h) ----
-
-def vsr_prop_input_bf16(frame, prev, flow, warp_out, frame_out=None):
-    """The CB16 twin of vsr_prop_input — one sr_rvsr_prop_input_bf16 launch.  ``frame`` and ``flow`` stay fp32 views with dense
-    images ([N, 3, H, W], [N, 2, H, W]); ``prev``, ``warp_out`` and the one-block ``frame_out`` are CB16 windows.  Writes
-    bf16(flow_warp(widened prev, flow)) (zeros for None) into ``warp_out`` and bf16(frame) with 13 zero channels into ``frame_out``."""
-    _need_cuda(frame, 'vsr_prop_input_bf16')
-    _arg(frame.dim() == 4 and frame.size(1) == 3 and frame.dtype == torch.float32 and frame.numel() > 0 and frame[0].is_contiguous(),
-         f'vsr_prop_input_bf16: needs an fp32 [N, 3, H, W] frame batch with dense images, got {frame.dtype} {tuple(frame.shape)}')
-    n, _, h, w = frame.shape
-    _arg((prev is None) == (flow is None), 'vsr_prop_input_bf16: prev and flow come together')
-    _arg(isinstance(warp_out, CB16) and (warp_out.n, warp_out.h, warp_out.w) == (n, h, w), 'vsr_prop_input_bf16: warp_out does not fit')
-    d = _lib.RvsrPropDesc()
-    d.frame, d.frame_img_stride = frame.data_ptr(), frame.stride(0)
-    if prev is not None:
-        _arg(isinstance(prev, CB16) and (prev.n, prev.h, prev.w, prev.cbn) == (n, h, w, warp_out.cbn), 'vsr_prop_input_bf16: prev does not fit')
-        _arg(flow.dtype == torch.float32 and tuple(flow.shape) == (n, 2, h, w) and flow[0].is_contiguous() and flow.device == frame.device,
-             f'vsr_prop_input_bf16: flow must be an fp32 [{n}, 2, {h}, {w}] view with dense images, got {flow.dtype} {tuple(flow.shape)}')
-        d.prev, d.prev_img_stride, d.flow, d.flow_img_stride = prev.ptr, prev.img_stride, flow.data_ptr(), flow.stride(0)
-    if frame_out is not None:
-        _arg(isinstance(frame_out, CB16) and (frame_out.n, frame_out.h, frame_out.w, frame_out.cbn) == (n, h, w, 1),
-             'vsr_prop_input_bf16: frame_out must be a one-block window')
-        d.frame_out, d.frame_out_img_stride = frame_out.ptr, frame_out.img_stride
-    d.warp_out, d.warp_out_img_stride = warp_out.ptr, warp_out.img_stride
-    d.n, d.h, d.w, d.fb = n, h, w, warp_out.cbn
-    _launch_arg('sr_rvsr_prop_input_bf16', frame.device, C.byref(d))
-    return warp_out
 
 
 def vsr_trunk_pack_bf16(cfg, params, blob=None):
     """The bf16 blob of a trunk (bf16 weight images, fp32 biases) from its fp32 parameters in state_dict order —
     sr_rvsr_trunk_pack_bf16."""
-    lib = _lib.load()
-    nbytes = lib.sr_rvsr_trunk_packed_bytes_bf16(C.byref(cfg))
-    n = 2 * (1 + 2 * cfg.num_block)
-    _arg(nbytes > 0, f'vsr_trunk_pack_bf16: bad config num_feat={cfg.num_feat} (a multiple of 16, CB16) num_block={cfg.num_block} '
-                     f'cin_segs={cfg.cin_segs}')
-    _arg(n == len(params), f'vsr_trunk_pack_bf16: {len(params)} parameters, the config has {n}')
-    for p in params:
-        _need_cuda(p, 'vsr_trunk_pack_bf16')
-        _arg(p.dtype == torch.float32 and p.is_contiguous(), 'vsr_trunk_pack_bf16: parameters must be contiguous fp32')
-    if blob is None:
-        blob = torch.empty(nbytes, dtype=torch.uint8, device=params[0].device)
-    _arg(blob.numel() >= nbytes and blob.dtype == torch.uint8, 'vsr_trunk_pack_bf16: blob too small')
-    ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in params])
+    _arg(_lib.load().sr_rvsr_trunk_packed_bytes_bf16(C.byref(cfg)) > 0,
+         f'vsr_trunk_pack_bf16: bad config num_feat={cfg.num_feat} (a multiple of 16, CB16) num_block={cfg.num_block} '
+         f'cin_segs={cfg.cin_segs}')
+    blob, ptrs = _vsr_trunk_pack_args('vsr_trunk_pack_bf16', 'sr_rvsr_trunk_packed_bytes_bf16', cfg, params, blob)
     _launch_arg('sr_rvsr_trunk_pack_bf16', blob.device, C.byref(cfg), ptrs, blob.data_ptr())
     return blob
+
+
+def _vsr_trunk_args(who, CB, lanes, ws_query, cfg, blob, src, out):
+    """The checked arguments of a trunk call on windows of class ``CB`` (``lanes`` channels a block), after the device."""
+    _arg(isinstance(src, CB) and isinstance(out, CB) and src.cbn == 1 + cfg.cin_segs * cfg.num_feat // lanes
+         and out.cbn == cfg.num_feat // lanes and (out.n, out.h, out.w) == (src.n, src.h, src.w), f'{who}: windows do not fit the config')
+    nbytes = getattr(_lib.load(), ws_query)(C.byref(cfg), src.n, src.h, src.w)
+    ws = scratch(src.device, nbytes, who)
+    return (C.byref(cfg), blob.data_ptr(), src.ptr, src.img_stride, out.ptr, out.img_stride, src.n, src.h, src.w, ws.data_ptr(), nbytes)
+
+
+def vsr_trunk(cfg, blob, src, out):
+    """ConvResidualBlocks on the CB8 window ``src`` (frame block + cin_segs feature windows) into the CB8 window ``out`` — one
+    sr_vsr_trunk_f32 call: 1 + 2 * num_block conv launches, no allocation beyond the grow-only scratch."""
+    _launch_arg('sr_vsr_trunk_f32', src.device, *_vsr_trunk_args('vsr_trunk', CB8, 8, 'sr_vsr_trunk_workspace_bytes', cfg, blob, src, out))
+    return out
 
 
 def vsr_trunk_bf16(cfg, blob, src, out):
     """ConvResidualBlocks on the CB16 window ``src`` (frame block + cin_segs feature windows) into the CB16 window ``out`` — one
     sr_rvsr_trunk_bf16 call: 1 + 2 * num_block sr_conv3x3_bf16 launches, no allocation beyond the grow-only scratch."""
-    _arg(cfg.num_feat % 16 == 0 and isinstance(src, CB16) and isinstance(out, CB16) and src.cbn == 1 + cfg.cin_segs * cfg.num_feat // 16
-         and out.cbn == cfg.num_feat // 16 and (out.n, out.h, out.w) == (src.n, src.h, src.w), 'vsr_trunk_bf16: windows do not fit the config')
-    nbytes = _lib.load().sr_rvsr_trunk_workspace_bytes_bf16(C.byref(cfg), src.n, src.h, src.w)
-    ws = scratch(src.device, nbytes, 'vsr_trunk_bf16')
-    _launch_arg('sr_rvsr_trunk_bf16', src.device, C.byref(cfg), blob.data_ptr(), src.ptr, src.img_stride, out.ptr, out.img_stride, src.n,
-                src.h, src.w, ws.data_ptr(), nbytes)
+    _arg(cfg.num_feat % 16 == 0, 'vsr_trunk_bf16: windows do not fit the config')     # a valid fp32 config may not be one here
+    _launch_arg('sr_rvsr_trunk_bf16', src.device,
+                *_vsr_trunk_args('vsr_trunk_bf16', CB16, 16, 'sr_rvsr_trunk_workspace_bytes_bf16', cfg, blob, src, out))
     return out

@@ -1,8 +1,8 @@
-// Stand-alone driver for the host-side code of vsr_ops.hip: the argument checks of its entry points, the trunk plan (which convs
-// have a Winograd image, the blob and workspace sizes) and the pack table it builds, run with the host sanitizers on a machine
-// without a GPU.  Every call below returns before anything is launched.  The library services that translation unit uses are
+// Stand-alone driver for the host-side code of vsr_ops.hip, fp32 and bf16: the argument checks of its entry points, the trunk
+// plan (which convs have a Winograd image, the blob and workspace sizes) and the pack table it builds, run with the host sanitizers
+// on a machine without a GPU.  Every call below returns before anything is launched.  The library services that translation unit uses are
 // stubbed here: the size queries restate the documented sizes closely enough for the plan arithmetic (the real ones are compared
-// in tests/test_vsr_host.py), the pack table runner only inspects the table it is handed.
+// in tests/test_vsr_host.py and tests/test_vsr_bf16_host.py), the pack table runner only inspects the table it is handed.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //       image_restoration_amd/csrc/vsr_ops.hip tests/helpers/vsr_host_checks.cpp \
@@ -13,10 +13,11 @@
 
 #include "../../image_restoration_amd/csrc/sr_internal.h"
 #include "../../include/sr_hip_vsr.h"
+#include "../../include/sr_hip_vsr_bf16.h"
 
 static char g_err[512];
 static size_t g_rows = 0, g_wino_rows = 0, g_image_bytes = 0;
-static bool g_rows_inside = true;
+static bool g_rows_inside = true, g_rows_bf16_ok = true, g_bf16 = false;
 namespace sr {
 void set_error(const char* fmt, ...) {
   va_list ap;
@@ -32,15 +33,18 @@ bool wino_f32_weights_eligible(int cout, int cin) { return cin >= 8 && cout > 0 
 size_t wino_f32_image_floats(int cout, int cin_pad) { return (size_t)cout * cin_pad * 16; }
 int conv3x3_wino_f32(const sr_conv3x3_desc*, const float*, hipStream_t, bool) { return SR_ELAUNCH; }  // never reached
 size_t pack_table_bytes(size_t entries) { return align_up((entries + 1) * sizeof(PackEntry), 256); }
-int pack_table_run(std::vector<PackEntry>& entries, void* blob, size_t image_bytes, bool, hipStream_t) {
+int pack_table_run(std::vector<PackEntry>& entries, void* blob, size_t image_bytes, bool bf16, hipStream_t) {
   g_rows = entries.size();
   g_wino_rows = 0;
   g_image_bytes = image_bytes;
-  g_rows_inside = true;
+  g_rows_inside = g_rows_bf16_ok = true;
+  g_bf16 = bf16;
   for (const PackEntry& e : entries) {  // every image starts inside [blob, blob + image_bytes)
     if (e.kind == 3) ++g_wino_rows;
     if ((char*)e.out < (char*)blob || (char*)e.out >= (char*)blob + image_bytes) g_rows_inside = false;
     if (e.kind == 0 && ((char*)e.bout < (char*)blob || (char*)e.bout >= (char*)blob + image_bytes)) g_rows_inside = false;
+    // what a bf16 table promises on top: forward rows only, a segment length, images and biases 256-byte aligned
+    if (e.kind != 0 || e.seg <= 0 || ((uintptr_t)e.out & 255u) || ((uintptr_t)e.bout & 255u)) g_rows_bf16_ok = false;
   }
   return SR_OK;
 }
@@ -53,6 +57,16 @@ extern "C" int sr_conv3x3_cin_pad(int cin, int first_seg, int seg) {
 extern "C" size_t sr_conv3x3_packed_weight_floats(int cout, int cin_pad) { return (size_t)((cout + 31) / 32 * 32) * cin_pad * 9; }
 extern "C" size_t sr_conv3x3_packed_bias_floats(int cout) { return (size_t)((cout + 31) / 32 * 32); }
 extern "C" int sr_conv3x3_f32(const sr_conv3x3_desc*, void*) { return SR_ELAUNCH; }  // never reached
+static int r16(int v) { return (v + 15) / 16 * 16; }
+extern "C" int sr_conv3x3_cin_pad16(int cin, int first_seg, int seg) {
+  if (seg <= 0) return cin == first_seg ? r16(cin) : -1;
+  if (cin < first_seg || (cin - first_seg) % seg) return -1;
+  return r16(first_seg) + (cin - first_seg) / seg * r16(seg);
+}
+extern "C" size_t sr_conv3x3_packed_weight_elems_bf16(int cout, int cin, int first_seg, int seg, int) {
+  return (size_t)((cout + 31) / 32 * 32) * sr_conv3x3_cin_pad16(cin, first_seg, seg) * 9;
+}
+extern "C" int sr_conv3x3_bf16(const sr_conv3x3_desc*, void*) { return SR_ELAUNCH; }  // never reached
 
 static int failures = 0;
 static int checks = 0;
@@ -100,7 +114,7 @@ static sr_vsr_prop_desc good() {
   return d;
 }
 
-int main() {
+static void checks_f32() {
   const char* PI = "sr_vsr_prop_input_f32";
   REFUSED(sr_vsr_prop_input_f32(nullptr, nullptr), PI, "null descriptor");
   sr_vsr_prop_desc d = good();
@@ -195,7 +209,7 @@ int main() {
         // the pack table: one row per conv and one per Winograd image, every image inside the blob
         std::vector<const float*> params(2 * convs, P);
         EXPECT(sr_vsr_trunk_pack_f32(&c, params.data(), (float*)(uintptr_t)(1 << 20), nullptr) == SR_OK);
-        EXPECT(g_rows == (size_t)(convs + wino) && g_wino_rows == (size_t)wino && g_rows_inside);
+        EXPECT(g_rows == (size_t)(convs + wino) && g_wino_rows == (size_t)wino && g_rows_inside && !g_bf16);
         EXPECT(g_image_bytes + sr::pack_table_bytes(g_rows) == bytes);
         params[2 * convs - 1] = nullptr;
         REFUSED(sr_vsr_trunk_pack_f32(&c, params.data(), (float*)(uintptr_t)(1 << 20), nullptr), "sr_vsr_trunk_pack_f32", "null parameter");
@@ -225,7 +239,159 @@ int main() {
   REFUSED(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns - 8, 2, 8, 8, WS, need, nullptr), TR, "smaller than the image");
   REFUSED_AS(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns, 2, 8, 8, WS, need - 1, nullptr), SR_ENOSPACE, TR, "workspace");
   REFUSED_AS(sr_vsr_trunk_f32(&c, P, P, in_ns, Q, out_ns, 2, 8, 8, nullptr, need, nullptr), SR_ENOSPACE, TR, "workspace");
+}
 
+// ---------------------------------------------------------------------------------------------------------------- bf16
+static char* const P16 = (char*)256;
+static char* const Q16 = (char*)4096;
+static char* const ODD16 = (char*)260;  // 4-byte aligned only
+
+static sr_rvsr_prop_desc good16() {
+  sr_rvsr_prop_desc d = {};
+  d.frame = (const float*)ODD16;
+  d.frame_img_stride = 3 * 20;
+  d.prev = P16;
+  d.prev_img_stride = 16 * 20 * 4;
+  d.flow = (const float*)ODD16;
+  d.flow_img_stride = 2 * 20;
+  d.frame_out = Q16;
+  d.frame_out_img_stride = 16 * 20 * 3;
+  d.warp_out = Q16 + 2 * 16 * 20;
+  d.warp_out_img_stride = 16 * 20 * 3;
+  d.n = 2;
+  d.h = 4;
+  d.w = 5;
+  d.fb = 2;
+  return d;
+}
+
+static void checks_bf16() {
+  const char* PI = "sr_rvsr_prop_input_bf16";
+  REFUSED(sr_rvsr_prop_input_bf16(nullptr, nullptr), PI, "null descriptor");
+  sr_rvsr_prop_desc d = good16();
+  d.frame = nullptr;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "null frame");
+  d = good16();
+  d.warp_out = nullptr;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "null frame");
+  d = good16();
+  d.flow = nullptr;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "both");
+  d = good16();
+  d.prev = nullptr;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "both");
+  for (int which = 0; which < 6; ++which) {
+    d = good16();
+    (which == 0 ? d.n : which == 1 ? d.h : which == 2 ? d.w : d.fb) = which < 4 ? 0 : which == 4 ? 65535 : -3;
+    REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "bad shape");
+  }
+  d = good16();
+  d.n = 65536;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "bad shape");
+  d = good16();
+  d.h = 1 << 14;
+  d.w = 1 << 14;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "too large");
+  d = good16();
+  d.prev = ODD16;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "16-byte aligned");
+  d = good16();
+  d.frame_out = ODD16;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "16-byte aligned");
+  d = good16();
+  d.warp_out = ODD16;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "16-byte aligned");
+  d = good16();
+  d.frame = (const float*)258;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "4-byte aligned");
+  d = good16();
+  d.flow = (const float*)257;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "4-byte aligned");
+  d = good16();
+  d.prev_img_stride += 4;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "multiples of 8");
+  d = good16();
+  d.warp_out_img_stride += 1;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "multiples of 8");
+  d = good16();
+  d.frame_out_img_stride += 12;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "multiples of 8");
+  d = good16();
+  d.frame_img_stride = 3 * 20 - 1;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+  d = good16();
+  d.flow_img_stride = 2 * 20 - 1;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+  d = good16();
+  d.prev_img_stride = 16 * 20 * 2 - 8;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+  d = good16();
+  d.warp_out_img_stride = 16 * 20;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+  d = good16();
+  d.frame_out_img_stride = 16 * 20 - 8;
+  REFUSED(sr_rvsr_prop_input_bf16(&d, nullptr), PI, "smaller than the image");
+
+  // ---- trunk configs and plans
+  const sr_vsr_trunk_cfg bad[] = {{0, 1, 1}, {-16, 1, 1}, {8, 1, 1}, {24, 1, 1}, {64, -1, 1}, {64, 1, 0}, {64, 1, 3}, {8192, 1, 1}, {64, 5000, 1}};
+  for (const sr_vsr_trunk_cfg& c : bad) {
+    REFUSED(sr_rvsr_trunk_pack_bf16(&c, (const float* const*)P16, Q16, nullptr), "sr_rvsr_trunk_pack_bf16", "bad config");
+    REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, 0, Q16, 0, 1, 8, 8, nullptr, 0, nullptr), "sr_rvsr_trunk_bf16", "bad config");
+    EXPECT(sr_rvsr_trunk_packed_bytes_bf16(&c) == 0);
+    EXPECT(sr_rvsr_trunk_workspace_bytes_bf16(&c, 1, 8, 8) == 0);
+  }
+  EXPECT(sr_rvsr_trunk_packed_bytes_bf16(nullptr) == 0);
+  EXPECT(sr_rvsr_trunk_workspace_bytes_bf16(nullptr, 1, 8, 8) == 0);
+  const int feats[] = {64, 48, 16};
+  for (int nf : feats)
+    for (int segs = 1; segs <= 2; ++segs)
+      for (int nb = 0; nb <= 30; nb += 15) {
+        const sr_vsr_trunk_cfg c = {nf, nb, segs};
+        const int convs = 1 + 2 * nb;
+        const size_t bytes = sr_rvsr_trunk_packed_bytes_bf16(&c);
+        EXPECT(bytes > 0 && bytes % 256 == 0);
+        EXPECT(sr_rvsr_trunk_workspace_bytes_bf16(&c, 2, 13, 37) == 3 * sr::align_up((size_t)2 * nf * 13 * 37 * 2, 256));
+        EXPECT(sr_rvsr_trunk_workspace_bytes_bf16(&c, 0, 13, 37) == 0 && sr_rvsr_trunk_workspace_bytes_bf16(&c, 1, -1, 37) == 0);
+        // the pack table: one bf16 row per conv, every image and bias inside the blob
+        std::vector<const float*> params(2 * convs, (const float*)P16);
+        EXPECT(sr_rvsr_trunk_pack_bf16(&c, params.data(), (void*)(uintptr_t)(1 << 20), nullptr) == SR_OK);
+        EXPECT(g_rows == (size_t)convs && g_wino_rows == 0 && g_rows_inside && g_rows_bf16_ok && g_bf16);
+        EXPECT(g_image_bytes + sr::pack_table_bytes(g_rows) == bytes);
+        params[2 * convs - 1] = nullptr;
+        REFUSED(sr_rvsr_trunk_pack_bf16(&c, params.data(), (void*)(uintptr_t)(1 << 20), nullptr), "sr_rvsr_trunk_pack_bf16", "null parameter");
+      }
+  const sr_vsr_trunk_cfg c = {64, 2, 1};
+  const float* two[10];
+  for (const float*& p : two) p = (const float*)P16;
+  REFUSED(sr_rvsr_trunk_pack_bf16(&c, nullptr, Q16, nullptr), "sr_rvsr_trunk_pack_bf16", "null argument");
+  REFUSED(sr_rvsr_trunk_pack_bf16(&c, two, nullptr, nullptr), "sr_rvsr_trunk_pack_bf16", "null argument");
+  REFUSED(sr_rvsr_trunk_pack_bf16(&c, two, ODD16, nullptr), "sr_rvsr_trunk_pack_bf16", "256-byte aligned");
+
+  const char* TR = "sr_rvsr_trunk_bf16";
+  void* const WS = (void*)(uintptr_t)(1 << 20);
+  const size_t need = sr_rvsr_trunk_workspace_bytes_bf16(&c, 2, 8, 8);
+  const long long in_ns = 80 * 64, out_ns = 64 * 64;
+  REFUSED(sr_rvsr_trunk_bf16(&c, nullptr, P16, in_ns, Q16, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, nullptr, in_ns, Q16, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, nullptr, out_ns, 2, 8, 8, WS, need, nullptr), TR, "null packed");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, Q16, out_ns, 0, 8, 8, WS, need, nullptr), TR, "bad shape");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, Q16, out_ns, 2, 8, -8, WS, need, nullptr), TR, "bad shape");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, Q16, out_ns, 1, 4096, 4096, WS, need, nullptr), TR, "too large");
+  REFUSED(sr_rvsr_trunk_bf16(&c, ODD16, P16, in_ns, Q16, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, ODD16, in_ns, Q16, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, ODD16, out_ns, 2, 8, 8, WS, need, nullptr), TR, "aligned");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, Q16, out_ns, 2, 8, 8, (char*)WS + 16, need, nullptr), TR, "aligned");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns + 4, Q16, out_ns, 2, 8, 8, WS, need, nullptr), TR, "multiples of 8");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns - 8, Q16, out_ns, 2, 8, 8, WS, need, nullptr), TR, "smaller than the image");
+  REFUSED(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, Q16, out_ns - 8, 2, 8, 8, WS, need, nullptr), TR, "smaller than the image");
+  REFUSED_AS(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, Q16, out_ns, 2, 8, 8, WS, need - 1, nullptr), SR_ENOSPACE, TR, "workspace");
+  REFUSED_AS(sr_rvsr_trunk_bf16(&c, P16, P16, in_ns, Q16, out_ns, 2, 8, 8, nullptr, need, nullptr), SR_ENOSPACE, TR, "workspace");
+
+}
+
+int main() {
+  checks_f32();
+  checks_bf16();
   printf("vsr_host_checks: %d checks, %d failures\n", checks, failures);
   return failures ? 1 : 0;
 }

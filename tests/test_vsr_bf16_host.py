@@ -16,8 +16,8 @@ All are <= 0.75, so the GPU tests check IconVSR whole (and in the split form as 
 y64 over the bound, first case): zeroed flows 7.3, swapped flow planes 7.1, zeroed backward features 13.9 (the second case, measured
 once the same way: 7.1, 7.1, 15.4).
 
-The host side of vsr_ops_bf16.hip (argument checks, size queries, plan building) is also run under the host sanitizers by the
-stand-alone program tests/helpers/vsr_bf16_host_checks.cpp; its result is reported in DESIGN.md §33.
+The bf16 host side of vsr_ops.hip (argument checks, size queries, plan building) is also run under the host sanitizers by the
+stand-alone program tests/helpers/vsr_host_checks.cpp; its result is reported in DESIGN.md §33 and §35.
 """
 import ast
 import ctypes as C

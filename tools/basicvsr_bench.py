@@ -19,6 +19,7 @@ reported:
                 bf16 convs; SpyNet stays fp32 (same parameters, its own module)
     other fp32  with --other-tree: the product of another built checkout of this project (the parent commit, say), imported as a
                 second copy of the package under another name so that it runs on its own libsr_hip.so in the same process
+    other bf16  with --other-tree: that checkout's product with set_compute_dtype('bf16'), compared with this tree's bf16 row
 
 Per variant the median and the spread (min, max) of the rounds are reported.  Also: one trunk call alone on one frame (ms, TFLOP/s on the algorithmic 2 * 9 * cin * cout FLOP per pixel, fraction of the 157.3
 TFLOP/s fp32 MFMA peak) and sr_vsr_prop_input_f32 alone (ms and bytes/s on 32 bytes per corner, pixel and block, plus the store,
@@ -164,7 +165,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--out', default=None)
     ap.add_argument('--wino-off', action='store_true', help='sr_dev_set_wino_f32(0): the product path on the direct kernels too')
-    ap.add_argument('--other-tree', default=None, help='root of another built checkout of this project: its fp32 product as a further row')
+    ap.add_argument('--other-tree', default=None, help='root of another built checkout of this project: its fp32 and bf16 products as further rows')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('basicvsr_bench needs a GPU: timings are device timings')
@@ -177,10 +178,13 @@ def main():
     ref = TorchBasicVSR(net).to(dev).eval()
     net16 = BasicVSR(num_feat=64, num_block=args.num_block).to(dev).eval().set_compute_dtype('bf16')
     net16.load_state_dict(net.state_dict())
-    other = None
+    other = other16 = None
     if args.other_tree:
-        other = other_basicvsr(args.other_tree)(num_feat=64, num_block=args.num_block).to(dev).eval()
+        cls = other_basicvsr(args.other_tree)
+        other = cls(num_feat=64, num_block=args.num_block).to(dev).eval()
         other.load_state_dict(net.state_dict())
+        other16 = cls(num_feat=64, num_block=args.num_block).to(dev).eval().set_compute_dtype('bf16')
+        other16.load_state_dict(net.state_dict())
     nf, nb = 64, args.num_block
     rows = []
     with torch.no_grad():
@@ -190,10 +194,11 @@ def main():
             d_layer, d_torch = float((per_layer_forward(net, x) - y).abs().max()), float((ref(x) - y).abs().max())
             variants = (('product', lambda: net(x)), ('per-layer', lambda: per_layer_forward(net, x)), ('torch', lambda: ref(x)),
                         ('bf16', lambda: net16(x)))
-            d_bf16, d_other = float((net16(x) - y).abs().max()), None
+            y16 = net16(x)
+            d_bf16, d_other, d_other16 = float((y16 - y).abs().max()), None, None
             if other is not None:
-                variants += (('other fp32', lambda: other(x)),)
-                d_other = float((other(x) - y).abs().max())
+                variants += (('other fp32', lambda: other(x)), ('other bf16', lambda: other16(x)))
+                d_other, d_other16 = float((other(x) - y).abs().max()), float((other16(x) - y16).abs().max())
             # interleaved at the level of single forwards: a round runs every variant once; median over the rounds
             for _ in range(args.warmup):
                 for _, fn in variants:
@@ -203,7 +208,7 @@ def main():
                 for k, fn in variants:
                     ms[k].append(timed(fn, 1, 0))
             r = dict(case=f'{n} frames {h}x{w}', frames=n, max_abs_diff_per_layer=d_layer, max_abs_diff_torch=d_torch,
-                     max_abs_diff_bf16=d_bf16, max_abs_diff_other=d_other)
+                     max_abs_diff_bf16=d_bf16, max_abs_diff_other=d_other, max_abs_diff_other_bf16=d_other16)
             for k, _ in variants:
                 r[k + '_ms'] = statistics.median(ms[k])
                 r[k + '_ms_per_frame'] = statistics.median(ms[k]) / n
@@ -242,6 +247,8 @@ def main():
         if 'other fp32_ms' in r:
             print(f'    other fp32 {r["other fp32_ms"]:.2f} ms [{r["other fp32_ms_min"]:.2f}, {r["other fp32_ms_max"]:.2f}]; max|other - '
                   f'product| {r["max_abs_diff_other"]:.2e}')
+            print(f'    other bf16 {r["other bf16_ms"]:.2f} ms [{r["other bf16_ms_min"]:.2f}, {r["other bf16_ms_max"]:.2f}]; max|other bf16 - '
+                  f'bf16| {r["max_abs_diff_other_bf16"]:.2e}')
         print(f'    bf16 trunk call {r["trunk_bf16_ms"]:.3f} ms = {r["trunk_bf16_tflops"]:.1f} TFLOP/s ({r["trunk_bf16_of_peak"]:.3f} of the bf16 '
               f'peak); bf16 prop input {1000 * r["prop_input_bf16_ms"]:.1f} us = {r["prop_input_bf16_gbytes_per_s"]:.0f} GB/s')
     if args.out:
