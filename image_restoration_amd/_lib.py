@@ -574,6 +574,36 @@ VSR_BF16_SIGNATURES = {
     'sr_rvsr_trunk_bf16': (C.c_int, [C.POINTER(VsrTrunkCfg), _P, _P, C.c_longlong, _P, C.c_longlong, _I, _I, _I, _P, C.c_size_t, _P]),
 }
 
+
+
+class VsrPropBwdDesc(C.Structure):
+    """struct sr_vsr_prop_bwd_desc (include/sr_hip_vsr_bwd.h)."""
+    _fields_ = [('g', C.c_void_p), ('g_img_stride', C.c_longlong), ('prev', C.c_void_p), ('prev_img_stride', C.c_longlong),
+                ('flow', C.c_void_p), ('flow_img_stride', C.c_longlong), ('dprev', C.c_void_p), ('dprev_img_stride', C.c_longlong),
+                ('dflow', C.c_void_p), ('dflow_img_stride', C.c_longlong), ('n', C.c_int), ('h', C.c_int), ('w', C.c_int),
+                ('fb', C.c_int)]
+
+
+class VsrTrunkBwdDesc(C.Structure):
+    """struct sr_vsr_trunk_bwd_desc (include/sr_hip_vsr_bwd.h)."""
+    _fields_ = [('packed_dgrad', C.c_void_p), ('in_', C.c_void_p), ('in_img_stride', C.c_longlong), ('out', C.c_void_p),
+                ('out_img_stride', C.c_longlong), ('stack', C.c_void_p), ('stack_bytes', C.c_size_t), ('dout', C.c_void_p),
+                ('dout_img_stride', C.c_longlong), ('din', C.c_void_p), ('din_img_stride', C.c_longlong),
+                ('dparams', C.POINTER(C.c_void_p)), ('accumulate', C.c_int), ('n', C.c_int), ('h', C.c_int), ('w', C.c_int),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_vsr_bwd.h declares
+VSR_BWD_SIGNATURES = {
+    'sr_vsr_prop_input_bwd_f32': (C.c_int, [C.POINTER(VsrPropBwdDesc), _P]),
+    'sr_vsr_trunk_keep_bytes': (C.c_size_t, [C.POINTER(VsrTrunkCfg), _I, _I, _I]),
+    'sr_vsr_trunk_keep_f32': (C.c_int, [C.POINTER(VsrTrunkCfg), _P, _P, C.c_longlong, _P, C.c_longlong, _I, _I, _I, _P, C.c_size_t, _P]),
+    'sr_vsr_trunk_packed_dgrad_bytes': (C.c_size_t, [C.POINTER(VsrTrunkCfg)]),
+    'sr_vsr_trunk_pack_dgrad_f32': (C.c_int, [C.POINTER(VsrTrunkCfg), C.POINTER(C.c_void_p), _P, _P]),
+    'sr_vsr_trunk_bwd_workspace_bytes': (C.c_size_t, [C.POINTER(VsrTrunkCfg), _I, _I, _I]),
+    'sr_vsr_trunk_bwd_f32': (C.c_int, [C.POINTER(VsrTrunkCfg), C.POINTER(VsrTrunkBwdDesc), _P]),
+}
+
 _lib = None
 
 
@@ -590,7 +620,7 @@ def load():
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
             + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()) + list(VSR_BF16_SIGNATURES.items()) \
-            + list(FLOW_BWD_SIGNATURES.items()):
+            + list(FLOW_BWD_SIGNATURES.items()) + list(VSR_BWD_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -22,9 +22,17 @@ CB16 bf16 activations: the clip tensor is [n * b, 2 * num_feat 
 sr_rvsr_prop_input_bf16 and one sr_rvsr_trunk_bf16, the head runs on the bf16 convs and ``conv_last`` stores fp32 NCHW.  The input
 clip, SpyNet and the flows stay fp32, so ``get_flow`` is the same bits in both modes; ``num_feat % 16 == 0`` is required.
 
-Inference only, x4: outputs never carry a grad_fn, and a forward that would need a graph (train mode, grad enabled,
-something requiring grad) raises NotImplementedError — training (the recurrent backward, on top of SpyNet's backward in
-archs/spynet_autograd.py) is the follow-up.
+x4 only.  By default the networks run inference: outputs carry no grad_fn, and a forward that would need a graph (train mode, grad
+enabled, something requiring grad) raises NotImplementedError.  ``BasicVSR.set_autograd(True)`` enables fp32 training, as
+``SpyNet.set_autograd`` does for the flow estimator (and it switches ``self.spynet`` too): ``get_flow`` then goes through
+SpyNet's Function when a ``spynet.*`` parameter requires grad, and ``propagate`` is ONE autograd Function over (x, the two flow
+tensors, the parameters) whose backward is archs/basicvsr_autograd.py — the head batched over the frames, then the two branches
+walked against their direction, per step one sr_vsr_trunk_bwd_f32 and one sr_vsr_prop_input_bwd_f32.  Autograd itself joins the
+two Functions.  The training forward issues the inference forward's launches (sr_vsr_trunk_keep_f32 is the same driver) and its
+output is the inference output bit for bit.  The frames are data: a clip that requires grad is refused.  bf16 and IconVSR stay
+forward only (IconVSR's keyframe branch and fusion convs are the follow-up), and so does training from an option file
+(models/video_recurrent_model.py).  What a training forward keeps, and the one step of the backward that is not bit-reproducible,
+are stated in archs/basicvsr_autograd.py.
 ValueError, before anything is launched, for: fewer than two frames (the reference's ``get_flow`` cannot reshape an empty batch),
 channels other than 3, a dtype other than fp32, a side of 32 pixels or fewer (SpyNet's rule), ``num_feat % 8 != 0``.
 """
@@ -103,6 +111,20 @@ class ConvResidualBlocks(HipDriverNet):
                               stem + '_pack')
         return cfg, blob
 
+    def packed_dgrad(self, dev):
+        """The blob of fp32 data-gradient images (sr_vsr_trunk_pack_dgrad_f32) for the current parameters: a second kind beside
+        the forward blob, under the same weights key."""
+        lib, cfg = _lib.load(), self.cfg()
+        with torch.cuda.device(dev):
+            return self._blob(('dgrad', False), lib, cfg, torch.cuda.current_stream(dev).cuda_stream, 'sr_vsr_trunk_packed_dgrad_bytes',
+                              'sr_vsr_trunk_pack_dgrad')
+
+    def run_keep(self, src, out, packed=None):
+        """``run`` on fp32 windows with every activation the backward reads kept: (out, the activation stack) — one
+        sr_vsr_trunk_keep_f32 call, the launches of ``run``."""
+        cfg, blob = packed or self.packed(src.device)
+        return hip_ops.vsr_trunk_keep(cfg, blob, src, out)
+
     def run(self, src, out, packed=None):
         """``src``: CB8 (fp32) or CB16 (bf16) window [frame block, feature windows]; ``out``: window of num_out_ch channels of the
         same kind; ``packed``: what ``packed(device, bf16)`` returned for the current parameters (looked up here when None)."""
@@ -125,6 +147,7 @@ class BasicVSR(HipGenerator):
     """
 
     _fuses = True
+    _autograd = False
 
     def __init__(self, num_feat=64, num_block=15, spynet_path=None):
         super().__init__()
@@ -159,6 +182,15 @@ class BasicVSR(HipGenerator):
         """The _Layout record of the compute dtype."""
         return _LAYOUTS[self.compute_dtype]
 
+    # ------------------------------------------------------------------------------------------------------ training
+    def set_autograd(self, enabled=True):
+        """Whether an fp32 forward that needs a graph (train mode, grad enabled, a parameter or a flow requiring grad) builds one
+        (archs/basicvsr_autograd.py) instead of being refused; also switches ``self.spynet``.  Off by default; set after
+        construction, like set_compute_dtype.  Returns self."""
+        self._autograd = bool(enabled)
+        self.spynet.set_autograd(enabled)
+        return self
+
     # ------------------------------------------------------------------------------------------------------ refusals
     def _check(self, x, flows=()):
         if x.dim() != 5 or x.size(2) != 3:
@@ -183,9 +215,18 @@ class BasicVSR(HipGenerator):
         if not (x.is_cuda and all(f.is_cuda for f in flows)):
             raise _lib.SrHipError(f'{type(self).__name__}.forward runs only on a HIP device (no CPU fallback): move the module and '
                                   'inputs with .to("cuda")')
-        if needs_graph:
-            raise NotImplementedError(f'{type(self).__name__} runs inference only: call .eval() (or run under torch.no_grad()); '
-                                      'training (SpyNet\'s backward and the recurrent backward) is the follow-up')
+        if needs_graph and not self._autograd:
+            raise NotImplementedError(self._refusal())
+        if needs_graph and x.requires_grad:
+            raise NotImplementedError(f'{type(self).__name__} computes no gradient of the input clip: x must not require grad (the '
+                                      'frames are data; the parameters and flows passed to propagate are differentiated)')
+        return needs_graph
+
+    def _refusal(self):
+        """What a forward that needs a graph is told while set_autograd is off."""
+        return (f'{type(self).__name__} runs inference only by default: call .eval() (or run under torch.no_grad()), or enable the '
+                'recurrent backward (on top of SpyNet\'s) with set_autograd(True); training from an option file '
+                '(VideoRecurrentModel) is the follow-up')
 
     def _check_frames(self, n):
         """A subclass's own rule on the number of frames."""
@@ -194,8 +235,11 @@ class BasicVSR(HipGenerator):
     def get_flow(self, x):
         """(flows_forward, flows_backward), each [b, n - 1, 2, h, w]: flows_backward[:, i] is SpyNet(x_i, x_{i+1}),
         flows_forward[:, i] is SpyNet(x_{i+1}, x_i)."""
-        self._check(x)
-        with torch.no_grad():
+        needs_graph = self._check(x)
+        # a graph through SpyNet only when one of its parameters wants a gradient: the flows then carry a grad_fn (spynet_apply,
+        # per chunk) that autograd joins to propagate's; otherwise as in inference
+        flow_graph = bool(needs_graph) and any(p.requires_grad for p in self.spynet.parameters())
+        with torch.set_grad_enabled(flow_graph):
             x = x.contiguous()
             b, n, c, h, w = x.shape
             x_1 = x[:, :-1].reshape(-1, c, h, w)
@@ -209,53 +253,85 @@ class BasicVSR(HipGenerator):
             return flows[pairs:].view(b, n - 1, 2, h, w), flows[:pairs].view(b, n - 1, 2, h, w)
 
     # --------------------------------------------------------------------------------------------------- propagation
-    def _branch(self, trunk, x, flows, feats, cb0, order, tin):
+    def _branch(self, trunk, x, flows, feats, cb0, order, tin, keep=None):
         """One propagation branch over the frames in ``order``: per step one step-input launch (sr_vsr_prop_input_f32 /
         sr_rvsr_prop_input_bf16) and one trunk call (sr_vsr_trunk_f32 / sr_rvsr_trunk_bf16).  ``flows[:, j]`` warps the feature of
-        the previous step onto frame ``order[k]``: j = i for the backward branch, i - 1 for the forward branch."""
+        the previous step onto frame ``order[k]``: j = i for the backward branch, i - 1 for the forward branch.  ``keep`` (a
+        dict, fp32): the trunk call is sr_vsr_trunk_keep_f32, every step gets a trunk input of its own and ``keep[i]`` =
+        (that input, the activation stack) of frame i."""
         L = self._layout()
         CB, b, fb = L.CB, x.size(0), self.num_feat // L.lanes
-        frame_out, warp_out = CB(tin, 0, 1), CB(tin, 1, fb)
-        prev, packed, src = None, trunk.packed(x.device, L.bf16), CB(tin)
+        prev, packed = None, trunk.packed(x.device, L.bf16)
         for k, i in enumerate(order):
+            if keep is not None and k > 0:
+                tin = torch.empty_like(tin)
             flow = None if prev is None else flows[:, min(i, order[k - 1])]
-            L.prop_input(x[:, i], prev, flow, warp_out, frame_out)
-            prev = trunk.run(src, CB(feats[i * b:(i + 1) * b], cb0, fb), packed)
+            L.prop_input(x[:, i], prev, flow, CB(tin, 1, fb), CB(tin, 0, 1))
+            out = CB(feats[i * b:(i + 1) * b], cb0, fb)
+            if keep is None:
+                prev = trunk.run(CB(tin), out, packed)
+            else:
+                prev, stack = trunk.run_keep(CB(tin), out, packed)
+                keep[i] = (tin, stack)
 
-    def _reconstruct(self, feats, frames, y):
+    def _reconstruct(self, feats, frames, y, keep=None):
         """The upsampling head on images [s, e) of the frame-major clip tensors, into y[s:e].  In bf16 every activation is stored
         as bf16 once, after its epilogue; conv_last writes fp32 NCHW and the x4 bilinear base of the fp32 frames is added in fp32
-        in both modes."""
+        in both modes.  ``keep`` (a list): receives the four activations the head's backward reads — the fused feature, the two
+        shuffled maps and conv_hr's output, each after its LeakyReLU."""
         L = self._layout()
         out = L.CB(feats)
         if self._fuses:     # BasicVSR: fusion 1x1 of [backward, forward]; IconVSR reconstructs from the forward feature alone
             out = L.conv1x1(out, L.packed(self, self.fusion), act_slope=0.1)
-        out = L.pixel_shuffle(L.conv3x3(out, L.packed(self, self.upconv1), act_slope=0.1), self.num_feat, 2)
-        out = L.pixel_shuffle(L.conv3x3(out, L.packed(self, self.upconv2), act_slope=0.1), 64, 2)
-        out = L.conv3x3(out, L.packed(self, self.conv_hr), act_slope=0.1)
-        L.conv3x3(out, L.packed(self, self.conv_last), out_nchw=y)
+        up1 = L.pixel_shuffle(L.conv3x3(out, L.packed(self, self.upconv1), act_slope=0.1), self.num_feat, 2)
+        up2 = L.pixel_shuffle(L.conv3x3(up1, L.packed(self, self.upconv2), act_slope=0.1), 64, 2)
+        hr = L.conv3x3(up2, L.packed(self, self.conv_hr), act_slope=0.1)
+        L.conv3x3(hr, L.packed(self, self.conv_last), out_nchw=y)
         hip_ops.bilinear_up(frames, 4, out=y)
+        if keep is not None:
+            keep.extend((out, up1, up2, hr))
 
-    def propagate(self, x, flows_forward, flows_backward):
-        """The network after ``get_flow``: x [b, n, 3, h, w], flows [b, n - 1, 2, h, w] -> [b, n, 3, 4h, 4w]."""
-        self._check(x, (flows_forward, flows_backward))
+    def run_forward(self, x, flows_forward, flows_backward, keep=None):
+        """The launches of ``propagate`` on contiguous device tensors, under no_grad.  ``keep`` (a dict, fp32 only) makes it the
+        training forward — the same launches, with sr_vsr_trunk_keep_f32 as the trunk call — and receives what the backward
+        reads (archs/basicvsr_autograd.py):
+            x, flows_forward, flows_backward    the inputs
+            feats                               the per-clip feature tensor
+            backward, forward                   per branch {frame i: (the trunk input of the step, its activation stack)}
+            head                                [(s, e, [fused, up1, up2, hr])] per chunk of frames [s, e)"""
         with torch.no_grad():
-            x, flows_forward, flows_backward = x.contiguous(), flows_forward.contiguous(), flows_backward.contiguous()
             b, n, _, h, w = x.shape
             L = self._layout()
             blk, dtype, fb, dev = L.lanes, L.dtype, self.num_feat // L.lanes, x.device
             feats = torch.empty((n * b, 2 * fb, h, w, blk), dtype=dtype, device=dev)
             tin = torch.empty((b, 1 + fb, h, w, blk), dtype=dtype, device=dev)
-            self._branch(self.backward_trunk, x, flows_backward, feats, 0, list(range(n - 1, -1, -1)), tin)
-            self._branch(self.forward_trunk, x, flows_forward, feats, fb, list(range(n)), tin)
+            steps = (None, None) if keep is None else ({}, {})
+            self._branch(self.backward_trunk, x, flows_backward, feats, 0, list(range(n - 1, -1, -1)), tin, steps[0])
+            self._branch(self.forward_trunk, x, flows_forward, feats, fb, list(range(n)), torch.empty_like(tin) if keep is not None else tin,
+                         steps[1])
             # reconstruction, frame-major: image i * b + k is frame i of clip k
             frames = x.transpose(0, 1).reshape(n * b, 3, h, w)
             y = torch.empty((n * b, 3, 4 * h, 4 * w), dtype=torch.float32, device=dev)
             # per image: the 4 * num_feat / 256 / 64-channel maps at 2x / 4x size alive around a conv, about 4 maps of 64 x 16 h w floats
             chunk = max(1, _RECON_BUDGET // (4 * 4 * 64 * 16 * h * w))
+            head = []
             for s in range(0, n * b, chunk):
-                self._reconstruct(feats[s:s + chunk], frames[s:s + chunk], y[s:s + chunk])
+                acts = None if keep is None else []
+                self._reconstruct(feats[s:s + chunk], frames[s:s + chunk], y[s:s + chunk], acts)
+                head.append((s, min(s + chunk, n * b), acts))
+            if keep is not None:
+                keep.update(x=x, flows_forward=flows_forward, flows_backward=flows_backward, feats=feats, backward=steps[0],
+                            forward=steps[1], head=head)
             return y.view(n, b, 3, 4 * h, 4 * w).transpose(0, 1).contiguous()
+
+    def propagate(self, x, flows_forward, flows_backward):
+        """The network after ``get_flow``: x [b, n, 3, h, w], flows [b, n - 1, 2, h, w] -> [b, n, 3, 4h, 4w].  With
+        ``set_autograd(True)``, in train mode with something requiring grad, the result carries a grad_fn whose backward fills the
+        gradients of the parameters and of the two flow tensors (archs/basicvsr_autograd.py)."""
+        if self._check(x, (flows_forward, flows_backward)):
+            from .basicvsr_autograd import basicvsr_apply
+            return basicvsr_apply(self, x.contiguous(), flows_forward, flows_backward)
+        return self.run_forward(x.contiguous(), flows_forward.contiguous(), flows_backward.contiguous())
 
     def forward(self, x):
         return self.propagate(x, *self.get_flow(x))
@@ -312,6 +388,17 @@ class IconVSR(BasicVSR):
     2 * temporal_padding + 1 frames, and BasicVSR's refusals."""
 
     _fuses = False
+
+    def set_autograd(self, enabled=True):
+        if enabled:
+            raise NotImplementedError('IconVSR.set_autograd(True): IconVSR runs inference only; its training (the backward of the EDVR '
+                                      'keyframe branch and of the fusion convs, on top of BasicVSR\'s recurrent backward) is the '
+                                      'follow-up')
+        return super().set_autograd(False)
+
+    def _refusal(self):
+        return ('IconVSR runs inference only: call .eval() (or run under torch.no_grad()); training (the backward of its keyframe '
+                'branch and fusion convs, on top of BasicVSR\'s recurrent backward) is the follow-up')
 
     def __init__(self, num_feat=64, num_block=15, keyframe_stride=5, temporal_padding=2, spynet_path=None, edvr_path=None):
         HipGenerator.__init__(self)

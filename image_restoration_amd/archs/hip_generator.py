@@ -125,7 +125,10 @@ def residual_block_backward(net, sv, b, g, router, **extra):
 
 class GradRouter:
     """Where the parameter gradients of one backward go: into the tuple returned to autograd (``grads``, None for a frozen
-    parameter), or, with an optim.FlatAdam arena attached (``net._grad_sink``), added straight into the arena."""
+    parameter), or, with an optim.FlatAdam arena attached (``net._grad_sink``), added straight into the arena.  A parameter that
+    several launches of one backward contribute to (a head run in chunks, a trunk shared by the steps of a recurrent branch) is
+    stored by the first of them and ADDED into by the later ones, in call order, by the kernels' accumulate mode: ``wgrad`` does so
+    by itself, whole-call targets through ``shared_targets``."""
 
     def __init__(self, net, params, need_p):
         self.need_p = need_p
@@ -135,6 +138,8 @@ class GradRouter:
         self.to_sink = self.sink is not None and any(need_p)
         if self.to_sink and not all(need_p):
             raise _lib.SrHipError('flat-arena mode needs every generator parameter to require grad')
+        self._first = {}     # index of a conv's weight -> what its first wgrad call returned
+        self._shared = {}    # id of the first parameter of a shared_targets call -> its pointers
 
     def wgrad(self, conv, src, d, scale=1.0, dilation=None):
         """weight / bias gradient of ``conv`` from its source and its pre-activation output gradient: the dense 3x3 path of
@@ -144,6 +149,9 @@ class GradRouter:
         if not (self.to_sink or self.need_p[iw] or self.need_p[ib]):
             return
         out = (self.sink.grad_ptrs[iw], self.sink.grad_ptrs[ib]) if self.to_sink else None   # arena: added in place
+        first = None if self.to_sink else self._first.get(iw)
+        if first is not None:                                  # a later launch of the same conv adds into the first one's tensors
+            out = (first[0].data_ptr(), first[1].data_ptr())
         k = conv.weight.shape[2]
         if dilation is None and k == 3:
             res = hip_ops.conv3x3_wgrad(src, d, conv.out_channels, conv.in_channels, scale=scale, out=out)
@@ -151,9 +159,20 @@ class GradRouter:
             res = hip_ops.conv7x7_wgrad(src, d, conv.out_channels, conv.in_channels, scale=scale, out=out)
         else:
             res = hip_ops.convd_wgrad(src, d, conv.out_channels, conv.in_channels, k, dilation or 1, scale=scale, out=out)
-        if not self.to_sink:
+        if not self.to_sink and first is None:
+            self._first[iw] = res
             self.grads[iw] = res[0] if self.need_p[iw] else None
             self.grads[ib] = res[1] if self.need_p[ib] else None
+
+    def shared_targets(self, params):
+        """``targets`` for parameters that several calls of one backward write: the first call gets fresh tensors to store into,
+        every later call the same pointers with accumulate set."""
+        key = id(params[0])
+        if not self.to_sink and key in self._shared:
+            return self._shared[key], True
+        ptrs, accumulate = self.targets(params)
+        self._shared[key] = ptrs
+        return ptrs, accumulate
 
     def targets(self, params):
         """Device pointers (or None) the gradients of ``params`` go to, and whether they accumulate (arena)."""

@@ -1084,5 +1084,6 @@ extern "C" const char* sr_kernel_name(int id) {
                                     "spynet_level_upT_kernel",            "resize_bilinear_adjoint_kernel"};
     return qnames[id - 169];
   }
+  if (id == 178) return "vsr_prop_input_bwd_kernel";  // vsr_bwd_ops.hip (include/sr_hip_vsr_bwd.h); 177 stays unnamed
   return (id >= 0 && id < 8) ? names[id] : "";
 }

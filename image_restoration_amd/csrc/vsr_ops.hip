@@ -29,6 +29,7 @@
 #include "../../include/sr_hip_vsr_bf16.h"
 #include "flow_device.h"
 #include "sr_internal.h"
+#include "vsr_trunk.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -338,10 +339,13 @@ int trunk_pack(const sr_vsr_trunk_cfg* cfg, const Kind& k, const char* who, cons
   return sr::pack_table_run(tab, packed, P.packed_bytes, k.bf16, stream);
 }
 
-// ConvResidualBlocks: `who` the entry point, `ws_query` the name of its workspace query (for the message)
+// ConvResidualBlocks: `who` the entry point, `ws_query` the name of its workspace query (for the message).  The activations are
+// numbered in the order they are written: 0 the first conv's output, 1 + 2 b the ReLU output of block b, 2 + 2 b its output (the
+// last one is `out`).  keep = false: activation i lives in buffer i % 3 of the workspace, the rotation of sr_hip_vsr.h.  keep = true
+// (include/sr_hip_vsr_bwd.h): the workspace is the caller's stack of 2 * num_block buffers and activation i stays in buffer i.
 int trunk_run(const sr_vsr_trunk_cfg* cfg, const Kind& k, const char* who, const char* ws_query, const void* packed_, const void* in,
               long long in_img_stride, void* out, long long out_img_stride, int n, int h, int w, void* workspace,
-              size_t workspace_bytes, hipStream_t stream) {
+              size_t workspace_bytes, hipStream_t stream, bool keep = false) {
   const char* const packed = (const char*)packed_;
   TrunkPlan P;
   TRUNK_PLAN(P, cfg, k, who);
@@ -355,13 +359,12 @@ int trunk_run(const sr_vsr_trunk_cfg* cfg, const Kind& k, const char* who, const
   SR_CHECK_ARG(in_img_stride % mult == 0 && out_img_stride % mult == 0, "%s: image strides must be multiples of %d %s", who, mult, k.unit);
   SR_CHECK_ARG(n == 1 || (in_img_stride >= (long long)P.cin_pad0 * hw && out_img_stride >= feat_ns),
                "%s: an image stride is smaller than the image", who);
-  const size_t one = act_bytes(k, nf, n, h, w), need = cfg->num_block > 0 ? 3 * one : 0;
+  const size_t one = act_bytes(k, nf, n, h, w), need = (keep ? 2 : cfg->num_block > 0 ? 3 : 0) * (keep ? cfg->num_block : 1) * one;
   if (need > 0 && (!workspace || workspace_bytes < need)) {
-    sr::set_error("%s: workspace of %zu bytes, %zu needed (%s)", who, workspace_bytes, need, ws_query);
+    sr::set_error("%s: %s of %zu bytes, %zu needed (%s)", who, keep ? "stack" : "workspace", workspace_bytes, need, ws_query);
     return SR_ENOSPACE;
   }
-  void* buf[3] = {nullptr, nullptr, nullptr};
-  for (int i = 0; i < 3 && need; ++i) buf[i] = (char*)workspace + (size_t)i * one;
+  auto act = [&](int i) -> void* { return (char*)workspace + (size_t)(keep ? i : i % 3) * one; };
 
   const bool wino = !k.bf16 && sr::wino_f32_mode() != 0;
   size_t ci = 0;
@@ -397,22 +400,37 @@ int trunk_run(const sr_vsr_trunk_cfg* cfg, const Kind& k, const char* who, const
 
   const int nb = cfg->num_block;
   // main.0 + LeakyReLU(0.1)
-  int rc = nb == 0 ? conv(in, in_img_stride, out, out_img_stride, 0.1f, nullptr) : conv(in, in_img_stride, buf[0], feat_ns, 0.1f, nullptr);
-  int x = 0;  // buffer that holds the block input
+  int rc = nb == 0 ? conv(in, in_img_stride, out, out_img_stride, 0.1f, nullptr) : conv(in, in_img_stride, act(0), feat_ns, 0.1f, nullptr);
   for (int b = 0; b < nb && rc == SR_OK; ++b) {
-    const int t = (x + 1) % 3, y = (x + 2) % 3;
-    rc = conv(buf[x], feat_ns, buf[t], feat_ns, 0.f, nullptr);  // relu(conv1(x))
+    void *const x = act(2 * b), *const t = act(2 * b + 1);  // the block input and relu(conv1(x))
+    rc = conv(x, feat_ns, t, feat_ns, 0.f, nullptr);
     if (rc) break;
     if (b + 1 == nb)
-      rc = conv(buf[t], feat_ns, out, out_img_stride, 1.f, buf[x]);  // x + conv2(.)
+      rc = conv(t, feat_ns, out, out_img_stride, 1.f, x);  // x + conv2(.)
     else
-      rc = conv(buf[t], feat_ns, buf[y], feat_ns, 1.f, buf[x]);
-    x = y;
+      rc = conv(t, feat_ns, act(2 * b + 2), feat_ns, 1.f, x);
   }
   return rc;
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------- what vsr_bwd_ops.hip shares of the driver (vsr_trunk.h)
+namespace sr {
+
+size_t vsr_trunk_act_bytes(const sr_vsr_trunk_cfg* cfg, int n, int h, int w) {
+  TrunkPlan P;
+  if (!make_plan(cfg, kF32, &P) || n <= 0 || h <= 0 || w <= 0) return 0;
+  return act_bytes(kF32, cfg->num_feat, n, h, w);
+}
+
+int vsr_trunk_keep_run(const sr_vsr_trunk_cfg* cfg, const char* who, const char* stack_query, const float* packed, const float* in,
+                       long long in_img_stride, float* out, long long out_img_stride, int n, int h, int w, void* stack,
+                       size_t stack_bytes, hipStream_t stream) {
+  return trunk_run(cfg, kF32, who, stack_query, packed, in, in_img_stride, out, out_img_stride, n, h, w, stack, stack_bytes, stream, true);
+}
+
+}  // namespace sr
 
 // ------------------------------------------------------------------------------------------- fp32 (include/sr_hip_vsr.h)
 extern "C" int sr_vsr_prop_input_f32(const sr_vsr_prop_desc* d, void* stream) {

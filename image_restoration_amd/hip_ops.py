@@ -1804,3 +1804,103 @@ def vsr_trunk_bf16(cfg, blob, src, out):
     _launch_arg('sr_rvsr_trunk_bf16', src.device,
                 *_vsr_trunk_args('vsr_trunk_bf16', CB16, 16, 'sr_rvsr_trunk_workspace_bytes_bf16', cfg, blob, src, out))
     return out
+
+
+# ---- the recurrent backward of BasicVSR: the step-input adjoint, the trunk call that keeps its activations and the trunk's
+# backward (include/sr_hip_vsr_bwd.h) ----
+
+def vsr_prop_input_bwd(g, prev, flow, dprev=None, dflow=None):
+    """The adjoint of vsr_prop_input with respect to ``prev`` and ``flow`` — one sr_vsr_prop_input_bwd_f32 launch.  ``g``: CB8
+    window, the gradient of warp_out; ``prev``: the CB8 window that was warped; ``flow``: the fp32 [N, 2, H, W] view the forward
+    read.  ``dprev``: CB8 window the gradient is ADDED into with float atomics (never zeroed here), or None; ``dflow``: fp32
+    [N, 2, H, W] view with dense images the flow gradient is stored into (a float64 gather, bit-reproducible), or None."""
+    who = 'vsr_prop_input_bwd'
+    _arg(isinstance(g, CB8) and isinstance(prev, CB8) and (prev.n, prev.h, prev.w, prev.cbn) == (g.n, g.h, g.w, g.cbn),
+         f'{who}: g and prev must be CB8 windows of one shape')
+    n, h, w = g.n, g.h, g.w
+    _need_cuda(flow, who)
+    _arg(dprev is not None or dflow is not None, f'{who}: nothing to compute')
+    d = _lib.VsrPropBwdDesc()
+    for name, t in (('flow', flow), ('dflow', dflow)):
+        if t is None:
+            continue
+        _arg(t.dtype == torch.float32 and tuple(t.shape) == (n, 2, h, w) and t[0].is_contiguous() and t.device == g.device,
+             f'{who}: {name} must be an fp32 [{n}, 2, {h}, {w}] view with dense images, got {t.dtype} {tuple(t.shape)}')
+        setattr(d, name, t.data_ptr())
+        setattr(d, name + '_img_stride', t.stride(0))
+    if dprev is not None:
+        _arg(isinstance(dprev, CB8) and (dprev.n, dprev.h, dprev.w, dprev.cbn) == (n, h, w, g.cbn), f'{who}: dprev does not fit')
+        d.dprev, d.dprev_img_stride = dprev.ptr, dprev.img_stride
+    d.g, d.g_img_stride, d.prev, d.prev_img_stride = g.ptr, g.img_stride, prev.ptr, prev.img_stride
+    d.n, d.h, d.w, d.fb = n, h, w, g.cbn
+    _launch_arg('sr_vsr_prop_input_bwd_f32', g.device, C.byref(d))
+    return dprev, dflow
+
+
+def vsr_trunk_keep_bytes(cfg, n, h, w):
+    """Bytes of the activation stack of vsr_trunk_keep — sr_vsr_trunk_keep_bytes."""
+    return _lib.load().sr_vsr_trunk_keep_bytes(C.byref(cfg), n, h, w)
+
+
+def vsr_trunk_keep(cfg, blob, src, out, stack=None):
+    """vsr_trunk with every activation its backward reads written to ``stack`` (uint8, sr_vsr_trunk_keep_bytes; allocated when
+    None) — one sr_vsr_trunk_keep_f32 call, the launches of vsr_trunk.  Returns (out, stack)."""
+    who = 'vsr_trunk_keep'
+    _arg(isinstance(src, CB8) and isinstance(out, CB8) and src.cbn == 1 + cfg.cin_segs * cfg.num_feat // 8
+         and out.cbn == cfg.num_feat // 8 and (out.n, out.h, out.w) == (src.n, src.h, src.w), f'{who}: windows do not fit the config')
+    nbytes = vsr_trunk_keep_bytes(cfg, src.n, src.h, src.w)
+    if stack is None:
+        stack = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=src.device)
+    _arg(stack.dtype == torch.uint8 and stack.numel() >= nbytes and stack.device == src.device, f'{who}: the stack is too small')
+    _launch_arg('sr_vsr_trunk_keep_f32', src.device, C.byref(cfg), blob.data_ptr(), src.ptr, src.img_stride, out.ptr, out.img_stride,
+                src.n, src.h, src.w, stack.data_ptr(), nbytes)
+    return out, stack
+
+
+def vsr_trunk_stack_views(cfg, stack, n, h, w):
+    """The activations of a vsr_trunk_keep stack as CB8 tensors, in the order of the header: the first conv's output, then per
+    block the ReLU output and (but for the last block) the block output."""
+    one = -(-(4 * n * cfg.num_feat * h * w) // 256) * 256
+    return [CB8(stack[i * one:i * one + 4 * n * cfg.num_feat * h * w].view(torch.float32).view(n, cfg.num_feat // 8, h, w, 8))
+            for i in range(2 * cfg.num_block)]
+
+
+def vsr_trunk_pack_dgrad(cfg, params, blob=None):
+    """The blob of data-gradient images of a trunk from its parameters in state_dict order — sr_vsr_trunk_pack_dgrad_f32."""
+    blob, ptrs = _vsr_trunk_pack_args('vsr_trunk_pack_dgrad', 'sr_vsr_trunk_packed_dgrad_bytes', cfg, params, blob)
+    _launch_arg('sr_vsr_trunk_pack_dgrad_f32', blob.device, C.byref(cfg), ptrs, blob.data_ptr())
+    return blob
+
+
+def vsr_trunk_bwd(cfg, dblob, src, out, stack, dout, din, targets, accumulate=False):
+    """The adjoint of vsr_trunk_keep — one sr_vsr_trunk_bwd_f32 call.  ``dblob``: vsr_trunk_pack_dgrad of the forward's parameters;
+    ``src`` / ``out`` / ``stack``: the forward's input window, output window and stack; ``dout``: CB8 window, the gradient of
+    ``out``; ``din``: CB8 window laid out like ``src`` (block 0 receives the frame block's gradient) or None; ``targets``: one
+    device pointer (int) or None per parameter in state_dict order — a None target's launch is skipped; a bias target whose
+    weight target is None gets a scratch weight target.  ``accumulate``: the gradients are ADDED into the targets."""
+    who = 'vsr_trunk_bwd'
+    lib = _lib.load()
+    fb, nparams = cfg.num_feat // 8, lib.sr_vsr_trunk_num_params(C.byref(cfg))
+    _arg(nparams > 0 and len(targets) == nparams, f'{who}: {len(targets)} targets, the config has {nparams} parameters')
+    _arg(isinstance(src, CB8) and isinstance(out, CB8) and isinstance(dout, CB8) and src.cbn == 1 + cfg.cin_segs * fb
+         and out.cbn == dout.cbn == fb and _same(dout, out) and (out.n, out.h, out.w) == (src.n, src.h, src.w)
+         and (din is None or (isinstance(din, CB8) and _same(din, src))), f'{who}: windows do not fit the config')
+    n, h, w, dev = src.n, src.h, src.w, src.device
+    targets = list(targets)
+    for i in range(0, nparams, 2):
+        if targets[i] is None and targets[i + 1] is not None:
+            nw = cfg.num_feat * (3 + cfg.cin_segs * cfg.num_feat if i == 0 else cfg.num_feat) * 9
+            targets[i] = scratch(dev, 4 * nw, 'vsr_trunk_bwd_dw').data_ptr()
+    nstack, nws = vsr_trunk_keep_bytes(cfg, n, h, w), lib.sr_vsr_trunk_bwd_workspace_bytes(C.byref(cfg), n, h, w)
+    _arg(nstack == 0 or (stack is not None and stack.numel() >= nstack), f'{who}: the stack is too small')
+    ws = scratch(dev, nws, who)
+    d = _lib.VsrTrunkBwdDesc()
+    d.packed_dgrad, d.in_, d.in_img_stride, d.out, d.out_img_stride = dblob.data_ptr(), src.ptr, src.img_stride, out.ptr, out.img_stride
+    d.stack, d.stack_bytes = (stack.data_ptr() if nstack else None), nstack
+    d.dout, d.dout_img_stride = dout.ptr, dout.img_stride
+    if din is not None:
+        d.din, d.din_img_stride = din.ptr, din.img_stride
+    d.dparams = (C.c_void_p * nparams)(*targets)
+    d.accumulate, d.n, d.h, d.w, d.workspace, d.workspace_bytes = int(accumulate), n, h, w, ws.data_ptr(), nws
+    _launch_arg('sr_vsr_trunk_bwd_f32', dev, C.byref(cfg), C.byref(d))
+    return din

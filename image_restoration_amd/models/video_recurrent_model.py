@@ -9,9 +9,9 @@ one folder per ``dataset[idx]`` (strided over the ranks), scores every frame, an
 
 ``network_g.compute_dtype: bf16`` (an extension; the reference is fp32 only) runs BasicVSR / IconVSR on their bf16 forward.
 
-Inference only: building it with ``is_train`` raises NotImplementedError — training the recurrent networks (the recurrent backward,
-``fix_flow`` / ``flow_lr_mul``, the recurrent REDS dataset; SpyNet's own backward exists: ``SpyNet.set_autograd``) is the
-follow-up."""
+Inference only: building it with ``is_train`` raises NotImplementedError — the networks' backward exists
+(``BasicVSR.set_autograd``, archs/basicvsr_autograd.py, on top of ``SpyNet.set_autograd``); training them from an option file
+(``fix_flow`` / ``flow_lr_mul``, the recurrent REDS dataset) is the follow-up."""
 import os
 import os.path as osp
 from collections import Counter, OrderedDict
@@ -28,8 +28,8 @@ class VideoRecurrentModel(VideoBaseModel):
 
     def __init__(self, opt):
         if opt['is_train']:
-            raise NotImplementedError('VideoRecurrentModel tests only: training the recurrent video networks (SpyNet\'s backward, '
-                                      'fix_flow / flow_lr_mul, the recurrent REDS dataset) is the follow-up')
+            raise NotImplementedError('VideoRecurrentModel tests only: training the recurrent video networks from an option file '
+                                      '(fix_flow / flow_lr_mul, the recurrent REDS dataset, on BasicVSR.set_autograd) is the follow-up')
         # network_g.compute_dtype of a network that sets its dtype after construction (BasicVSR, IconVSR keep the reference's
         # constructor): taken out of a copy, so build_network sees the reference's keys and the caller's dict stays as it is
         net_opt, compute_dtype = dict(opt['network_g']), None

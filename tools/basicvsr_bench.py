@@ -2,6 +2,7 @@
 """Times BasicVSR inference (archs/basicvsr_arch.py) on one GPU, in the manner of tools/spynet_bench.py.
 
     python tools/basicvsr_bench.py [--num-block 30] [--reps 20] [--warmup 5] [--other-tree DIR] [--out results.json]
+    python tools/basicvsr_bench.py --backward [--num-block 30] [--batch 4] [--reps 5] [--warmup 2] [--out results.json]
 
 Cases: one 180x320 clip of 15 frames, and one 64x112 clip of 7 frames (below the Winograd size rule: the trunks run on the direct
 kernels).  Three variants on the same parameters and input, the launch profiler off, each forward timed with device events;
@@ -25,6 +26,12 @@ Per variant the median and the spread (min, max) of the rounds are reported.  Al
 TFLOP/s fp32 MFMA peak) and sr_vsr_prop_input_f32 alone (ms and bytes/s on 32 bytes per corner, pixel and block, plus the store,
 the frame and the flow), both from device events around 50 back-to-back calls; the same two for the bf16 entry points (fraction of
 the 2500.0 TFLOP/s dense bf16 MFMA peak).
+
+--backward times training instead (archs/basicvsr_autograd.py): forward plus backward of L = sum(y * g) at the REDS recipe's shape —
+15 frames of 64x64, num_feat 64, --batch clips — of the product with set_autograd(True) and, as a yardstick, of the torch variant
+above under PyTorch-ROCm autograd on the same device and parameters, the two alternating round by round; the largest relative L2
+between their parameter gradients; the bytes the training forward keeps per clip; and the per-kernel split of one product step from
+the launch profiler (count, milliseconds, share), with the share of the two step kernels (ids 159 and 178).
 """
 import argparse
 import importlib.util
@@ -158,6 +165,96 @@ def burst(fn, calls=50):
     return a.elapsed_time(b) / calls
 
 
+def kept_bytes(keep):
+    """Bytes of the tensors a training forward kept (BasicVSR.run_forward's ``keep``), each storage once."""
+    seen, total = set(), 0
+
+    def walk(v):
+        nonlocal total
+        if isinstance(v, torch.Tensor):
+            if v.untyped_storage().data_ptr() not in seen:
+                seen.add(v.untyped_storage().data_ptr())
+                total += v.untyped_storage().nbytes()
+        elif hasattr(v, 'buf'):
+            walk(v.buf)
+        elif isinstance(v, dict):
+            for u in v.values():
+                walk(u)
+        elif isinstance(v, (list, tuple)):
+            for u in v:
+                walk(u)
+    walk({k: v for k, v in keep.items() if k not in ('x', 'flows_forward', 'flows_backward')})
+    return total
+
+
+def backward_bench(args, dev):
+    """--backward: see the module docstring."""
+    import ctypes as C
+    from image_restoration_amd import _lib
+    lib = _lib.load()
+    n, h, w, b, nf, nb = 15, 64, 64, args.batch, 64, args.num_block
+    torch.manual_seed(0)
+    net = BasicVSR(num_feat=nf, num_block=nb).to(dev).train().set_autograd(True)
+    ref = TorchBasicVSR(net).to(dev).train()
+    x = torch.rand(b, n, 3, h, w, device=dev)
+    g = torch.randn(b, n, 3, 4 * h, 4 * w, device=dev)
+    params = list(net.parameters())
+
+    def step(model):
+        for q in params:
+            q.grad = None
+        (model(x) * g).sum().backward()
+    step(net)
+    mine = [q.grad.clone() for q in params]
+    step(ref)
+    rel = max(float((a - q.grad).norm() / q.grad.norm()) for a, q in zip(mine, params))
+    for _ in range(args.warmup):
+        step(net)
+        step(ref)
+    ms = {'product': [], 'torch': []}
+    for _ in range(args.reps):
+        ms['product'].append(timed(lambda: step(net), 1, 0))
+        ms['torch'].append(timed(lambda: step(ref), 1, 0))
+    keep = {}
+    with torch.no_grad():
+        ff, fb = net.get_flow(x)
+        net.run_forward(x, ff, fb, keep=keep)
+    kept = kept_bytes(keep)
+    del keep
+    cap = 1 << 16
+    _lib.check(lib.sr_profile_start(cap), 'sr_profile_start')
+    try:
+        step(net)
+        torch.cuda.synchronize()
+    finally:
+        recs = (_lib.LaunchRecord * cap)()
+        cnt = C.c_int(0)
+        _lib.check(lib.sr_profile_stop(recs, cap, C.byref(cnt)), 'sr_profile_stop')
+    split = {}
+    for i in range(min(cnt.value, cap)):
+        name = lib.sr_kernel_name(recs[i].kernel_id).decode() or f'id {recs[i].kernel_id}'
+        e = split.setdefault(name, dict(kernel_id=int(recs[i].kernel_id), launches=0, ms=0.0))
+        e['launches'] += 1
+        e['ms'] += float(recs[i].ms)
+    total = sum(e['ms'] for e in split.values())
+    steps = sum(e['ms'] for e in split.values() if e['kernel_id'] in (159, 178))
+    r = dict(case=f'{b} clips of {n} frames {h}x{w}, num_feat {nf}, num_block {nb}', product_ms=statistics.median(ms['product']),
+             product_ms_min=min(ms['product']), product_ms_max=max(ms['product']), torch_ms=statistics.median(ms['torch']),
+             torch_ms_min=min(ms['torch']), torch_ms_max=max(ms['torch']), max_rel_l2_gradients=rel, kept_bytes_per_clip=kept / b,
+             profiled_launches=int(cnt.value), profiled_ms=total, step_kernels_share=steps / total if total else None, split=split)
+    r['torch_over_product'] = r['torch_ms'] / r['product_ms']
+    print(f'{r["case"]}: forward + backward product {r["product_ms"]:.1f} ms [{r["product_ms_min"]:.1f}, {r["product_ms_max"]:.1f}], torch '
+          f'{r["torch_ms"]:.1f} ms [{r["torch_ms_min"]:.1f}, {r["torch_ms_max"]:.1f}], torch / product {r["torch_over_product"]:.2f}; '
+          f'max rel L2 of the parameter gradients {rel:.2e}; kept {kept / b / 2 ** 20:.0f} MiB per clip')
+    print(f'    launch profile of one step: {cnt.value} launches, {total:.1f} ms in kernels, step kernels (159, 178) '
+          f'{100 * steps / max(total, 1e-30):.1f} %')
+    for name, e in sorted(split.items(), key=lambda kv: -kv[1]['ms']):
+        print(f'    {name:44s} id {e["kernel_id"]:3d}  {e["launches"]:6d} launches {e["ms"]:9.2f} ms {100 * e["ms"] / max(total, 1e-30):5.1f} %')
+    if args.out:
+        with open(args.out, 'w') as f:
+            json.dump(dict(backward=True, reps=args.reps, warmup=args.warmup, rows=[r]), f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--num-block', type=int, default=30)
@@ -166,10 +263,15 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--wino-off', action='store_true', help='sr_dev_set_wino_f32(0): the product path on the direct kernels too')
     ap.add_argument('--other-tree', default=None, help='root of another built checkout of this project: its fp32 and bf16 products as further rows')
+    ap.add_argument('--backward', action='store_true', help='time forward + backward at the REDS recipe\'s shape instead, against '
+                    'PyTorch-ROCm autograd, with the per-kernel split')
+    ap.add_argument('--batch', type=int, default=4, help='clips per step of --backward')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('basicvsr_bench needs a GPU: timings are device timings')
     dev = torch.device('cuda:0')
+    if args.backward:
+        return backward_bench(args, dev)
     if args.wino_off:
         from image_restoration_amd import _lib
         _lib.load().sr_dev_set_wino_f32(0)
