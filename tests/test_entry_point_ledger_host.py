@@ -1,6 +1,9 @@
 """Every function include/sr_hip.h declares is either PINNED (mapped to the test that compares it with a reference of the
 same operation) or EXEMPT (a non-compute entry point, with the reason).  A new entry point fails this test until it is
-placed in one of the two tables; a removed one fails it until its row goes.  Runs without a GPU."""
+placed in one of the two tables; a removed one fails it until its row goes.  Runs without a GPU.
+
+The same holds for include/sr_hip_edvr.h and include/sr_hip_dcn.h (MORE_HEADERS): their comments name entry points of other headers, so
+their declarations are parsed as declarations (a return type at the start of a line), not as any ``sr_name(``."""
 import ast
 import os
 import re
@@ -180,6 +183,41 @@ EXEMPT = {
 }
 
 
+_EDVR = 'tests/test_edvr_ops_gpu.py::'
+_DCN = 'tests/test_dcn_ops_gpu.py::'
+MORE_HEADERS = {
+    'include/sr_hip_edvr.h': ({
+        'sr_conv3x3s2_f32': _EDVR + 'test_conv3x3s2_forward',
+        'sr_cb8_zero_insert2_f32': _EDVR + 'test_zero_insert_is_bit_exact',
+        'sr_pool3x3s2_fwd_f32': _EDVR + 'test_pool_forward',
+        'sr_pool3x3s2_bwd_f32': _EDVR + 'test_pool_backward',
+        'sr_tsa_corr_fwd_f32': _EDVR + 'test_tsa_corr',
+        'sr_tsa_corr_bwd_f32': _EDVR + 'test_tsa_corr',
+        'sr_tsa_gate_fwd_f32': _EDVR + 'test_tsa_gate',
+        'sr_tsa_gate_bwd_f32': _EDVR + 'test_tsa_gate',
+    }, {
+        'sr_conv3x3s2_lds_bytes': _SIZE,
+    }),
+    'include/sr_hip_dcn.h': ({
+        'sr_dcn_fwd_f32': _DCN + 'test_forward',
+        'sr_dcn_cols_f32': _DCN + 'test_backward',
+        'sr_dcn_bwd_data_f32': _DCN + 'test_backward',
+        # no test calls these two by name: they run inside DCNFn's backward (hip_ops.PackedDcnT packs Wt for dcol = Wt dz, from which
+        # dx, doffset and dmask come; hip_ops.dcn_wgrad unpacks dweight), which this test holds against float64 on every DCN of EDVR
+        'sr_dcn_pack_t_f32': 'tests/test_edvr_opwise_gpu.py::test_deformable_convolutions',
+        'sr_dcn_weight_unpack_f32': 'tests/test_edvr_opwise_gpu.py::test_deformable_convolutions',
+    }, {
+        'sr_dcn_cols_bytes': _SIZE,
+        'sr_dcn_packed_t_weight_floats': _SIZE,
+    }),
+}
+
+
+def declared_functions(header_text):
+    """Function names a header DECLARES: a return type at the start of a line, then the name."""
+    return set(re.findall(r'^(?:int|size_t|const char\s*\*)\s+(sr_[a-z0-9_]+)\s*\(', header_text, re.M))
+
+
 def declared_symbols(header_text):
     """Function names declared in the header (the parse of test_boundary.py::test_library_exports_every_declared_symbol)."""
     return set(re.findall(r'\b(sr_[a-z0-9_]+)\s*\(', header_text))
@@ -241,3 +279,24 @@ def test_the_ledger_notices_a_new_declaration_and_a_dropped_row(tmp_path):
     wrong = dict(PINNED, sr_cb8_axpby_f32=_LAYOUT + 'test_no_such_test')
     assert ledger_problems(declared, wrong, EXEMPT) == [
         'sr_cb8_axpby_f32: tests/test_layout_ops_gpu.py has no test function test_no_such_test']
+
+
+def test_every_entry_point_of_the_edvr_and_dcn_headers_is_pinned_or_exempt():
+    allowed = re.compile(r'(_bytes|_floats)$')
+    for header, (pinned, exempt) in MORE_HEADERS.items():
+        declared = declared_functions(open(os.path.join(ROOT, header)).read())
+        assert len(declared) >= 7, f'{header}: the parse found too few declarations'
+        problems = [p.replace('include/sr_hip.h', header) for p in ledger_problems(declared, pinned, exempt)]
+        assert not problems, problems
+        for s in exempt:
+            assert allowed.search(s), s
+    dcn = declared_functions(open(os.path.join(ROOT, 'include', 'sr_hip_dcn.h')).read())
+    assert {'sr_dcn_pack_t_f32', 'sr_dcn_weight_unpack_f32'} <= dcn
+    fewer = dict(MORE_HEADERS['include/sr_hip_dcn.h'][0])
+    del fewer['sr_dcn_pack_t_f32']
+    assert ledger_problems(dcn, fewer, MORE_HEADERS['include/sr_hip_dcn.h'][1]) == ['sr_dcn_pack_t_f32: in neither table']
+    # the two are reached from the Function the pinned test replays, and from nowhere else in the fp32 route
+    ops = open(os.path.join(ROOT, 'image_restoration_amd', 'hip_ops.py')).read()
+    auto = open(os.path.join(ROOT, 'image_restoration_amd', 'hip_autograd.py')).read()
+    assert "launch('sr_dcn_pack_t_f32'" in ops and "launch('sr_dcn_weight_unpack_f32'" in ops
+    assert 'H.PackedDcnT(weight)' in auto and 'H.dcn_wgrad(cols, dzc, cout, cin' in auto
