@@ -604,6 +604,18 @@ VSR_BWD_SIGNATURES = {
     'sr_vsr_trunk_bwd_f32': (C.c_int, [C.POINTER(VsrTrunkCfg), C.POINTER(VsrTrunkBwdDesc), _P]),
 }
 
+
+class VsrPropBwdDetDesc(C.Structure):
+    """struct sr_vsr_prop_bwd_det_desc (include/sr_hip_vsr_det.h)."""
+    _fields_ = [('d', VsrPropBwdDesc), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_vsr_det.h declares
+VSR_DET_SIGNATURES = {
+    'sr_vsr_prop_input_bwd_det_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
+    'sr_vsr_prop_input_bwd_det_f32': (C.c_int, [C.POINTER(VsrPropBwdDetDesc), _P]),
+}
+
 _lib = None
 
 
@@ -620,7 +632,7 @@ def load():
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
             + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()) + list(VSR_BF16_SIGNATURES.items()) \
-            + list(FLOW_BWD_SIGNATURES.items()) + list(VSR_BWD_SIGNATURES.items()):
+            + list(FLOW_BWD_SIGNATURES.items()) + list(VSR_BWD_SIGNATURES.items()) + list(VSR_DET_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

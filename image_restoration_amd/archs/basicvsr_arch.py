@@ -27,12 +27,13 @@ enabled, something requiring grad) raises NotImplementedError.  ``BasicVSR.set_a
 ``SpyNet.set_autograd`` does for the flow estimator (and it switches ``self.spynet`` too): ``get_flow`` then goes through
 SpyNet's Function when a ``spynet.*`` parameter requires grad, and ``propagate`` is ONE autograd Function over (x, the two flow
 tensors, the parameters) whose backward is archs/basicvsr_autograd.py — the head batched over the frames, then the two branches
-walked against their direction, per step one sr_vsr_trunk_bwd_f32 and one sr_vsr_prop_input_bwd_f32.  Autograd itself joins the
-two Functions.  The training forward issues the inference forward's launches (sr_vsr_trunk_keep_f32 is the same driver) and its
-output is the inference output bit for bit.  The frames are data: a clip that requires grad is refused.  bf16 and IconVSR stay
-forward only (IconVSR's keyframe branch and fusion convs are the follow-up), and so does training from an option file
-(models/video_recurrent_model.py).  What a training forward keeps, and the one step of the backward that is not bit-reproducible,
-are stated in archs/basicvsr_autograd.py.
+walked against their direction, per step one sr_vsr_trunk_bwd_f32 and one sr_vsr_prop_input_bwd_f32 (with
+``set_autograd(True, deterministic=True)``: sr_vsr_prop_input_bwd_det_f32, which makes the backward bit-reproducible).  Autograd
+itself joins the two Functions.  The training forward issues the inference forward's launches (sr_vsr_trunk_keep_f32 is the same
+driver) and its output is the inference output bit for bit.  The frames are data: a clip that requires grad is refused.  bf16
+and IconVSR stay forward only (IconVSR's keyframe branch and fusion convs are the follow-up).  Training from an option file is
+models/video_recurrent_model.py.  What a training forward keeps, and the one step of the default backward that is not
+bit-reproducible, are stated in archs/basicvsr_autograd.py.
 ValueError, before anything is launched, for: fewer than two frames (the reference's ``get_flow`` cannot reshape an empty batch),
 channels other than 3, a dtype other than fp32, a side of 32 pixels or fewer (SpyNet's rule), ``num_feat % 8 != 0``.
 """
@@ -148,6 +149,7 @@ class BasicVSR(HipGenerator):
 
     _fuses = True
     _autograd = False
+    _deterministic = False
 
     def __init__(self, num_feat=64, num_block=15, spynet_path=None):
         super().__init__()
@@ -183,11 +185,14 @@ class BasicVSR(HipGenerator):
         return _LAYOUTS[self.compute_dtype]
 
     # ------------------------------------------------------------------------------------------------------ training
-    def set_autograd(self, enabled=True):
+    def set_autograd(self, enabled=True, deterministic=False):
         """Whether an fp32 forward that needs a graph (train mode, grad enabled, a parameter or a flow requiring grad) builds one
         (archs/basicvsr_autograd.py) instead of being refused; also switches ``self.spynet``.  Off by default; set after
-        construction, like set_compute_dtype.  Returns self."""
+        construction, like set_compute_dtype.  ``deterministic``: the step-input adjoint of the backward sums in 64-bit integers
+        (sr_vsr_prop_input_bwd_det_f32) instead of with float atomics, which makes the whole backward bit-reproducible; off by
+        default, so a caller that does not ask keeps the atomic scatter and its bits.  Returns self."""
         self._autograd = bool(enabled)
+        self._deterministic = bool(enabled) and bool(deterministic)
         self.spynet.set_autograd(enabled)
         return self
 
@@ -225,8 +230,8 @@ class BasicVSR(HipGenerator):
     def _refusal(self):
         """What a forward that needs a graph is told while set_autograd is off."""
         return (f'{type(self).__name__} runs inference only by default: call .eval() (or run under torch.no_grad()), or enable the '
-                'recurrent backward (on top of SpyNet\'s) with set_autograd(True); training from an option file '
-                '(VideoRecurrentModel) is the follow-up')
+                'recurrent backward (on top of SpyNet\'s) with set_autograd(True), as VideoRecurrentModel does when it trains '
+                'from an option file; IconVSR and bf16 training are the follow-up')
 
     def _check_frames(self, n):
         """A subclass's own rule on the number of frames."""
@@ -389,7 +394,7 @@ class IconVSR(BasicVSR):
 
     _fuses = False
 
-    def set_autograd(self, enabled=True):
+    def set_autograd(self, enabled=True, deterministic=False):
         if enabled:
             raise NotImplementedError('IconVSR.set_autograd(True): IconVSR runs inference only; its training (the backward of the EDVR '
                                       'keyframe branch and of the fusion convs, on top of BasicVSR\'s recurrent backward) is the '

@@ -36,7 +36,9 @@ into the arena in place.
 
 The scatter into the previous step's window (float atomics, sr_vsr_prop_input_bwd_f32) is the ONE step of the whole backward that
 is not bit-reproducible: two backward passes of the same graph agree within that kernel's bound, carried through the steps before
-it, not bit for bit.  Everything else — the head, the trunk backward, dflow, SpyNet's backward — is.  Once differentiable."""
+it, not bit for bit.  Everything else — the head, the trunk backward, dflow, SpyNet's backward — is.  With
+``net.set_autograd(True, deterministic=True)`` that step is sr_vsr_prop_input_bwd_det_f32 (include/sr_hip_vsr_det.h: the same terms
+summed as 64-bit integers, three launches instead of one), and two backward passes agree bit for bit.  Once differentiable."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -70,6 +72,7 @@ def _branch_backward(net, trunk, steps, feats, dfeats, dtin, flows, dflows, cb0,
         return
     b, fb = dtin.size(0), net.num_feat // 8
     cfg, dblob = trunk.cfg(), trunk.packed_dgrad(feats.device)
+    prop_bwd = hip_ops.vsr_prop_input_bwd_det if net._deterministic else hip_ops.vsr_prop_input_bwd
     for k in range(len(order) - 1, -1, -1):
         i = order[k]
         if k == 0 and not wanted:
@@ -82,8 +85,8 @@ def _branch_backward(net, trunk, steps, feats, dfeats, dtin, flows, dflows, cb0,
         if k > 0:
             j = order[k - 1]
             pwin, at = slice(j * b, (j + 1) * b), min(i, j)
-            hip_ops.vsr_prop_input_bwd(CB8(dtin, 1, fb), CB8(feats[pwin], cb0, fb), flows[:, at], CB8(dfeats[pwin], cb0, fb),
-                                       None if dflows is None else dflows[:, at])
+            prop_bwd(CB8(dtin, 1, fb), CB8(feats[pwin], cb0, fb), flows[:, at], CB8(dfeats[pwin], cb0, fb),
+                     None if dflows is None else dflows[:, at])
 
 
 def run_backward(net, saved, dy, router, need_ff, need_fb):

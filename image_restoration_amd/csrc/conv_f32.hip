@@ -1085,5 +1085,9 @@ extern "C" const char* sr_kernel_name(int id) {
     return qnames[id - 169];
   }
   if (id == 178) return "vsr_prop_input_bwd_kernel";  // vsr_bwd_ops.hip (include/sr_hip_vsr_bwd.h); 177 stays unnamed
+  if (id >= 180 && id <= 182) {  // vsr_det_ops.hip (include/sr_hip_vsr_det.h); 179 stays unnamed
+    static const char* const dnames[3] = {"vsr_prop_det_scale_kernel", "vsr_prop_det_scatter_kernel", "vsr_prop_det_finish_kernel"};
+    return dnames[id - 180];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -7,7 +7,7 @@ from .device_pipeline import DeviceClipPipeline, DeviceDegradePipeline, DevicePa
 from .ocr_degradation_dataset import OCRDegradationDataset  # noqa: F401
 from .prefetch_dataloader import (BackgroundIterator, CPUPrefetcher, CUDAPrefetcher, DeviceFeed, HostFeed,  # noqa: F401
                                   PrefetchDataLoader)
-from .reds_dataset import REDSDataset  # noqa: F401
+from .reds_dataset import REDSDataset, REDSRecurrentDataset  # noqa: F401
 from .single_image_dataset import SingleImageDataset  # noqa: F401
 from .synthetic_clip_dataset import SyntheticClipDataset  # noqa: F401
 from .synthetic_dataset import SyntheticPairedDataset  # noqa: F401

@@ -1,7 +1,12 @@
 """Synthetic training clips with REDSDataset's sample dict (``lq`` [t, c, h, w], ``gt`` [c, h, w] of the centre frame, ``key``), so
 the EDVR quick start runs without REDS: one random texture per clip (uniform noise, numpy PCG64), translated from frame to frame by
 the clip's own motion, a whole number of LQ pixels per frame, and the LQ frames are the x``scale`` box average of the GT frames.
-The motion is free of sub-pixel parts on both grids, so every LQ frame is exactly the box average of a GT window."""
+The motion is free of sub-pixel parts on both grids, so every LQ frame is exactly the box average of a GT window.
+
+``recurrent: true`` gives REDSRecurrentDataset's sample dict instead — ``gt`` [t, c, H, W], the ground truth of every frame — for
+the networks that return the whole clip (BasicVSR), and accepts any ``num_frame`` >= 2.  Such a set also serves as a validation set of
+VideoRecurrentModel: every clip is a folder of its own (``folder`` in the item, ``data_info['folder']`` one entry per frame).  The
+default (false) keeps the items above."""
 import numpy as np
 import torch
 from torch.utils import data
@@ -21,8 +26,14 @@ class SyntheticClipDataset(data.Dataset):
         self.num_frame = int(opt.get('num_frame', 5))
         self.max_motion = int(opt.get('max_motion', 2))   # LQ pixels per frame, each axis
         self.seed = int(opt.get('seed', 0))
-        if self.num_frame % 2 != 1:
+        self.recurrent = bool(opt.get('recurrent', False))
+        if self.recurrent:
+            if self.num_frame < 2:
+                raise ValueError(f'a recurrent clip needs num_frame >= 2, but got {self.num_frame}')
+        elif self.num_frame % 2 != 1:
             raise ValueError(f'num_frame should be odd number, but got {self.num_frame}')
+        if self.recurrent:
+            self.data_info = {'folder': [f'{i:08d}' for i in range(self.length) for _ in range(self.num_frame)]}
         if self.gt_size % self.scale:
             raise ValueError(f'gt_size={self.gt_size} must be a multiple of scale={self.scale}')
 
@@ -38,5 +49,8 @@ class SyntheticClipDataset(data.Dataset):
         y0, x0 = (reach if my < 0 else 0), (reach if mx < 0 else 0)
         frames = np.stack([texture[:, y0 + k * my * s:y0 + k * my * s + g, x0 + k * mx * s:x0 + k * mx * s + g] for k in range(t)])
         lq = frames.reshape(t, 3, g // s, s, g // s, s).mean(axis=(3, 5), dtype=np.float32)
+        if self.recurrent:
+            return {'lq': torch.from_numpy(np.ascontiguousarray(lq)), 'gt': torch.from_numpy(np.ascontiguousarray(frames)),
+                    'key': f'synthetic/{index:08d}', 'folder': f'{index:08d}'}
         return {'lq': torch.from_numpy(np.ascontiguousarray(lq)), 'gt': torch.from_numpy(np.ascontiguousarray(frames[t // 2])),
                 'key': f'synthetic/{index:08d}'}

@@ -1837,6 +1837,46 @@ def vsr_prop_input_bwd(g, prev, flow, dprev=None, dflow=None):
     return dprev, dflow
 
 
+def vsr_prop_input_bwd_det_workspace_bytes(n, h, w, fb):
+    """Bytes of the workspace of vsr_prop_input_bwd_det — sr_vsr_prop_input_bwd_det_workspace_bytes."""
+    return _lib.load().sr_vsr_prop_input_bwd_det_workspace_bytes(n, h, w, fb)
+
+
+def vsr_prop_input_bwd_det(g, prev, flow, dprev=None, dflow=None, workspace=None):
+    """vsr_prop_input_bwd with a bit-reproducible ``dprev`` (include/sr_hip_vsr_det.h) — one sr_vsr_prop_input_bwd_det_f32 call:
+    the terms are summed as 64-bit integers in ``workspace`` (uint8, vsr_prop_input_bwd_det_workspace_bytes; the grow-only scratch
+    when None) and added into ``dprev`` with one rounding; ``dflow`` is vsr_prop_input_bwd's bit for bit.  Three launches with
+    ``dprev``, one without."""
+    who = 'vsr_prop_input_bwd_det'
+    _arg(isinstance(g, CB8) and isinstance(prev, CB8) and (prev.n, prev.h, prev.w, prev.cbn) == (g.n, g.h, g.w, g.cbn),
+         f'{who}: g and prev must be CB8 windows of one shape')
+    n, h, w = g.n, g.h, g.w
+    _need_cuda(flow, who)
+    _arg(dprev is not None or dflow is not None, f'{who}: nothing to compute')
+    dd = _lib.VsrPropBwdDetDesc()
+    d = dd.d
+    for name, t in (('flow', flow), ('dflow', dflow)):
+        if t is None:
+            continue
+        _arg(t.dtype == torch.float32 and tuple(t.shape) == (n, 2, h, w) and t[0].is_contiguous() and t.device == g.device,
+             f'{who}: {name} must be an fp32 [{n}, 2, {h}, {w}] view with dense images, got {t.dtype} {tuple(t.shape)}')
+        setattr(d, name, t.data_ptr())
+        setattr(d, name + '_img_stride', t.stride(0))
+    if dprev is not None:
+        _arg(isinstance(dprev, CB8) and (dprev.n, dprev.h, dprev.w, dprev.cbn) == (n, h, w, g.cbn), f'{who}: dprev does not fit')
+        d.dprev, d.dprev_img_stride = dprev.ptr, dprev.img_stride
+        nbytes = vsr_prop_input_bwd_det_workspace_bytes(n, h, w, g.cbn)
+        if workspace is None:
+            workspace = scratch(g.device, nbytes, who)
+        _arg(workspace.dtype == torch.uint8 and workspace.numel() >= nbytes and workspace.device == g.device,
+             f'{who}: the workspace is too small')
+        dd.workspace, dd.workspace_bytes = workspace.data_ptr(), nbytes
+    d.g, d.g_img_stride, d.prev, d.prev_img_stride = g.ptr, g.img_stride, prev.ptr, prev.img_stride
+    d.n, d.h, d.w, d.fb = n, h, w, g.cbn
+    _launch_arg('sr_vsr_prop_input_bwd_det_f32', g.device, C.byref(dd))
+    return dprev, dflow
+
+
 def vsr_trunk_keep_bytes(cfg, n, h, w):
     """Bytes of the activation stack of vsr_trunk_keep — sr_vsr_trunk_keep_bytes."""
     return _lib.load().sr_vsr_trunk_keep_bytes(C.byref(cfg), n, h, w)

@@ -9,9 +9,28 @@ one folder per ``dataset[idx]`` (strided over the ranks), scores every frame, an
 
 ``network_g.compute_dtype: bf16`` (an extension; the reference is fp32 only) runs BasicVSR / IconVSR on their bf16 forward.
 
-Inference only: building it with ``is_train`` raises NotImplementedError — the networks' backward exists
-(``BasicVSR.set_autograd``, archs/basicvsr_autograd.py, on top of ``SpyNet.set_autograd``); training them from an option file
-(``fix_flow`` / ``flow_lr_mul``, the recurrent REDS dataset) is the follow-up."""
+Training (``is_train``; the reference's video_recurrent_model.py:17-62) runs BasicVSR in fp32 on a HIP device, on
+``BasicVSR.set_autograd(True, deterministic=train.deterministic_backward)``:
+
+``train.flow_lr_mul``  the parameters whose name contains ``spynet`` form a second Adam parameter group at ``lr * flow_lr_mul``
+    (normal parameters first, as in the reference).  1 (the default) is one group.  Both groups step in ONE launch
+    (sr_adam_step_groups_f32), as EDVRModel's.
+``train.fix_flow``     below iteration ``fix_flow`` the parameters whose name contains ``spynet`` or ``edvr`` do not train; from
+    iteration ``fix_flow`` on all of them.  While they are frozen the network computes no flow gradient and SpyNet's backward is
+    not walked.
+``train.deterministic_backward``  (an extension, default true) the step-input adjoint of the recurrent backward sums in 64-bit
+    integers (include/sr_hip_vsr_det.h), so two runs from one seed take bit-identical steps and a resumed run continues the
+    uninterrupted one's trajectory bit for bit; false selects the float-atomic scatter, which is neither.
+
+The loss is taken on the whole output [b, n, 3, 4h, 4w] against ``gt`` of the same shape.  Validation inside training is
+``dist_validation`` below; saving images while training raises, as in the reference.
+
+Deviation, the one of EDVRModel: the reference freezes at ``current_iter == 1`` only, so a run resumed inside the warm-up trains
+everything from there; here the freeze holds for every iteration below ``fix_flow``, resumed or not.
+
+Not trained yet — NotImplementedError at construction, naming what is supported: a model on the CPU (``num_gpu: 0``), IconVSR
+(the backward of its keyframe branch), ``compute_dtype: bf16``; Vimeo-90K recurrent clips have no dataset.  They are the
+follow-up."""
 import os
 import os.path as osp
 from collections import Counter, OrderedDict
@@ -27,9 +46,20 @@ from .video_base_model import VideoBaseModel
 class VideoRecurrentModel(VideoBaseModel):
 
     def __init__(self, opt):
+        self.fix_flow_iter = None
+        self._flow_frozen = False
         if opt['is_train']:
-            raise NotImplementedError('VideoRecurrentModel tests only: training the recurrent video networks from an option file '
-                                      '(fix_flow / flow_lr_mul, the recurrent REDS dataset, on BasicVSR.set_autograd) is the follow-up')
+            supported = 'supported: network_g.type BasicVSR in fp32 (no compute_dtype, or fp32) on a HIP device (num_gpu >= 1)'
+            if opt['num_gpu'] == 0:
+                raise NotImplementedError('VideoRecurrentModel trains on a HIP device only (num_gpu: 0 has no kernels to run); '
+                                          f'{supported}.  IconVSR, bf16 and Vimeo-90K training are the follow-up')
+            if opt['network_g'].get('type') != 'BasicVSR':
+                raise NotImplementedError(f"VideoRecurrentModel cannot train network_g.type {opt['network_g'].get('type')!r}; "
+                                          f'{supported}.  IconVSR training is the follow-up')
+            if opt['network_g'].get('compute_dtype', 'fp32') != 'fp32':
+                raise NotImplementedError(f"VideoRecurrentModel cannot train with compute_dtype {opt['network_g']['compute_dtype']!r}; "
+                                          f'{supported}.  bf16 training is the follow-up')
+            self.fix_flow_iter = opt['train'].get('fix_flow')
         # network_g.compute_dtype of a network that sets its dtype after construction (BasicVSR, IconVSR keep the reference's
         # constructor): taken out of a copy, so build_network sees the reference's keys and the caller's dict stays as it is
         net_opt, compute_dtype = dict(opt['network_g']), None
@@ -39,7 +69,37 @@ class VideoRecurrentModel(VideoBaseModel):
         super().__init__(opt)
         if compute_dtype is not None:
             self.net_g.set_compute_dtype(compute_dtype)
+        if self.is_train:   # the EMA shadow (built in init_training_settings) only ever runs under no_grad: it keeps the switch off
+            self.net_g.set_autograd(True, deterministic=self.opt['train'].get('deterministic_backward', True))
         self.center_frame_only = False
+
+    def setup_optimizers(self):
+        train_opt = self.opt['train']
+        flow_lr_mul = train_opt.get('flow_lr_mul', 1)
+        self.logger.info(f'Multiple the learning rate for flow network with {flow_lr_mul}.')
+        block = dict(train_opt['optim_g'])
+        kind = block.pop('type')
+        if kind != 'Adam':
+            raise NotImplementedError(f'optimizer {kind} is not supperted yet.')
+        if flow_lr_mul == 1:
+            self.optimizer_g = self.gen.attach_adam(block, self.logger)
+        else:   # normal parameters first, then the flow network at its own rate
+            self.optimizer_g = self.gen.attach_adam(block, self.logger, group_of=lambda name: 1 if 'spynet' in name else 0,
+                                                    group_lrs=[block['lr'], block['lr'] * flow_lr_mul])
+
+    def optimize_parameters(self, current_iter):
+        if self.fix_flow_iter:
+            if current_iter < self.fix_flow_iter and not self._flow_frozen:
+                self.logger.info(f'Fix flow network and feature extractor for {self.fix_flow_iter} iters.')
+                for name, param in self.net_g.named_parameters():
+                    if 'spynet' in name or 'edvr' in name:
+                        param.requires_grad_(False)
+                self._flow_frozen = True
+            elif current_iter >= self.fix_flow_iter and self._flow_frozen:
+                self.logger.warning('Train all the parameters.')
+                self.net_g.requires_grad_(True)
+                self._flow_frozen = False
+        super().optimize_parameters(current_iter)
 
     def test(self):
         """One forward over the clip ``self.lq`` [b, n, c, h, w] without autograd."""

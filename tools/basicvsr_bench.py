@@ -3,6 +3,7 @@
 
     python tools/basicvsr_bench.py [--num-block 30] [--reps 20] [--warmup 5] [--other-tree DIR] [--out results.json]
     python tools/basicvsr_bench.py --backward [--num-block 30] [--batch 4] [--reps 5] [--warmup 2] [--out results.json]
+    python tools/basicvsr_bench.py --backward --deterministic [--num-block 30] [--batch 4] [--reps 5] [--warmup 2] [--out results.json]
 
 Cases: one 180x320 clip of 15 frames, and one 64x112 clip of 7 frames (below the Winograd size rule: the trunks run on the direct
 kernels).  Three variants on the same parameters and input, the launch profiler off, each forward timed with device events;
@@ -32,6 +33,11 @@ the 2500.0 TFLOP/s dense bf16 MFMA peak).
 above under PyTorch-ROCm autograd on the same device and parameters, the two alternating round by round; the largest relative L2
 between their parameter gradients; the bytes the training forward keeps per clip; and the per-kernel split of one product step from
 the launch profiler (count, milliseconds, share), with the share of the two step kernels (ids 159 and 178).
+
+--backward --deterministic times the deterministic backward (set_autograd(True, deterministic=True): sr_vsr_prop_input_bwd_det_f32,
+kernels 180-182) against the default one (kernel 178) at the same shape in one process, the two alternating round by round: the
+step time of each as median [min, max], the time of the step-input adjoint's kernels per step from the launch profiler, whether two
+deterministic passes agree bit for bit, and the largest relative L2 between the two modes' parameter gradients.
 """
 import argparse
 import importlib.util
@@ -255,6 +261,74 @@ def backward_bench(args, dev):
             json.dump(dict(backward=True, reps=args.reps, warmup=args.warmup, rows=[r]), f, indent=1)
 
 
+def deterministic_bench(args, dev):
+    """--backward --deterministic: see the module docstring."""
+    import ctypes as C
+    from image_restoration_amd import _lib
+    lib = _lib.load()
+    n, h, w, b, nf, nb = 15, 64, 64, args.batch, 64, args.num_block
+    torch.manual_seed(0)
+    net = BasicVSR(num_feat=nf, num_block=nb).to(dev).train()
+    x = torch.rand(b, n, 3, h, w, device=dev)
+    g = torch.randn(b, n, 3, 4 * h, 4 * w, device=dev)
+    params = list(net.parameters())
+    modes = (('atomic', False), ('deterministic', True))
+
+    def step(deterministic):
+        net.set_autograd(True, deterministic=deterministic)
+        for q in params:
+            q.grad = None
+        (net(x) * g).sum().backward()
+    grads = {}
+    for name, det in modes:
+        step(det)
+        grads[name] = [q.grad.clone() for q in params]
+    step(True)
+    same = all(torch.equal(a, q.grad) for a, q in zip(grads['deterministic'], params))
+    rel = max(float((a - d).norm() / d.norm()) for a, d in zip(grads['atomic'], grads['deterministic']))
+    for _ in range(args.warmup):
+        for _, det in modes:
+            step(det)
+    ms = {name: [] for name, _ in modes}
+    for _ in range(args.reps):                      # rows alternate: a drift of the clock reaches both alike
+        for name, det in modes:
+            ms[name].append(timed(lambda: step(det), 1, 0))
+    kernels = {}
+    cap = 1 << 16
+    for name, det in modes:
+        _lib.check(lib.sr_profile_start(cap), 'sr_profile_start')
+        try:
+            step(det)
+            torch.cuda.synchronize()
+        finally:
+            recs = (_lib.LaunchRecord * cap)()
+            cnt = C.c_int(0)
+            _lib.check(lib.sr_profile_stop(recs, cap, C.byref(cnt)), 'sr_profile_stop')
+        per = {}
+        for i in range(min(cnt.value, cap)):
+            if recs[i].kernel_id in (178, 180, 181, 182):
+                e = per.setdefault(int(recs[i].kernel_id), dict(name=lib.sr_kernel_name(recs[i].kernel_id).decode(), launches=0, ms=0.0))
+                e['launches'] += 1
+                e['ms'] += float(recs[i].ms)
+        kernels[name] = per
+    rows = []
+    for name, _ in modes:
+        v = ms[name]
+        rows.append(dict(mode=name, step_ms=statistics.median(v), step_ms_min=min(v), step_ms_max=max(v), step_input_kernels=kernels[name],
+                         step_input_ms=sum(e['ms'] for e in kernels[name].values())))
+    case = f'{b} clips of {n} frames {h}x{w}, num_feat {nf}, num_block {nb}'
+    print(f'{case}: two deterministic backward passes bit-identical: {same}; max rel L2 atomic vs deterministic gradients {rel:.2e}')
+    for r in rows:
+        print(f'    {r["mode"]:14s} forward + backward {r["step_ms"]:.1f} ms [{r["step_ms_min"]:.1f}, {r["step_ms_max"]:.1f}]; step-input adjoint '
+              f'{r["step_input_ms"]:.3f} ms per step: ' + ', '.join(f'{e["name"]} (id {k}) {e["launches"]} launches {e["ms"]:.3f} ms'
+                                                                    for k, e in sorted(r['step_input_kernels'].items())))
+    print(f'    deterministic / atomic step time {rows[1]["step_ms"] / rows[0]["step_ms"]:.4f}')
+    if args.out:
+        with open(args.out, 'w') as f:
+            json.dump(dict(backward=True, deterministic=True, case=case, reps=args.reps, warmup=args.warmup, bit_identical=same,
+                           max_rel_l2_atomic_vs_deterministic=rel, rows=rows), f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--num-block', type=int, default=30)
@@ -266,12 +340,16 @@ def main():
     ap.add_argument('--backward', action='store_true', help='time forward + backward at the REDS recipe\'s shape instead, against '
                     'PyTorch-ROCm autograd, with the per-kernel split')
     ap.add_argument('--batch', type=int, default=4, help='clips per step of --backward')
+    ap.add_argument('--deterministic', action='store_true', help='with --backward: the deterministic backward (set_autograd(True, '
+                    'deterministic=True)) against the atomic one in one process, rows alternating')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('basicvsr_bench needs a GPU: timings are device timings')
     dev = torch.device('cuda:0')
+    if args.deterministic and not args.backward:
+        raise SystemExit('--deterministic times the backward: give --backward too')
     if args.backward:
-        return backward_bench(args, dev)
+        return deterministic_bench(args, dev) if args.deterministic else backward_bench(args, dev)
     if args.wino_off:
         from image_restoration_amd import _lib
         _lib.load().sr_dev_set_wino_f32(0)
