@@ -616,6 +616,18 @@ VSR_DET_SIGNATURES = {
     'sr_vsr_prop_input_bwd_det_f32': (C.c_int, [C.POINTER(VsrPropBwdDetDesc), _P]),
 }
 
+
+class DcnBwdDetDesc(C.Structure):
+    """struct sr_dcn_bwd_det_desc (include/sr_hip_dcn_det.h)."""
+    _fields_ = [('d', DcnBwdDesc), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_dcn_det.h declares
+DCN_DET_SIGNATURES = {
+    'sr_dcn_bwd_data_det_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
+    'sr_dcn_bwd_data_det_f32': (C.c_int, [C.POINTER(DcnBwdDetDesc), _P]),
+}
+
 _lib = None
 
 
@@ -632,7 +644,8 @@ def load():
             + list(EDSR_SIGNATURES.items()) + list(CA_BF16_SIGNATURES.items()) + list(DCN_SIGNATURES.items()) + list(EDVR_SIGNATURES.items()) \
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
             + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()) + list(VSR_BF16_SIGNATURES.items()) \
-            + list(FLOW_BWD_SIGNATURES.items()) + list(VSR_BWD_SIGNATURES.items()) + list(VSR_DET_SIGNATURES.items()):
+            + list(FLOW_BWD_SIGNATURES.items()) + list(VSR_BWD_SIGNATURES.items()) + list(VSR_DET_SIGNATURES.items()) \
+            + list(DCN_DET_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -166,6 +166,13 @@ def _need_gpu(x):
         raise NotImplementedError
 
 
+def _set_deterministic(module, flag):
+    for m in module.modules():
+        if isinstance(m, DCNv2Pack):
+            m.deterministic = bool(flag)
+    return module
+
+
 class PCDAlignment(nn.Module):
     """EDVR's alignment of one frame's features to the centre frame's: deformable convs on a three-level pyramid, coarse to
     fine, and one more deformable conv on the result (the reference's PCDAlignment, edvr_arch.py:9-98).
@@ -205,6 +212,11 @@ class PCDAlignment(nn.Module):
         self.cas_offset_conv2 = Conv3x3Params(num_feat, num_feat)
         self.cas_dcnpack = DCNv2Pack(num_feat, num_feat, 3, padding=1, deformable_groups=deformable_groups)
         self.num_feat = num_feat
+
+    def set_deterministic(self, flag=True):
+        """This project's own switch: every deformable conv below takes the bit-reproducible input gradient
+        (include/sr_hip_dcn_det.h) in its backward.  Off by default; the forward is the same.  Returns self."""
+        return _set_deterministic(self, flag)
 
     def _layers(self, ops, nbr, ref):
         conv, cat = ops.conv, ops.cat
@@ -491,6 +503,12 @@ class EDVR(nn.Module):
         self.upconv2 = Conv3x3Params(num_feat, 64 * 4)
         self.conv_hr = Conv3x3Params(64, 64)
         self.conv_last = Conv3x3Params(64, 3)
+
+    def set_deterministic(self, flag=True):
+        """This project's own switch: every deformable conv of the network takes the bit-reproducible input gradient
+        (include/sr_hip_dcn_det.h), after which two backward passes of the fp32 network agree bit for bit.  Off by default.  With
+        compute_dtype='bf16' the flag is accepted and does nothing: that path is forward only.  Returns self."""
+        return _set_deterministic(self, flag)
 
     def _align(self, ops, feat_l, b, t):
         ref_l = [ops.center_over_t(f, b, t, self.center_frame_idx) for f in feat_l]

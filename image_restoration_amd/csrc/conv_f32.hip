@@ -1089,5 +1089,9 @@ extern "C" const char* sr_kernel_name(int id) {
     static const char* const dnames[3] = {"vsr_prop_det_scale_kernel", "vsr_prop_det_scatter_kernel", "vsr_prop_det_finish_kernel"};
     return dnames[id - 180];
   }
+  if (id >= 184 && id <= 186) {  // dcn_det_ops.hip (include/sr_hip_dcn_det.h); 183 stays unnamed
+    static const char* const cnames[3] = {"deform_det_scale_kernel", "deform_det_scatter_kernel", "deform_det_finish_kernel"};
+    return cnames[id - 184];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

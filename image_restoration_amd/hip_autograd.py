@@ -115,7 +115,7 @@ class ConvFn(torch.autograd.Function):
 class DCNFn(torch.autograd.Function):
     """Modulated deformable 3x3/s1/p1 convolution (+bias, +LeakyReLU(act_slope)) on CB8 (include/sr_hip_dcn.h).
 
-    forward(x, offset, mask_or_logits, weight, bias, act_slope, deformable_groups, mask_is_logit[, windows]): ``offset`` /
+    forward(x, offset, mask_or_logits, weight, bias, act_slope, deformable_groups, mask_is_logit[, windows[, deterministic]]): ``offset`` /
     ``mask`` are CB8 tensors of 18 * dg / 9 * dg channels (pad channels ignored).  With ``windows`` = ((first block, blocks) of
     the offsets, (first block, blocks) of the mask) both arguments are the SAME tensor (DCNv2Pack: the conv_offset output, whose
     two thirds are block-aligned when dg % 4 == 0); its gradient is then one tensor the kernel writes both windows of, returned
@@ -124,12 +124,15 @@ class DCNFn(torch.autograd.Function):
     backward : LeakyReLU mask against the saved output; columns (sr_dcn_cols_f32) -> sr_convd_wgrad_f32 ksize 1 ->
                sr_dcn_weight_unpack_f32 for dweight / dbias; dcol = Wt dz (sr_convd_f32 ksize 1 on sr_dcn_pack_t_f32's image);
                sr_dcn_bwd_data_f32 for doffset / dmask (bit-reproducible) and dx (atomicAdd: last bits depend on arrival order).
+               With ``deterministic`` (behind ``windows``, which may be None) sr_dcn_bwd_data_det_f32 instead: the same doffset /
+               dmask, and a dx summed in 64-bit integers (include/sr_hip_dcn_det.h), so that two backward passes agree bit for bit.
     """
 
     @staticmethod
     def forward(ctx, x, offset, mask, weight, bias, act_slope, deformable_groups, mask_is_logit, *extra):
         dg = deformable_groups
         windows = extra[0] if extra else None
+        ctx.deterministic = bool(extra[1]) if len(extra) > 1 else False
         ctx.nextra = len(extra)
         src = _cb8(x)
         ctx.windows = windows   # ((off cb0, off cbn), (mask cb0, mask cbn)) when offset and mask are one tensor
@@ -176,7 +179,8 @@ class DCNFn(torch.autograd.Function):
                 else:                          # pad channels are not written by the kernel
                     doff, dmsk = torch.zeros_like(offset), torch.zeros_like(mask)
                     do_w, dm_w = _cb8(doff), _cb8(dmsk)
-            dxw = H.dcn_bwd_data(dcol, src, off_w, mask_w, ctx.dg, mask_is_logit=ctx.logit, want_dx=need_x, doffset=do_w, dmask=dm_w)
+            bwd_data = H.dcn_bwd_data_det if ctx.deterministic else H.dcn_bwd_data
+            dxw = bwd_data(dcol, src, off_w, mask_w, ctx.dg, mask_is_logit=ctx.logit, want_dx=need_x, doffset=do_w, dmask=dm_w)
             dx = dxw.buf if dxw is not None else None
         return (dx, doff if need_o else None, dmsk if need_m else None, dw if need_w else None, db if need_b else None,
                 None, None, None) + (None,) * ctx.nextra

@@ -978,6 +978,43 @@ def dcn_bwd_data(dcol, x, offset, mask, dg, *, mask_is_logit=False, want_dx=True
     return dx
 
 
+def dcn_bwd_data_det_workspace_bytes(n, cin, h, w):
+    """Bytes of the workspace of dcn_bwd_data_det — sr_dcn_bwd_data_det_workspace_bytes."""
+    return _lib.load().sr_dcn_bwd_data_det_workspace_bytes(n, cin, h, w)
+
+
+def dcn_bwd_data_det(dcol, x, offset, mask, dg, *, mask_is_logit=False, want_dx=True, dx=None, doffset=None, dmask=None, workspace=None):
+    """dcn_bwd_data with a bit-reproducible ``dx`` (include/sr_hip_dcn_det.h) — one sr_dcn_bwd_data_det_f32 call: the terms are
+    summed as 64-bit integers in ``workspace`` (uint8, dcn_bwd_data_det_workspace_bytes; the grow-only scratch when None) and
+    STORED into ``dx`` with one rounding (a new CB8 tensor, or the CB8 window ``dx`` when given, which need not be zeroed;
+    returned, or None); ``doffset`` / ``dmask`` are dcn_bwd_data's bit for bit."""
+    who = 'dcn_bwd_data_det'
+    _arg(isinstance(dcol, CB8) and isinstance(x, CB8) and dcol.channels == 9 * x.channels and dcol.cb0 == 0
+         and dcol.cbn == dcol.buf.size(1), f'{who}: dcol must be a whole CB8 tensor of 9 * cin channels')
+    _arg((doffset is None) == (dmask is None), f'{who}: doffset and dmask go together')
+    if dx is None and want_dx:
+        dx = CB8.empty(x.n, x.channels, x.h, x.w, x.device)
+    _arg(dx is None or (isinstance(dx, CB8) and (dx.n, dx.cbn, dx.h, dx.w) == (x.n, x.cbn, x.h, x.w)), f'{who}: dx does not fit')
+    dd = _lib.DcnBwdDetDesc()
+    d = dd.d
+    _dcn_desc(d.fwd, x, offset, mask, dg, mask_is_logit, 1)
+    d.dcol = dcol.ptr
+    if dx is not None:
+        d.dx, d.dx_img_stride = dx.ptr, dx.img_stride
+        nbytes = dcn_bwd_data_det_workspace_bytes(x.n, x.channels, x.h, x.w)
+        _arg(nbytes > 0, f'{who}: bad shape n={x.n} cin={x.channels} h={x.h} w={x.w}')
+        if workspace is None:
+            workspace = scratch(x.device, nbytes, who)
+        _arg(workspace.dtype == torch.uint8 and workspace.numel() >= nbytes and workspace.device == x.device,
+             f'{who}: the workspace is too small')
+        dd.workspace, dd.workspace_bytes = workspace.data_ptr(), nbytes
+    if doffset is not None:
+        _arg(doffset.channels >= 18 * dg and dmask.channels >= 9 * dg, f'{who}: doffset / dmask do not fit')
+        d.doffset, d.doffset_img_stride, d.dmask, d.dmask_img_stride = doffset.ptr, doffset.img_stride, dmask.ptr, dmask.img_stride
+    _launch_arg('sr_dcn_bwd_data_det_f32', x.device, C.byref(dd))
+    return dx
+
+
 # ---- EDVR: stride-2 conv and its zero insertion, TSA's pooling, correlation and gate (include/sr_hip_edvr.h) ----
 
 def _arg(cond, msg):

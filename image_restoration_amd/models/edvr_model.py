@@ -7,7 +7,13 @@
     and their bias-correction count starts at ``tsa_iter``; ``optim.FlatAdam`` does the same from ``requires_grad`` (its
     docstring has the equivalence and its limit).
 
-Both go through ONE launch per step (sr_adam_step_groups_f32).  With neither option set the optimiser is the plain single-group
+``train.deterministic_backward``  (an extension, default false) ``EDVR.set_deterministic(True)``: the input gradient of every
+    deformable convolution sums in 64-bit integers (include/sr_hip_dcn_det.h) instead of float atomics, so two runs from one seed
+    take bit-identical steps and a resumed run continues the uninterrupted one's trajectory bit for bit.  Off by default
+    only because the float-atomic scatter is what this model has always run; DESIGN.md §39 has the measurements (the deterministic
+    step is the faster one) and the argument for flipping the default later.
+
+``dcn_lr_mul`` and ``tsa_iter`` go through ONE launch per step (sr_adam_step_groups_f32).  With neither option set the optimiser is the plain single-group
 FlatAdam on sr_adam_step_f32, like every other model.
 
 Deviations.  The reference freezes at ``current_iter == 1`` only, so a run resumed inside the warm-up trains everything from
@@ -30,6 +36,8 @@ class EDVRModel(VideoBaseModel):
                                  'there is no TSA module to train')
         self._tsa_frozen = False
         super().__init__(opt)
+        if opt['is_train'] and opt['train'].get('deterministic_backward', False):
+            self.get_bare_model(self.net_g).set_deterministic(True)
 
     def setup_optimizers(self):
         train_opt = self.opt['train']

@@ -31,9 +31,12 @@ def check_config(cin, ksize, stride, padding, dilation, groups, deformable_group
                          f'supported; supported: {SUPPORTED}')
 
 
-def modulated_deform_conv(input, offset, mask, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, deformable_groups=1):
+def modulated_deform_conv(input, offset, mask, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, deformable_groups=1, *,
+                          deterministic=False):
     """The reference's ``modulated_deform_conv`` (ModulatedDeformConvFunction.apply, deform_conv.py:121-189): NCHW in, NCHW out.
-    ``offset`` [N, 18 * dg, H, W] with (h, w) interleaved per tap inside each group's 18 channels, ``mask`` [N, 9 * dg, H, W]."""
+    ``offset`` [N, 18 * dg, H, W] with (h, w) interleaved per tap inside each group's 18 channels, ``mask`` [N, 9 * dg, H, W].
+    ``deterministic`` is this project's own key: the input gradient is then summed in 64-bit integers
+    (include/sr_hip_dcn_det.h) and two backward passes agree bit for bit; the forward and the other gradients are the same."""
     for t in (input, offset, mask, weight):
         if t.dtype != torch.float32:
             check_config(input.size(1), weight.shape[2:], stride, padding, dilation, groups, deformable_groups, t.dtype)
@@ -45,13 +48,17 @@ def modulated_deform_conv(input, offset, mask, weight, bias=None, stride=1, padd
                          f'{tuple(weight.shape)} do not fit input {tuple(input.shape)} with deformable_groups {dg}')
     if not input.is_cuda:
         raise NotImplementedError
-    y = A.DCNFn.apply(A.ToCB8.apply(input), A.ToCB8.apply(offset), A.ToCB8.apply(mask), weight, bias, 1.0, dg, False)
+    extra = (None, True) if deterministic else ()
+    y = A.DCNFn.apply(A.ToCB8.apply(input), A.ToCB8.apply(offset), A.ToCB8.apply(mask), weight, bias, 1.0, dg, False, *extra)
     return A.FromCB8.apply(y, weight.size(0))
 
 
 class ModulatedDeformConv(nn.Module):
     """Parameters and forward of the reference's ModulatedDeformConv (deform_conv.py:293-337): weight U(+-1/sqrt(cin * 9)),
-    bias zero."""
+    bias zero.  ``deterministic`` (an attribute, not a constructor argument: the signature is the reference's) selects the
+    bit-reproducible input gradient of ``modulated_deform_conv``."""
+
+    deterministic = False
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, deformable_groups=1,
                  bias=True):
@@ -87,7 +94,7 @@ class ModulatedDeformConv(nn.Module):
 
     def forward(self, x, offset, mask):
         return modulated_deform_conv(x, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups,
-                                     self.deformable_groups)
+                                     self.deformable_groups, deterministic=self.deterministic)
 
 
 class ModulatedDeformConvPack(ModulatedDeformConv):
@@ -119,12 +126,13 @@ class ModulatedDeformConvPack(ModulatedDeformConv):
         LeakyReLU(act_slope) in the epilogue.  When dg % 4 == 0 the two parts are channel-block windows of ``co`` and are read
         in place with the sigmoid in the sampler; otherwise they are split by a copy first."""
         dg = self.deformable_groups
+        det = self.deterministic   # DCNFn's trailing flag goes behind ``windows``, and only when set
         if dg % 4 == 0:
             windows = ((0, 18 * dg // 8), (18 * dg // 8, (9 * dg + 7) // 8))
-            return A.DCNFn.apply(x, co, co, self.weight, self.bias, act_slope, dg, True, windows)
+            return A.DCNFn.apply(x, co, co, self.weight, self.bias, act_slope, dg, True, windows, *((True,) if det else ()))
         nchw = A.FromCB8.apply(co, 27 * dg)
         offset, logit = A.ToCB8.apply(nchw[:, :18 * dg]), A.ToCB8.apply(nchw[:, 18 * dg:])
-        return A.DCNFn.apply(x, offset, logit, self.weight, self.bias, act_slope, dg, True)
+        return A.DCNFn.apply(x, offset, logit, self.weight, self.bias, act_slope, dg, True, *((None, True) if det else ()))
 
     def offset_absmean(self, co):
         """mean |offset| over the real offset channels of ``co`` (one device reduction and a host sync)."""

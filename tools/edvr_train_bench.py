@@ -10,7 +10,11 @@
   ``dcn_lr_mul`` / ``tsa_iter``, split into forward, loss + backward, optimiser and EMA by HIP events around the phases of
   SRModel.optimize_parameters, median of ``--steps``; and the launch profiler's count of launches and sum of kernel time for one step.
 
-    python tools/edvr_train_bench.py [--calls 30 --warmup 5 --steps 7]
+* ``--deterministic``: only the ``step`` row, with and without ``train.deterministic_backward``, two models
+  alternating in one process over ``--steps`` rounds, median [min, max]; and the kernels of the deformable convolutions' data
+  gradient from one profiled step of each.
+
+    python tools/edvr_train_bench.py [--calls 30 --warmup 5 --steps 7] [--deterministic]
 """
 import argparse
 import ctypes as C
@@ -153,13 +157,66 @@ def bench_step(steps, dev, **train_kw):
     return out
 
 
+def bench_deterministic(rounds, dev):
+    """The ``step`` row with and without ``train.deterministic_backward``: two models of one seed in one process, one step of each
+    per round, alternating, so both see the same clocks; median [min, max] over the rounds after two warm-up rounds.  Then one
+    profiled step of each: launches and kernel time of the deformable convolutions' data gradient (ids 112; 184, 185, 186)."""
+    import logging
+    logging.getLogger('basicsr').setLevel(logging.ERROR)
+    lq, gt = torch.rand(4, 5, 3, 64, 64, device=dev), torch.rand(4, 3, 256, 256, device=dev)
+    models, phases = OD(), OD()
+    for key, flag in (('atomic', False), ('deterministic', True)):
+        torch.manual_seed(0)
+        models[key] = build_model(model_opt(deterministic_backward=flag))
+        models[key].feed_data(dict(lq=lq, gt=gt))
+        phases[key] = OD(forward=[], backward=[], total=[])
+
+    def step(model):
+        def fwd():
+            model.gen.clear_grads()
+            model.output = model.net_g(model.lq)
+
+        def bwd():
+            book = LossBook()
+            model.content_terms(book)
+            book.objective.backward()
+        t = [event_ms(fwd), event_ms(bwd), event_ms(lambda: model.gen.update(False)), event_ms(lambda: model.gen.blend_shadow(model.ema_decay))]
+        return t[0], t[1], sum(t)
+    for r in range(rounds + 2):
+        for key, model in models.items():
+            model.update_learning_rate(r + 1)
+            t = step(model)
+            if r >= 2:
+                for k, v in zip(phases[key], t):
+                    phases[key][k].append(v)
+    lib = _lib.load()
+    out = OD()
+    for key, model in models.items():
+        row = OD((k, OD(median_ms=round(statistics.median(v), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))) for k, v in phases[key].items())
+        recs = profile(lambda: model.optimize_parameters(rounds + 3))
+        row['profiled_launches'] = len(recs)
+        row['profiled_kernel_ms'] = round(sum(r.ms for r in recs), 3)
+        row['dcn_data_gradient'] = OD((f'{i} {lib.sr_kernel_name(i).decode()}', OD(launches=sum(r.kernel_id == i for r in recs),
+                                                                                   ms=round(sum(r.ms for r in recs if r.kernel_id == i), 4)))
+                                      for i in (112, 184, 185, 186))
+        out[key] = row
+    out['rounds'] = rounds
+    out['total_ratio_of_medians'] = round(out['deterministic']['total']['median_ms'] / out['atomic']['total']['median_ms'], 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--calls', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--steps', type=int, default=7)
+    ap.add_argument('--deterministic', action='store_true',
+                    help='only the step row, with and without train.deterministic_backward, alternating in one process (--steps rounds)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
+    if args.deterministic:
+        print(json.dumps(OD(step_deterministic=bench_deterministic(args.steps, dev))))
+        return
     out = OD(adam=bench_adam(args.calls, args.warmup, dev))
     out['step_plain'] = bench_step(args.steps, dev)
     out['step_dcn_lr_mul'] = bench_step(args.steps, dev, dcn_lr_mul=0.25)
