@@ -628,6 +628,24 @@ DCN_DET_SIGNATURES = {
     'sr_dcn_bwd_data_det_f32': (C.c_int, [C.POINTER(DcnBwdDetDesc), _P]),
 }
 
+
+class TofConv9x9Desc(C.Structure):
+    """struct sr_tof_conv9x9_desc (include/sr_hip_tof.h)."""
+    _fields_ = [('in_', C.c_void_p), ('in_img_stride', C.c_longlong), ('cin', C.c_int), ('cout', C.c_int), ('n', C.c_int),
+                ('h', C.c_int), ('w', C.c_int), ('packed', C.c_void_p), ('out', C.c_void_p), ('out_img_stride', C.c_longlong),
+                ('relu', C.c_int)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_tof.h declares
+TOF_SIGNATURES = {
+    'sr_tof_conv9x9_packed_floats': (C.c_size_t, [_I, _I]),
+    'sr_tof_conv9x9_pack_f32': (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    'sr_tof_conv9x9_f32': (C.c_int, [C.POINTER(TofConv9x9Desc), _P]),
+    'sr_tof_level_input_f32': (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
+    'sr_tof_align_f32': (C.c_int, [_P, _P, C.c_longlong, _P, C.c_longlong, _I, _I, _I, _I, _P]),
+    'sr_tof_finish_f32': (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
+}
+
 _lib = None
 
 
@@ -645,7 +663,7 @@ def load():
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
             + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()) + list(VSR_BF16_SIGNATURES.items()) \
             + list(FLOW_BWD_SIGNATURES.items()) + list(VSR_BWD_SIGNATURES.items()) + list(VSR_DET_SIGNATURES.items()) \
-            + list(DCN_DET_SIGNATURES.items()):
+            + list(DCN_DET_SIGNATURES.items()) + list(TOF_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

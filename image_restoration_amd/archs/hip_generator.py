@@ -58,7 +58,7 @@ class HipGenerator(nn.Module):
         if w.dtype != torch.float32 or b.dtype != torch.float32:
             raise _lib.SrHipError(f'{type(self).__name__} parameters must be fp32')
         cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv if w.shape[2] == 3 else \
-            hip_ops.PackedConv7x7 if w.shape[2] == 7 else hip_ops.PackedConvK
+            hip_ops.PackedConv7x7 if w.shape[2] == 7 else hip_ops.PackedConv9x9 if w.shape[2] == 9 else hip_ops.PackedConvK
         pc = cls(w, b if mode == 0 else None, mode=mode)
         self._packs[key] = (sig, pc)
         return pc

@@ -1093,5 +1093,10 @@ extern "C" const char* sr_kernel_name(int id) {
     static const char* const cnames[3] = {"deform_det_scale_kernel", "deform_det_scatter_kernel", "deform_det_finish_kernel"};
     return cnames[id - 184];
   }
+  if (id >= 188 && id <= 192) {  // tof_ops.hip (include/sr_hip_tof.h); 187 stays unnamed
+    static const char* const tnames[5] = {"tof_conv9x9_f32_kernel", "tof_conv9x9_pack_kernel", "tof_level_input_kernel", "tof_align_kernel",
+                                          "tof_finish_kernel"};
+    return tnames[id - 188];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

@@ -6,7 +6,11 @@ The motion is free of sub-pixel parts on both grids, so every LQ frame is exactl
 ``recurrent: true`` gives REDSRecurrentDataset's sample dict instead — ``gt`` [t, c, H, W], the ground truth of every frame — for
 the networks that return the whole clip (BasicVSR), and accepts any ``num_frame`` >= 2.  Such a set also serves as a validation set of
 VideoRecurrentModel: every clip is a folder of its own (``folder`` in the item, ``data_info['folder']`` one entry per frame).  The
-default (false) keeps the items above."""
+default (false) keeps the items above.
+
+``video_test: true`` (not recurrent) adds what VideoBaseModel's validation reads from a VideoTestDataset item — ``folder``, ``idx``
+and ``lq_path`` — and ``data_info['folder']``, every clip a folder of one centre frame; with ``scale: 1`` the LQ frames are the GT
+frames, the input of a network that restores pre-upsampled frames (TOFlow)."""
 import numpy as np
 import torch
 from torch.utils import data
@@ -32,8 +36,11 @@ class SyntheticClipDataset(data.Dataset):
                 raise ValueError(f'a recurrent clip needs num_frame >= 2, but got {self.num_frame}')
         elif self.num_frame % 2 != 1:
             raise ValueError(f'num_frame should be odd number, but got {self.num_frame}')
+        self.video_test = bool(opt.get('video_test', False)) and not self.recurrent
         if self.recurrent:
             self.data_info = {'folder': [f'{i:08d}' for i in range(self.length) for _ in range(self.num_frame)]}
+        elif self.video_test:
+            self.data_info = {'folder': [f'{i:08d}' for i in range(self.length)]}
         if self.gt_size % self.scale:
             raise ValueError(f'gt_size={self.gt_size} must be a multiple of scale={self.scale}')
 
@@ -52,5 +59,8 @@ class SyntheticClipDataset(data.Dataset):
         if self.recurrent:
             return {'lq': torch.from_numpy(np.ascontiguousarray(lq)), 'gt': torch.from_numpy(np.ascontiguousarray(frames)),
                     'key': f'synthetic/{index:08d}', 'folder': f'{index:08d}'}
-        return {'lq': torch.from_numpy(np.ascontiguousarray(lq)), 'gt': torch.from_numpy(np.ascontiguousarray(frames[t // 2])),
+        item = {'lq': torch.from_numpy(np.ascontiguousarray(lq)), 'gt': torch.from_numpy(np.ascontiguousarray(frames[t // 2])),
                 'key': f'synthetic/{index:08d}'}
+        if self.video_test:
+            item.update(folder=f'{index:08d}', idx='0/1', lq_path=f'synthetic/{index:08d}/{t // 2:08d}.png')
+        return item

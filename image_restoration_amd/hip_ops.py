@@ -1981,3 +1981,104 @@ def vsr_trunk_bwd(cfg, dblob, src, out, stack, dout, din, targets, accumulate=Fa
     d.accumulate, d.n, d.h, d.w, d.workspace, d.workspace_bytes = int(accumulate), n, h, w, ws.data_ptr(), nws
     _launch_arg('sr_vsr_trunk_bwd_f32', dev, C.byref(cfg), C.byref(d))
     return din
+
+
+# ---- TOFlow: the 9x9 conv, SPyNetTOF's level input, the aligned stack and the finish (include/sr_hip_tof.h) ----
+
+CONV9X9_SHAPES = ((21, 64), (64, 64))   # (cin, cout) of TOFlow's conv_1 and conv_2
+
+
+class PackedConv9x9:
+    """MFMA operand image of one 9x9 conv of TOFlow (weights in operand order, then the bias) — sr_tof_conv9x9_pack_f32.
+    ``mode`` exists for HipGenerator.packed: only 0 (forward) is served."""
+
+    def __init__(self, weight, bias=None, mode=0):
+        _need_cuda(weight, 'PackedConv9x9')
+        _arg(mode == 0, f'PackedConv9x9: mode {mode} is not supported; supported: 0 (forward)')
+        _arg(weight.dim() == 4 and tuple(weight.shape[2:]) == (9, 9) and weight.dtype == torch.float32,
+             f'PackedConv9x9: needs an fp32 [cout, cin, 9, 9] weight, got {weight.dtype} {tuple(weight.shape)}')
+        _arg(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (weight.size(0),)), 'PackedConv9x9: bias does not fit')
+        weight = weight.detach().contiguous()
+        bias = None if bias is None else bias.detach().contiguous()
+        self.mode = 0
+        self.cout, self.cin = weight.shape[:2]
+        nfloats = _lib.load().sr_tof_conv9x9_packed_floats(self.cout, self.cin)
+        _arg(nfloats > 0, f'conv9x9: (cin, cout) = ({self.cin}, {self.cout}) is not supported; supported: {CONV9X9_SHAPES}')
+        self.w = torch.empty(nfloats, dtype=torch.float32, device=weight.device)
+        _launch_arg('sr_tof_conv9x9_pack_f32', weight.device, weight.data_ptr(), _p(bias), self.cout, self.cin, self.w.data_ptr())
+
+
+def conv9x9(src, pc, out=None, *, relu=False):
+    """out = [relu](conv9x9(src) + bias) on CB8, stride 1, pad 4 — one sr_tof_conv9x9_f32 launch.  ``pc``: PackedConv9x9; the
+    21-channel source is a 3-block window whose channels 21-23 are ignored."""
+    _arg(src.cbn == (pc.cin + 7) // 8, f'conv9x9: source has {src.cbn} channel blocks, the weight image needs {(pc.cin + 7) // 8}')
+    if out is None:
+        out = CB8.empty(src.n, pc.cout, src.h, src.w, src.device)
+    _arg((out.n, out.h, out.w) == (src.n, src.h, src.w) and out.cbn >= pc.cout // 8, 'conv9x9: output window does not fit')
+    d = _lib.TofConv9x9Desc()
+    d.in_, d.in_img_stride, d.cin, d.cout, d.n, d.h, d.w = src.ptr, src.img_stride, pc.cin, pc.cout, src.n, src.h, src.w
+    d.packed, d.out, d.out_img_stride, d.relu = pc.w.data_ptr(), out.ptr, out.img_stride, int(bool(relu))
+    _launch_arg('sr_tof_conv9x9_f32', src.device, C.byref(d))
+    return out
+
+
+def _frames(t, what, lead):
+    _need_cuda(t, what)
+    _arg(t.dim() == len(lead) + 3 and t.is_contiguous() and t.dtype == torch.float32 and t.numel() > 0
+         and all(want is None or got == want for got, want in zip(t.shape, lead + (3,))),
+         f'{what}: needs a non-empty contiguous fp32 [{", ".join("B" if v is None else str(v) for v in lead)}, 3, H, W] tensor, got '
+         f'{t.dtype} {tuple(t.shape)}')
+    return t.shape
+
+
+def tof_level_input(ref, supp, flow_prev=None, *, clip=None, ref_idx=None):
+    """(the level's CB8 input block [ref, warp(supp, up, zeros), up], up as a CB8 block) of SPyNetTOF — one
+    sr_tof_level_input_f32 launch.  Either ``ref`` and ``supp`` [N, 3, H, W], or ``clip`` [B, 7, 3, H, W] with ``ref_idx``: the
+    N = 6 B pairs (frame ref_idx, every other frame in order) of the clips, image n = 6 b + k, read in place.  ``flow_prev``: the
+    coarser level's flow (a one-block CB8 window at H / 2 x W / 2), None at the coarsest level."""
+    if clip is not None:
+        b, _, _, h, w = _frames(clip, 'tof_level_input', (None, 7))
+        _arg(ref is None and supp is None and ref_idx in range(7), 'tof_level_input: a clip comes with ref_idx in 0..6 and no ref / supp')
+        n, group, skip, stride = 6 * b, 6, ref_idx, 21 * h * w
+        ref_ptr, supp_ptr, dev = clip.data_ptr() + ref_idx * 3 * h * w * 4, clip.data_ptr(), clip.device
+    else:
+        n, _, h, w = _frames(ref, 'tof_level_input', (None,))
+        _arg(supp.shape == ref.shape and supp.is_contiguous() and supp.dtype == torch.float32 and supp.device == ref.device,
+             'tof_level_input: supp does not fit ref')
+        group, skip, stride, ref_ptr, supp_ptr, dev = 1, 1, 3 * h * w, ref.data_ptr(), supp.data_ptr(), ref.device
+    _arg(flow_prev is None or (h % 2 == 0 and w % 2 == 0 and flow_prev.cb0 == 0 and tuple(flow_prev.buf.shape) == (n, 1, h // 2, w // 2, 8)),
+         f'tof_level_input: flow_prev must be one CB8 block at {h // 2}x{w // 2}')
+    out, up = CB8.empty(n, 8, h, w, dev), CB8.empty(n, 8, h, w, dev)
+    _launch_arg('sr_tof_level_input_f32', dev, ref_ptr, stride, supp_ptr, stride, group, skip, None if flow_prev is None else flow_prev.ptr,
+                out.ptr, up.ptr, n, h, w)
+    return out, up
+
+
+def tof_align(clip, flows, ref_idx, out=None):
+    """The 21-channel aligned stack of TOFlow as a 3-block CB8 tensor: frame i of ``clip`` [B, 7, 3, H, W] warped (zeros padding) by
+    its flow, frame ``ref_idx`` copied, channels 21-23 zero — one sr_tof_align_f32 launch.  ``flows``: the one-block CB8 buffer
+    [6 B, 1, H, W, 8] of the six flows of each clip, image 6 b + k."""
+    b, _, _, h, w = _frames(clip, 'tof_align', (None, 7))
+    _arg(ref_idx in range(7), f'tof_align: ref_idx {ref_idx} is not one of the 7 frames')
+    _arg(isinstance(flows, CB8) and flows.cb0 == 0 and tuple(flows.buf.shape) == (6 * b, 1, h, w, 8) and flows.device == clip.device,
+         f'tof_align: flows must be one CB8 block per pair, [{6 * b}, 1, {h}, {w}, 8]')
+    if out is None:
+        out = CB8.empty(b, 24, h, w, clip.device)
+    _arg((out.n, out.cbn, out.h, out.w) == (b, 3, h, w), 'tof_align: output window does not fit')
+    _launch_arg('sr_tof_align_f32', clip.device, clip.data_ptr(), flows.ptr, flows.img_stride, out.ptr, out.img_stride, b, ref_idx, h, w)
+    return out
+
+
+def tof_finish(y, clip, ref_idx, mean, std, out=None):
+    """(y + clip[:, ref_idx]) * std[c] + mean[c] as an NCHW tensor [B, 3, H, W]: ``y`` the one-block CB8 output of conv_4, ``clip``
+    the normalised [B, 7, 3, H, W] frames — one sr_tof_finish_f32 launch."""
+    b, t, _, h, w = _frames(clip, 'tof_finish', (None, None))
+    _arg(0 <= ref_idx < t, f'tof_finish: ref_idx {ref_idx} is not one of the {t} frames')
+    _arg(isinstance(y, CB8) and (y.n, y.h, y.w) == (b, h, w) and y.cbn >= 1 and y.device == clip.device, 'tof_finish: y does not fit the clip')
+    f3 = [(C.c_float * 3)(*[float(v) for v in vals]) for vals in (mean, std)]
+    if out is None:
+        out = torch.empty((b, 3, h, w), dtype=torch.float32, device=clip.device)
+    _arg(tuple(out.shape) == (b, 3, h, w) and out.is_contiguous() and out.dtype == torch.float32, 'tof_finish: output does not fit')
+    _launch_arg('sr_tof_finish_f32', clip.device, y.ptr, y.img_stride, clip.data_ptr() + ref_idx * 3 * h * w * 4, t * 3 * h * w,
+                out.data_ptr(), b, h, w, f3[0], f3[1])
+    return out

@@ -361,3 +361,62 @@ def edsr_state_dict(seed=0, **cfg):
         w, b = conv_params(rng, ws, rdb_style=False)
         sd[wn], sd[bn] = w, b
     return sd
+
+
+def tof_param_shapes():
+    """(name, shape) in state_dict order of TOFlow (tof_arch.py:111-126): 114 entries, the ``mean`` / ``std`` buffers and every
+    BatchNorm ``num_batches_tracked`` (shape ()) included."""
+    out = [('mean', (1, 3, 1, 1)), ('std', (1, 3, 1, 1))]
+    for level in range(4):
+        for i, (cin, cout) in enumerate(((8, 32), (32, 64), (64, 32), (32, 16), (16, 2))):
+            base = f'spynet.basic_module.{level}.basic_module'
+            out.append((f'{base}.{3 * i}.weight', (cout, cin, 7, 7)))
+            if i == 4:
+                out.append((f'{base}.{3 * i}.bias', (cout,)))
+                continue
+            for p in ('weight', 'bias', 'running_mean', 'running_var'):
+                out.append((f'{base}.{3 * i + 1}.{p}', (cout,)))
+            out.append((f'{base}.{3 * i + 1}.num_batches_tracked', ()))
+    for name, cin, cout, k in (('conv_1', 21, 64, 9), ('conv_2', 64, 64, 9), ('conv_3', 64, 64, 1), ('conv_4', 64, 3, 1)):
+        out.append((f'{name}.weight', (cout, cin, k, k)))
+        out.append((f'{name}.bias', (cout,)))
+    return out
+
+
+def tof_state_dict(seed=0, flow_gain=4.0, flow_bias=0.2, recon_gain=2.0):
+    """OrderedDict name -> numpy array for TOFlow, drawn in state_dict order from one seeded generator.  Convs ~ U(+-1/sqrt(fan_in))
+    (nn.Conv2d's default range) with these departures, without which the flows stay far below a pixel, BatchNorm is the identity
+    and the 9x9 path barely moves the output: BatchNorm gamma ~ U(0.5, 1.5), beta and running_mean ~ U(-0.3, 0.3), running_var ~
+    U(0.5, 2) and num_batches_tracked = 100; the last conv of every level has its weight scaled by ``flow_gain`` and its bias ~
+    U(+-flow_bias); the four reconstruction convs are scaled by ``recon_gain``."""
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    for name, shape in tof_param_shapes():
+        leaf = name.rsplit('.', 1)[-1]
+        if name == 'mean':
+            v = np.array([0.485, 0.456, 0.406]).reshape(shape)
+        elif name == 'std':
+            v = np.array([0.229, 0.224, 0.225]).reshape(shape)
+        elif leaf == 'num_batches_tracked':
+            sd[name] = np.array(100, np.int64)
+            continue
+        elif len(shape) == 4:
+            bound = 1.0 / math.sqrt(shape[1] * shape[2] * shape[3])
+            v = rng.uniform(-bound, bound, shape)
+            if name.startswith('conv_'):
+                v = v * recon_gain
+            elif shape[0] == 2:
+                v = v * flow_gain
+            fan_bound = bound
+        elif leaf == 'running_var':
+            v = rng.uniform(0.5, 2.0, shape)
+        elif leaf == 'running_mean':
+            v = rng.uniform(-0.3, 0.3, shape)
+        elif '.basic_module.' in name and shape[0] != 2:       # BatchNorm gamma / beta
+            v = rng.uniform(0.5, 1.5, shape) if leaf == 'weight' else rng.uniform(-0.3, 0.3, shape)
+        elif shape[0] == 2:                                     # bias of a level's last conv
+            v = rng.uniform(-flow_bias, flow_bias, shape)
+        else:                                                   # bias of a reconstruction conv
+            v = rng.uniform(-fan_bound, fan_bound, shape)
+        sd[name] = np.asarray(v, np.float32)
+    return sd
