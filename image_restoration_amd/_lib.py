@@ -646,6 +646,26 @@ TOF_SIGNATURES = {
     'sr_tof_finish_f32': (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),
 }
 
+
+class DufConvDesc(C.Structure):
+    """struct sr_duf_conv_desc (include/sr_hip_duf.h)."""
+    _fields_ = [('in_', C.c_void_p), ('in_frame_stride', C.c_longlong), ('in_clip_stride', C.c_longlong), ('cin', C.c_int),
+                ('cout', C.c_int), ('kt', C.c_int), ('pad_t', C.c_int), ('b', C.c_int), ('t', C.c_int), ('h', C.c_int), ('w', C.c_int),
+                ('packed', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p), ('out', C.c_void_p),
+                ('out_frame_stride', C.c_longlong), ('out_clip_stride', C.c_longlong), ('out_cb0', C.c_int), ('relu', C.c_int)]
+
+
+# name -> (restype, argtypes); every symbol include/sr_hip_duf.h declares
+DUF_SIGNATURES = {
+    'sr_duf_conv3d_packed_floats': (C.c_size_t, [_I, _I, _I]),
+    'sr_duf_conv3d_pack_f32': (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
+    'sr_duf_conv3d_f32': (C.c_int, [C.POINTER(DufConvDesc), _P]),
+    'sr_duf_pw_packed_floats': (C.c_size_t, [_I]),
+    'sr_duf_pw_pack_f32': (C.c_int, [_P, _P, _I, _P, _P]),
+    'sr_duf_pw_f32': (C.c_int, [C.POINTER(DufConvDesc), _P]),
+    'sr_duf_filter_f32': (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, _P, _I, _I, _I, _I, _I, _I, _P]),
+}
+
 _lib = None
 
 
@@ -663,7 +683,7 @@ def load():
             + list(EDVR_BF16_SIGNATURES.items()) + list(STYLEGAN2_SIGNATURES.items()) + list(TRAIN_GROUPS_SIGNATURES.items()) \
             + list(DEGRADE_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(VSR_SIGNATURES.items()) + list(VSR_BF16_SIGNATURES.items()) \
             + list(FLOW_BWD_SIGNATURES.items()) + list(VSR_BWD_SIGNATURES.items()) + list(VSR_DET_SIGNATURES.items()) \
-            + list(DCN_DET_SIGNATURES.items()) + list(TOF_SIGNATURES.items()):
+            + list(DCN_DET_SIGNATURES.items()) + list(TOF_SIGNATURES.items()) + list(DUF_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -64,11 +64,15 @@ class BasicModule(nn.Module):
         raise RuntimeError('BasicModule is a parameter container; SPyNetTOF launches the HIP kernels')
 
 
-def fold_batchnorm(weight, bn_weight, bn_bias, running_mean, running_var, eps):
-    """(w', b') of eval-mode BatchNorm behind a bias-free conv, in float64 on the host, rounded once to fp32 (CPU tensors)."""
+def fold_batchnorm(weight, bn_weight, bn_bias, running_mean, running_var, eps, bias=None):
+    """(w', b') of eval-mode BatchNorm behind a conv of any rank, in float64 on the host, rounded once to fp32 (CPU tensors):
+    ``w' = w * s``, ``b' = (b - mean) * s + beta``, ``s = gamma / sqrt(var + eps)``; ``bias`` None is a bias-free conv."""
     scale = bn_weight.detach().cpu().double() / torch.sqrt(running_var.detach().cpu().double() + float(eps))
-    w = weight.detach().cpu().double() * scale.view(-1, 1, 1, 1)
-    b = bn_bias.detach().cpu().double() - running_mean.detach().cpu().double() * scale
+    w = weight.detach().cpu().double() * scale.view(-1, *([1] * (weight.dim() - 1)))
+    if bias is None:
+        b = bn_bias.detach().cpu().double() - running_mean.detach().cpu().double() * scale
+    else:
+        b = (bias.detach().cpu().double() - running_mean.detach().cpu().double()) * scale + bn_bias.detach().cpu().double()
     return w.float(), b.float()
 
 

@@ -1098,5 +1098,9 @@ extern "C" const char* sr_kernel_name(int id) {
                                           "tof_finish_kernel"};
     return tnames[id - 188];
   }
+  if (id >= 194 && id <= 197) {  // duf_ops.hip (include/sr_hip_duf.h); 193 stays unnamed
+    static const char* const dnames[4] = {"duf_conv3d_f32_kernel", "duf_conv_pack_kernel", "duf_pw_f32_kernel", "duf_filter_f32_kernel"};
+    return dnames[id - 194];
+  }
   return (id >= 0 && id < 8) ? names[id] : "";
 }

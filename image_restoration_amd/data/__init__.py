@@ -11,4 +11,4 @@ from .reds_dataset import REDSDataset, REDSRecurrentDataset  # noqa: F401
 from .single_image_dataset import SingleImageDataset  # noqa: F401
 from .synthetic_clip_dataset import SyntheticClipDataset  # noqa: F401
 from .synthetic_dataset import SyntheticPairedDataset  # noqa: F401
-from .video_test_dataset import VideoRecurrentTestDataset, VideoTestDataset  # noqa: F401
+from .video_test_dataset import VideoRecurrentTestDataset, VideoTestDataset, VideoTestDUFDataset  # noqa: F401

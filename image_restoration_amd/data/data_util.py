@@ -107,3 +107,40 @@ def generate_frame_indices(crt_idx, max_frame_num, num_frames, padding='reflecti
         else:
             out.append(pos + num_frames if before else pos - num_frames)
     return out
+
+
+def generate_gaussian_kernel(kernel_size=13, sigma=1.6):
+    """The ``kernel_size`` x ``kernel_size`` Gaussian of ``duf_downsample`` (float64 numpy), in closed form: the outer product of
+    the 1D Gaussian exp(-x^2 / (2 sigma^2)) truncated at radius int(4 sigma + 0.5) and normalised to sum 1 — what Gaussian
+    smoothing of a unit impulse gives while the radius fits in the kernel, so that no boundary rule enters (sigma 0.8 / 1.2 / 1.6
+    at 13 taps: radius 3 / 5 / 6).  A radius that does not fit is a ValueError."""
+    import numpy as np
+    radius = int(4.0 * float(sigma) + 0.5)
+    if radius > kernel_size // 2:
+        raise ValueError(f'generate_gaussian_kernel: sigma={sigma} needs radius {radius}, which does not fit in {kernel_size} taps')
+    xs = np.arange(-radius, radius + 1, dtype=np.float64)
+    g = np.exp(-0.5 / (float(sigma) * float(sigma)) * xs ** 2)
+    g = g / g.sum()
+    k1 = np.zeros(kernel_size)
+    k1[kernel_size // 2 - radius:kernel_size // 2 + radius + 1] = g
+    return np.outer(k1, k1)
+
+
+def duf_downsample(x, kernel_size=13, scale=4):
+    """The downsampling of the official DUF code on frames [b, t, c, h, w] (or [t, c, h, w]): reflect padding by
+    ``kernel_size // 2 + 2 * scale``, the Gaussian of sigma ``0.4 * scale`` at stride ``scale``, then two rows and columns cut
+    from every side.  Runs where ``x`` lies, in its dtype."""
+    import torch
+    from torch.nn import functional as F
+    if scale not in (2, 3, 4):
+        raise ValueError(f'Only support scale (2, 3, 4), but got {scale}.')
+    squeeze = x.ndim == 4
+    if squeeze:
+        x = x.unsqueeze(0)
+    b, t, c, h, w = x.size()
+    pad = kernel_size // 2 + scale * 2
+    x = F.pad(x.reshape(-1, 1, h, w), (pad, pad, pad, pad), 'reflect')
+    kernel = torch.from_numpy(generate_gaussian_kernel(kernel_size, 0.4 * scale)).type_as(x).unsqueeze(0).unsqueeze(0)
+    x = F.conv2d(x, kernel, stride=scale)[:, :, 2:-2, 2:-2]
+    x = x.reshape(b, t, c, x.size(2), x.size(3))
+    return x.squeeze(0) if squeeze else x

@@ -8,7 +8,8 @@ clips to use, first word of each line; otherwise every sub-folder of the roots, 
 of a clip) and ``lq_path`` of the centre frame.  ``data_info`` lists the same per frame, as VideoBaseModel.validation reads it.
 
 Deviations: any dataset name is taken (the reference refuses names other than Vid4 / REDS4 / REDSofficial although it treats them
-alike); PIL decodes instead of cv2.  ``VideoRecurrentTestDataset`` below hands out whole folders; the Vimeo90K and DUF test datasets are not built."""
+alike); PIL decodes instead of cv2.  ``VideoTestDUFDataset`` below makes its LQ frames with the DUF downsampling and
+``VideoRecurrentTestDataset`` hands out whole folders; the Vimeo90K test datasets are not built."""
 import logging
 import os
 
@@ -86,6 +87,38 @@ class VideoTestDataset(ImageSource, Dataset):
         else:
             lq = self.read_sequence([self.imgs_lq[folder][i] for i in select], 'lq')
             gt = self.read_sequence([self.imgs_gt[folder][idx]], 'gt')[0]
+        return {'lq': lq, 'gt': gt, 'folder': folder, 'idx': self.data_info['idx'][index],
+                'border': self.data_info['border'][index], 'lq_path': self.data_info['lq_path'][index]}
+
+
+@DATASET_REGISTRY.register()
+class VideoTestDUFDataset(VideoTestDataset):
+    """The test set of DUF (behaviour of basicsr/data/video_test_dataset.py:202-251): VideoTestDataset with two more keys,
+    ``use_duf_downsampling`` (the LQ frames are made from the GT frames with data_util.duf_downsample, 13 taps) and ``scale``.
+    Without ``cache_data`` the GT frames are cropped to a multiple of ``scale`` first, as the reference does; with it the cached
+    frames are used as they are.  The returned keys are VideoTestDataset's."""
+
+    def _mod_crop(self, frames):
+        s = self.opt['scale']
+        h, w = frames.shape[-2:]
+        return frames[..., :h - h % s, :w - w % s]
+
+    def __getitem__(self, index):
+        folder = self.data_info['folder'][index]
+        idx, max_idx = (int(v) for v in self.data_info['idx'][index].split('/'))
+        select = data_util.generate_frame_indices(idx, max_idx, self.opt['num_frame'], padding=self.opt['padding'])
+        down = self.opt['use_duf_downsampling']
+        if self.cache_data:
+            lq = (self.imgs_gt if down else self.imgs_lq)[folder].index_select(0, torch.LongTensor(select))
+            gt = self.imgs_gt[folder][idx]
+        else:
+            if down:
+                lq = self._mod_crop(self.read_sequence([self.imgs_gt[folder][i] for i in select], 'gt'))
+            else:
+                lq = self.read_sequence([self.imgs_lq[folder][i] for i in select], 'lq')
+            gt = self._mod_crop(self.read_sequence([self.imgs_gt[folder][idx]], 'gt'))[0]
+        if down:
+            lq = data_util.duf_downsample(lq, kernel_size=13, scale=self.opt['scale'])
         return {'lq': lq, 'gt': gt, 'folder': folder, 'idx': self.data_info['idx'][index],
                 'border': self.data_info['border'][index], 'lq_path': self.data_info['lq_path'][index]}
 

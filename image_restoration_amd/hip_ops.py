@@ -2082,3 +2082,132 @@ def tof_finish(y, clip, ref_idx, mean, std, out=None):
     _launch_arg('sr_tof_finish_f32', clip.device, y.ptr, y.img_stride, clip.data_ptr() + ref_idx * 3 * h * w * 4, t * 3 * h * w,
                 out.data_ptr(), b, h, w, f3[0], f3[1])
     return out
+
+
+# ---- DUF: 3D convolutions on frame-major CB8 clips, the 1x1x1 conv, the dynamic-filter tail (include/sr_hip_duf.h) ----
+
+DUF_CONV3D_COUTS = (16, 32, 64, 256)
+
+
+class ClipCB8:
+    """A frame-major channel-blocked clip: storage ``buf`` [B, T, C/8, H, W, 8] fp32 plus a frame window [t0, t0 + tn).  Frame t
+    of clip i is a CB8 image; a dense concatenation is one such buffer at its final channel count."""
+
+    def __init__(self, buf, t0=0, tn=None):
+        assert buf.dim() == 6 and buf.size(5) == 8 and buf.dtype == torch.float32 and buf.is_contiguous()
+        self.buf, self.t0 = buf, t0
+        self.tn = buf.size(1) - t0 if tn is None else tn
+        assert 0 <= t0 and self.tn > 0 and t0 + self.tn <= buf.size(1)
+
+    @classmethod
+    def empty(cls, b, t, channels, h, w, device):
+        return cls(torch.empty((b, t, (channels + 7) // 8, h, w, 8), dtype=torch.float32, device=device))
+
+    b = property(lambda s: s.buf.size(0))
+    cbn = property(lambda s: s.buf.size(2))
+    h = property(lambda s: s.buf.size(3))
+    w = property(lambda s: s.buf.size(4))
+    device = property(lambda s: s.buf.device)
+    frame_stride = property(lambda s: s.buf.size(2) * s.buf.size(3) * s.buf.size(4) * 8)
+    clip_stride = property(lambda s: s.buf.size(1) * s.frame_stride)
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr() + self.t0 * self.frame_stride * 4
+
+    def frames(self, t0, tn):
+        """The window of frames [t0, t0 + tn) of this window."""
+        return ClipCB8(self.buf, self.t0 + t0, tn)
+
+    def images(self):
+        """The clips of a one-frame window as a plain CB8 batch (a view; needs T == 1 in storage)."""
+        assert self.buf.size(1) == 1
+        return CB8(self.buf.view(self.b, self.cbn, self.h, self.w, 8))
+
+
+class PackedDufConv:
+    """MFMA operand image (weights in operand order, then the bias) of one DUF convolution: an OIDHW weight [cout, cin, kt, 3, 3]
+    -> sr_duf_conv3d_pack_f32, [c, c, 1, 1, 1] -> sr_duf_pw_pack_f32."""
+
+    def __init__(self, weight, bias=None):
+        _need_cuda(weight, 'PackedDufConv')
+        _arg(weight.dim() == 5 and weight.dtype == torch.float32 and tuple(weight.shape[3:]) in ((3, 3), (1, 1)),
+             f'PackedDufConv: needs an fp32 [cout, cin, kt, 3, 3] or [c, c, 1, 1, 1] weight, got {weight.dtype} {tuple(weight.shape)}')
+        _arg(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (weight.size(0),)), 'PackedDufConv: bias does not fit')
+        weight = weight.detach().contiguous()
+        bias = None if bias is None else bias.detach().contiguous()
+        self.cout, self.cin, self.kt = weight.shape[:3]
+        self.pw = weight.size(3) == 1
+        lib = _lib.load()
+        if self.pw:
+            _arg(self.kt == 1 and self.cout == self.cin, f'PackedDufConv: a 1x1x1 weight must be [c, c, 1, 1, 1], got {tuple(weight.shape)}')
+            nfloats = lib.sr_duf_pw_packed_floats(self.cout)
+            _arg(nfloats > 0, f'duf_pw: c = {self.cout} is not supported; supported: a multiple of 8 up to 432')
+            self.w = torch.empty(nfloats, dtype=torch.float32, device=weight.device)
+            _launch_arg('sr_duf_pw_pack_f32', weight.device, weight.data_ptr(), _p(bias), self.cout, self.w.data_ptr())
+        else:
+            nfloats = lib.sr_duf_conv3d_packed_floats(self.cout, self.cin, self.kt)
+            _arg(nfloats > 0, f'duf_conv3d: (cin, cout, kt) = ({self.cin}, {self.cout}, {self.kt}) is not supported; supported: cin 3 or a '
+                 f'multiple of 8 up to 448, cout in {DUF_CONV3D_COUTS}, kt 1 or 3')
+            self.w = torch.empty(nfloats, dtype=torch.float32, device=weight.device)
+            _launch_arg('sr_duf_conv3d_pack_f32', weight.device, weight.data_ptr(), _p(bias), self.cout, self.cin, self.kt, self.w.data_ptr())
+
+
+def _duf_conv_desc(who, src, pc, dst, out_cb0, pad_t, relu, prologue):
+    _arg(isinstance(src, ClipCB8) and isinstance(dst, ClipCB8), f'{who}: source and destination must be ClipCB8 windows')
+    cinb = (pc.cin + 7) // 8
+    tout = src.tn - 2 * (1 - pad_t) if pc.kt == 3 else src.tn
+    _arg(src.cbn >= cinb, f'{who}: the source has too few channel blocks')
+    _arg((dst.b, dst.h, dst.w) == (src.b, src.h, src.w) and dst.tn == tout and dst.device == src.device
+         and out_cb0 >= 0 and dst.cbn >= out_cb0 + pc.cout // 8, f'{who}: the destination window does not fit')
+    d = _lib.DufConvDesc()
+    d.in_, d.in_frame_stride, d.in_clip_stride = src.ptr, src.frame_stride, src.clip_stride
+    d.cin, d.cout, d.kt, d.pad_t, d.b, d.t, d.h, d.w = pc.cin, pc.cout, pc.kt, pad_t, src.b, src.tn, src.h, src.w
+    d.packed, d.out, d.out_frame_stride, d.out_clip_stride = pc.w.data_ptr(), dst.ptr, dst.frame_stride, dst.clip_stride
+    d.out_cb0, d.relu = out_cb0, int(bool(relu))
+    if prologue is not None:
+        scale, shift = prologue
+        _arg(all(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (pc.cin,) and t.device == src.device
+                 for t in (scale, shift)), f'{who}: the prologue needs two fp32 [{pc.cin}] arrays on the device of the source')
+        d.scale, d.shift = scale.data_ptr(), shift.data_ptr()
+    return d
+
+
+def duf_conv3d(src, pc, dst, out_cb0=0, *, pad_t=0, relu=False, prologue=None):
+    """nn.Conv3d(cin, cout, (kt, 3, 3), 1, (pad_t, 1, 1)) [+ ReLU] from the channel prefix of the frames of ``src`` into channel
+    block ``out_cb0`` onward of the frames of ``dst`` (ClipCB8 windows; dst has src.tn - 2 frames for kt = 3 without temporal
+    padding) — one sr_duf_conv3d_f32 launch.  ``prologue``: (scale, shift), the operand becomes max(x * scale + shift, 0)."""
+    _arg(not pc.pw, 'duf_conv3d: the weight image is a 1x1x1 one')
+    d = _duf_conv_desc('duf_conv3d', src, pc, dst, out_cb0, pad_t, relu, prologue)
+    _launch_arg('sr_duf_conv3d_f32', src.device, C.byref(d))
+    return dst
+
+
+def duf_pw(src, pc, dst, out_cb0=0, *, relu=False, prologue=None):
+    """nn.Conv3d(c, c, 1) [+ ReLU] with the same optional prologue — one sr_duf_pw_f32 launch."""
+    _arg(pc.pw, 'duf_pw: the weight image is not a 1x1x1 one')
+    d = _duf_conv_desc('duf_pw', src, pc, dst, out_cb0, 0, relu, prologue)
+    _launch_arg('sr_duf_pw_f32', src.device, C.byref(d))
+    return dst
+
+
+def duf_filter(logits, centre, scale, res=None, *, softmax=True, shuffle=True):
+    """The tail of DUF: [softmax over the 25 taps of] ``logits`` (CB8, 25 s^2 channels, channel = tap * s^2 + sub) applied as a
+    5x5 filter to ``centre`` ([N, 3, H, W] fp32, a view whose images are contiguous: the centre frames of the clip, read in
+    place), plus ``res`` (CB8, 3 s^2 channels), pixel-shuffled to [N, 3, s H, s W] — or [N, 3 s^2, H, W] without ``shuffle`` —
+    one sr_duf_filter_f32 launch."""
+    _need_cuda(centre, 'duf_filter')
+    n, h, w = logits.n, logits.h, logits.w
+    s2 = scale * scale
+    _arg(scale in (2, 3, 4), f'duf_filter: scale {scale} is not supported; supported: 2, 3, 4')
+    _arg(isinstance(logits, CB8) and logits.cbn >= (25 * s2 + 7) // 8, f'duf_filter: logits need {25 * s2} channels')
+    _arg(centre.dtype == torch.float32 and tuple(centre.shape) == (n, 3, h, w) and tuple(centre.stride()[1:]) == (h * w, w, 1)
+         and centre.device == logits.device, f'duf_filter: centre must be fp32 [{n}, 3, {h}, {w}] with contiguous images')
+    _arg(res is None or (isinstance(res, CB8) and (res.n, res.h, res.w) == (n, h, w) and res.cbn >= (3 * s2 + 7) // 8),
+         'duf_filter: res does not fit')
+    shape = (n, 3, scale * h, scale * w) if shuffle else (n, 3 * s2, h, w)
+    out = torch.empty(shape, dtype=torch.float32, device=logits.device)
+    _launch_arg('sr_duf_filter_f32', logits.device, logits.ptr, logits.img_stride, None if res is None else res.ptr,
+                0 if res is None else res.img_stride, centre.data_ptr(), centre.stride(0) if n > 1 else 3 * h * w, out.data_ptr(), n,
+                scale, h, w, int(bool(softmax)), int(bool(shuffle)))
+    return out

@@ -420,3 +420,74 @@ def tof_state_dict(seed=0, flow_gain=4.0, flow_bias=0.2, recon_gain=2.0):
             v = rng.uniform(-fan_bound, fan_bound, shape)
         sd[name] = np.asarray(v, np.float32)
     return sd
+
+
+_DUF_BLOCKS = {16: (3, 32), 28: (9, 16), 52: (21, 16)}   # num_layer -> (num_block, num_grow_ch)
+
+
+def duf_param_shapes(num_layer=52, scale=4):
+    """[(name, shape)] of DUF's state_dict, in the reference's order (BatchNorm3d: weight, bias, running_mean, running_var,
+    num_batches_tracked)."""
+    nb, g = _DUF_BLOCKS[num_layer]
+    out = []
+
+    def bn(name, c):
+        out.extend([(f'{name}.weight', (c,)), (f'{name}.bias', (c,)), (f'{name}.running_mean', (c,)), (f'{name}.running_var', (c,)),
+                    (f'{name}.num_batches_tracked', ())])
+
+    def conv(name, cout, cin, kt, k):
+        out.extend([(f'{name}.weight', (cout, cin, kt, k, k)), (f'{name}.bias', (cout,))])
+
+    def dense(name, c):
+        bn(f'{name}.0', c)
+        conv(f'{name}.2', c, c, 1, 1)
+        bn(f'{name}.3', c)
+        conv(f'{name}.5', g, c, 3, 3)
+
+    conv('conv3d1', 64, 3, 1, 3)
+    c = 64
+    for i in range(nb):
+        dense(f'dense_block1.dense_blocks.{i}', c)
+        c += g
+    for i in range(3):
+        dense(f'dense_block2.temporal_reduce{i + 1}', c)
+        c += g
+    bn('bn3d2', c)
+    conv('conv3d2', 256, c, 1, 3)
+    s2 = scale * scale
+    conv('conv3d_r1', 256, 256, 1, 1)
+    conv('conv3d_r2', 3 * s2, 256, 1, 1)
+    conv('conv3d_f1', 512, 256, 1, 1)
+    conv('conv3d_f2', 25 * s2, 512, 1, 1)
+    return out
+
+
+def duf_state_dict(seed=0, num_layer=52, scale=4, conv_gain=2.0, filter_gain=12.0, res_gain=3.0):
+    """OrderedDict name -> numpy array for DUF, drawn in state_dict order from one seeded generator.  With the default
+    initialisation every BatchNorm is the identity, the 25 filter weights are near uniform and the residual is invisible, which
+    tests nothing.  So: convs ~ U(+-1/sqrt(fan_in)) scaled by ``conv_gain`` (a ReLU halves the energy, the uniform range thirds it),
+    biases ~ U(+-1/sqrt(fan_in)); BatchNorm gamma ~ U(0.5, 1.5), beta and running_mean ~ U(-0.3, 0.3), running_var ~ U(0.5, 2),
+    num_batches_tracked = 100; ``conv3d_f2`` is scaled by ``filter_gain`` (a peaked softmax) and ``conv3d_r2`` by ``res_gain`` (a
+    visible residual)."""
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    fan_bound = 1.0
+    for name, shape in duf_param_shapes(num_layer, scale):
+        leaf = name.rsplit('.', 1)[-1]
+        if leaf == 'num_batches_tracked':
+            sd[name] = np.array(100, np.int64)
+            continue
+        if len(shape) == 5:
+            fan_bound = 1.0 / math.sqrt(shape[1] * shape[2] * shape[3] * shape[4])
+            gain = filter_gain if name.startswith('conv3d_f2') else res_gain if name.startswith('conv3d_r2') else conv_gain
+            v = rng.uniform(-fan_bound, fan_bound, shape) * gain
+        elif leaf == 'running_var':
+            v = rng.uniform(0.5, 2.0, shape)
+        elif leaf == 'running_mean':
+            v = rng.uniform(-0.3, 0.3, shape)
+        elif name.rsplit('.', 2)[-2] in ('0', '3', 'bn3d2'):   # BatchNorm gamma / beta
+            v = rng.uniform(0.5, 1.5, shape) if leaf == 'weight' else rng.uniform(-0.3, 0.3, shape)
+        else:                                                   # bias of a conv
+            v = rng.uniform(-fan_bound, fan_bound, shape)
+        sd[name] = np.asarray(v, np.float32)
+    return sd
