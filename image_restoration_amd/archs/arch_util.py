@@ -11,6 +11,7 @@ import torch
 from torch import nn
 from torch.nn import init
 
+from .. import _lib
 from .. import hip_autograd as A
 from .. import hip_ops as H
 from ..ops.dcn import ModulatedDeformConvPack
@@ -60,6 +61,45 @@ def default_init_weights(module_list, scale=1, bias_fill=0, **kwargs):
                 init.constant_(m.weight, 1)
                 if m.bias is not None:
                     m.bias.data.fill_(bias_fill)
+
+
+def _bn_scale(bn_weight, running_var, eps):
+    """``gamma / sqrt(var + eps)`` of an eval-mode BatchNorm, in float64 on the host."""
+    return bn_weight.detach().cpu().double() / torch.sqrt(running_var.detach().cpu().double() + float(eps))
+
+
+def fold_batchnorm(weight, bn_weight, bn_bias, running_mean, running_var, eps, bias=None):
+    """(w', b') of eval-mode BatchNorm behind a conv of any rank, in float64 on the host, rounded once to fp32 (CPU tensors):
+    ``w' = w * s``, ``b' = (b - mean) * s + beta``, ``s = gamma / sqrt(var + eps)``; ``bias`` None is a bias-free conv."""
+    scale = _bn_scale(bn_weight, running_var, eps)
+    w = weight.detach().cpu().double() * scale.view(-1, *([1] * (weight.dim() - 1)))
+    if bias is None:
+        b = bn_bias.detach().cpu().double() - running_mean.detach().cpu().double() * scale
+    else:
+        b = (bias.detach().cpu().double() - running_mean.detach().cpu().double()) * scale + bn_bias.detach().cpu().double()
+    return w.float(), b.float()
+
+
+def bn_prologue(bn):
+    """(scale, shift) of eval-mode ``bn`` in front of a conv as fp32 CPU tensors: ``scale = gamma / sqrt(var + eps)``, ``shift =
+    beta - mean * scale`` in float64, rounded once.  The kernels apply ``max(x * scale + shift, 0)``."""
+    scale = _bn_scale(bn.weight, bn.running_var, bn.eps)
+    shift = bn.bias.detach().cpu().double() - bn.running_mean.detach().cpu().double() * scale
+    return scale.float(), shift.float()
+
+
+def refuse_inference_only(net_name, training, tensors, params, what):
+    """The refusals of a forward-only network whose BatchNorm layers run from their running statistics (TOFlow, DUF): training
+    mode, a forward that would need a graph, CPU inputs.  ``what``: what the network does with those layers."""
+    if training:
+        raise NotImplementedError(f'{net_name} runs in eval mode only: its BatchNorm layers are {what} their running statistics '
+                                  'and batch statistics are not built; call .eval()')
+    if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in params)):
+        raise NotImplementedError(f'{net_name} runs inference only: there is no backward; run under torch.no_grad() (or clear '
+                                  'requires_grad on the input and the parameters)')
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.SrHipError(f'{net_name}.forward runs only on a HIP device (no CPU fallback): move the module and inputs with '
+                              '.to("cuda")')
 
 
 def make_layer(basic_block, num_basic_block, **kwarg):

@@ -19,9 +19,10 @@ forward is a composition of launches (include/sr_hip_duf.h, include/sr_hip_ridne
 
 The concat buffer is allocated once at the final channel count, so no concatenation copies anything.  BatchNorm runs in eval
 mode only: the one in front of a convolution becomes ``scale = gamma / sqrt(var + eps)``, ``shift = beta - mean * scale``
-(float64 on the host, rounded once), the one behind the 1x1x1 convolution is folded (``tof_arch.fold_batchnorm`` with the
-bias).  Packed weights, folds and prologue arrays are cached on storage pointer and version of every tensor they are made
-from, so an in-place edit of ``running_var`` is seen by the next forward.
+(float64 on the host, rounded once: ``arch_util.bn_prologue``), the one behind the 1x1x1 convolution is folded
+(``arch_util.fold_batchnorm`` with the bias).  Packed weights, folds and prologue arrays are cached by ``HipGenerator.derived`` on
+storage pointer, version and FlatAdam epoch of every tensor they are made from, so an in-place edit of ``running_var`` is seen by
+the next forward.
 
 ValueError for a clip that is not ``[b, 7, 3, h, w]`` fp32 (the temporal arithmetic 7 -> 7 -> 5 -> 3 -> 1 fixes 7 frames);
 NotImplementedError in training mode (even under ``torch.no_grad()``) and when a graph would be needed; ``_lib.SrHipError`` for
@@ -31,10 +32,10 @@ import numpy as np
 import torch
 from torch import nn
 
-from .. import _lib, hip_ops
+from .. import hip_ops
 from ..utils.registry import ARCH_REGISTRY
+from .arch_util import bn_prologue, fold_batchnorm, refuse_inference_only  # noqa: F401  (bn_prologue: its old home)
 from .hip_generator import HipGenerator
-from .tof_arch import fold_batchnorm
 
 
 def _bn_args(adapt_official_weights):
@@ -48,14 +49,6 @@ def _dense_layers(cin, num_grow_ch, pad_t, bn):
         nn.Conv3d(cin, cin, (1, 1, 1), stride=(1, 1, 1), padding=(0, 0, 0), bias=True),
         nn.BatchNorm3d(cin, **bn), nn.ReLU(inplace=True),
         nn.Conv3d(cin, num_grow_ch, (3, 3, 3), stride=(1, 1, 1), padding=(pad_t, 1, 1), bias=True))
-
-
-def bn_prologue(bn):
-    """(scale, shift) of eval-mode ``bn`` as fp32 CPU tensors: ``scale = gamma / sqrt(var + eps)``, ``shift = beta - mean * scale``
-    in float64, rounded once.  The kernels apply ``max(x * scale + shift, 0)``."""
-    scale = bn.weight.detach().cpu().double() / torch.sqrt(bn.running_var.detach().cpu().double() + float(bn.eps))
-    shift = bn.bias.detach().cpu().double() - bn.running_mean.detach().cpu().double() * scale
-    return scale.float(), shift.float()
 
 
 class DenseBlocksTemporalReduce(nn.Module):
@@ -89,18 +82,6 @@ class DenseBlocks(nn.Module):
         raise RuntimeError('DenseBlocks is a parameter container; DUF launches the HIP kernels')
 
 
-def _refuse(name, training, tensors, params):
-    if training:
-        raise NotImplementedError(f'{name} runs in eval mode only: its BatchNorm layers are applied from their running statistics '
-                                  'and batch statistics are not built; call .eval()')
-    if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in params)):
-        raise NotImplementedError(f'{name} runs inference only: there is no backward; run under torch.no_grad() (or clear '
-                                  'requires_grad on the input and the parameters)')
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.SrHipError(f'{name}.forward runs only on a HIP device (no CPU fallback): move the module and inputs with '
-                              '.to("cuda")')
-
-
 class DynamicUpsamplingFilter(nn.Module):
     """The dynamic upsampling filter: ``forward(x, filters)`` with x [n, 3, h, w] and already-normalised filters
     [n, 25, s*s, h, w] (s in 2, 3, 4) -> [n, 3*s*s, h, w], the same filters on the three colours — one sr_duf_filter_f32 launch
@@ -124,7 +105,7 @@ class DynamicUpsamplingFilter(nn.Module):
                 or filters.size(2) not in (4, 9, 16) or tuple(filters.shape[3:]) != (h, w):
             raise ValueError(f'DynamicUpsamplingFilter: expected fp32 [{n}, 25, 4 | 9 | 16, {h}, {w}] filters, got {filters.dtype} '
                              f'{tuple(filters.shape)}')
-        _refuse('DynamicUpsamplingFilter', False, (x, filters), ())
+        refuse_inference_only('DynamicUpsamplingFilter', False, (x, filters), (), 'applied from')
         with torch.no_grad():
             s2 = filters.size(2)
             logits = hip_ops.nchw_to_cb8(filters.reshape(n, 25 * s2, h, w))
@@ -164,18 +145,7 @@ class DUF(HipGenerator):
         self.conv3d_f1 = nn.Conv3d(256, 512, (1, 1, 1), stride=(1, 1, 1), padding=(0, 0, 0), bias=True)
         self.conv3d_f2 = nn.Conv3d(512, 1 * 5 * 5 * (scale ** 2), (1, 1, 1), stride=(1, 1, 1), padding=(0, 0, 0), bias=True)
 
-    # ---- device images, rebuilt when a tensor they are made from changed
-    def _cached(self, key, tensors, extra, build):
-        sig = tuple((t.data_ptr(), t._version) for t in tensors) + (extra, self._pack_gen)
-        hit = self._packs.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        if any(t.dtype != torch.float32 for t in tensors):
-            raise _lib.SrHipError('DUF parameters must be fp32')
-        val = build()
-        self._packs[key] = (sig, val)
-        return val
-
+    # ---- device images, cached by HipGenerator.derived: rebuilt when a tensor they are made from changed
     def packed_conv(self, conv, bn=None):
         """The weight image of a Conv3d (hip_ops.PackedDufConv), with eval-mode ``bn`` behind it folded in."""
         tensors = (conv.weight, conv.bias) + (() if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var))
@@ -186,18 +156,18 @@ class DUF(HipGenerator):
             w, b = fold_batchnorm(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bias=conv.bias)
             dev = conv.weight.device
             return hip_ops.PackedDufConv(w.to(dev), b.to(dev))
-        return self._cached((id(conv), 'conv'), tensors, None if bn is None else float(bn.eps), build)
+        return self.derived((id(conv), 'conv'), tensors, None if bn is None else float(bn.eps), build)
 
     def packed_head(self, conv):
         """The sr_convd_f32 (ksize 1) image of one of the four 1x1x1 head convolutions."""
         w = conv.weight
-        return self._cached((id(conv), 'head'), (w, conv.bias), None,
+        return self.derived((id(conv), 'head'), (w, conv.bias), None,
                             lambda: hip_ops.PackedConvK(w.detach().view(w.size(0), w.size(1), 1, 1), conv.bias.detach()))
 
     def prologue(self, bn):
         """(scale, shift) of eval-mode ``bn`` on the device."""
         dev = bn.weight.device
-        return self._cached((id(bn), 'prologue'), (bn.weight, bn.bias, bn.running_mean, bn.running_var), float(bn.eps),
+        return self.derived((id(bn), 'prologue'), (bn.weight, bn.bias, bn.running_mean, bn.running_var), float(bn.eps),
                             lambda: tuple(t.to(dev) for t in bn_prologue(bn)))
 
     def _dense(self, seq, cat, tmp, cin, pad_t):
@@ -241,7 +211,7 @@ class DUF(HipGenerator):
         if x.dim() != 5 or x.size(1) != 7 or x.size(2) != 3 or x.dtype != torch.float32 or x.numel() == 0:
             raise ValueError(f'DUF: expected an fp32 [b, 7, 3, h, w] clip (the temporal reduction 7 -> 5 -> 3 -> 1 fixes 7 frames), '
                              f'got {x.dtype} {tuple(x.shape)}')
-        _refuse('DUF', self.training, (x,), self.parameters())
+        refuse_inference_only('DUF', self.training, (x,), self.parameters(), 'applied from')
         with torch.no_grad():
             return self.run_forward(x.contiguous(), keep)
 

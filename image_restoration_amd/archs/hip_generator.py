@@ -1,6 +1,8 @@
-"""What the per-layer HIP generators (MSRResNet, EDSR, RCAN, RIDNet) share: the weight-image cache and the forward dispatch
-(``HipGenerator``), the fp32 / bf16 ops table one layer list is written against (``F32``, ``BF16``) with the residual block and
-upsampling stage the networks have in common, and the autograd scaffold (``WholeNetFunction``, ``GradRouter``).
+"""What the per-layer HIP generators (MSRResNet, EDSR, RCAN, RIDNet, SpyNet, TOFlow, DUF) share: the forward dispatch and ONE
+cache of everything a net derives from its tensors (``HipGenerator.derived``: weight images, BatchNorm folds and prologues, the
+host copy of ``mean`` / ``std``; the eval-mode BatchNorm arithmetic itself is arch_util.fold_batchnorm / bn_prologue), the
+fp32 / bf16 ops table one layer list is written against (``F32``, ``BF16``) with the residual block and upsampling stage the
+networks have in common, and the autograd scaffold (``WholeNetFunction``, ``GradRouter``).
 
 A network built on this writes its parameters, ``run_forward(x, keep, ops)`` and the ``run_backward`` of its Function.  RRDBNet
 and the discriminators (whole-network C entry points) have their own base, hip_driver.py; GFPGANv1OCR (one Python-built pack for
@@ -42,26 +44,35 @@ class HipGenerator(nn.Module):
         """Call after parameter memory was written behind torch's version counters (fused Adam, EMA, a broadcast)."""
         self._pack_gen += 1
 
-    def packed(self, conv, mode=0, bf16=False):
-        """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter):
-        sr_conv3x3_pack_f32 for 3x3 convs (every dilation), sr_conv7x7_pack_f32 / sr_conv7x7_dgrad_pack_f32 for SpyNet's 7x7 convs, sr_convk_pack_f32 for any
-        other kernel size; rebuilt when the
-        parameter storage, its version, the FlatAdam epoch of the parameter or this net's generation (invalidate_packed) changed.
-        Not hip_ops.cached_pack: that cache is keyed on the process-global epoch, so one net's invalidate_packed() would repack
-        every other network's images (the discriminator's after each generator step)."""
-        w, b = conv.weight, conv.bias
-        sig = (w.data_ptr(), w._version, getattr(w, '_sr_epoch', (0,))[0], b.data_ptr(), b._version, self._pack_gen)
-        key = (id(conv), mode, bf16)
+    def derived(self, key, tensors, extra, build):
+        """``build()``, cached in ``_packs`` under ``key``: a weight image, a BatchNorm fold, host floats — anything made from
+        ``tensors``.  Rebuilt when the storage, the version or the FlatAdam epoch (``_sr_epoch``: a write behind torch's version
+        counter) of one of them, ``extra`` (a scalar the result depends on, e.g. a BatchNorm eps) or this net's generation
+        (invalidate_packed) changed; ``_apply`` empties the cache.  Refuses tensors that are not fp32."""
+        sig = tuple((t.data_ptr(), t._version, getattr(t, '_sr_epoch', (0,))[0]) for t in tensors) + (extra, self._pack_gen)
         hit = self._packs.get(key)
         if hit is not None and hit[0] == sig:
             return hit[1]
-        if w.dtype != torch.float32 or b.dtype != torch.float32:
+        if any(t.dtype != torch.float32 for t in tensors):
             raise _lib.SrHipError(f'{type(self).__name__} parameters must be fp32')
+        val = build()
+        self._packs[key] = (sig, val)
+        return val
+
+    def packed(self, conv, mode=0, bf16=False):
+        """Weight image of ``conv`` (mode 0: forward, 1: data gradient; bf16: the CB16 image rounded from the fp32 parameter):
+        sr_conv3x3_pack_f32 for 3x3 convs (every dilation), sr_conv7x7_pack_f32 / sr_conv7x7_dgrad_pack_f32 for SpyNet's 7x7 convs,
+        sr_tof_conv9x9_pack_f32 for TOFlow's 9x9 convs, sr_convk_pack_f32 for any other kernel size; cached by ``derived``.
+        Not hip_ops.cached_pack: that cache is keyed on the process-global epoch, so one net's invalidate_packed() would repack
+        every other network's images (the discriminator's after each generator step)."""
+        w, b = conv.weight, conv.bias
         cls = hip_ops.PackedConvBF16 if bf16 else hip_ops.PackedConv if w.shape[2] == 3 else \
             hip_ops.PackedConv7x7 if w.shape[2] == 7 else hip_ops.PackedConv9x9 if w.shape[2] == 9 else hip_ops.PackedConvK
-        pc = cls(w, b if mode == 0 else None, mode=mode)
-        self._packs[key] = (sig, pc)
-        return pc
+        return self.derived((id(conv), mode, bf16), (w, b), None, lambda: cls(w, b if mode == 0 else None, mode=mode))
+
+    def _norm_host(self):
+        """The ``mean`` and ``std`` buffers of a network that has them as host floats, read back once per value of the buffers."""
+        return self.derived('norm', (self.mean, self.std), None, lambda: (self.mean.flatten().tolist(), self.std.flatten().tolist()))
 
     def _drop_device_caches(self):
         """Whatever else a subclass keeps per device; cleared with the weight images when the module is moved or cast."""

@@ -73,7 +73,6 @@ class SpyNet(HipGenerator):
             self.load_state_dict(checkpoint['params'])
         for name, values in (('mean', _MEAN), ('std', _STD)):
             self.register_buffer(name, torch.tensor(values, dtype=torch.float32).view(1, 3, 1, 1))
-        self._norm = None
         self._autograd = False
 
     def set_autograd(self, enabled=True):
@@ -82,16 +81,6 @@ class SpyNet(HipGenerator):
         Returns self."""
         self._autograd = bool(enabled)
         return self
-
-    def _drop_device_caches(self):
-        self._norm = None
-
-    def _norm_host(self):
-        """(mean, std) as host floats, read back once per value of the buffers."""
-        sig = (self.mean.data_ptr(), self.mean._version, self.std.data_ptr(), self.std._version)
-        if self._norm is None or self._norm[0] != sig:
-            self._norm = (sig, self.mean.flatten().tolist(), self.std.flatten().tolist())
-        return self._norm[1], self._norm[2]
 
     def process(self, ref, supp, levels=None, keep=None):
         """The pyramid on a batch whose sides are multiples of 32: the flow [N, 2, H, W]; ``levels`` (a list) receives the flow

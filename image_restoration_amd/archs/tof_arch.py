@@ -20,9 +20,10 @@ composition of launches (include/sr_hip_tof.h, include/sr_hip_flow.h, include/sr
 
 BatchNorm runs in eval mode only and costs no launch: it is folded into the bias-free 7x7 conv in front of it,
 ``w' = w * gamma / sqrt(var + eps)``, ``b' = beta - mean * gamma / sqrt(var + eps)``, computed in float64 on the host and rounded
-once to fp32.  The folded image is cached on the storage and version of the conv weight and of the four BatchNorm tensors, so an
-in-place change of ``running_var`` is seen by the next forward.  A module in training mode raises NotImplementedError (batch
-statistics are not built), even under ``torch.no_grad()``.
+once to fp32 (``arch_util.fold_batchnorm``).  The folded image is cached by ``HipGenerator.derived`` on the storage, version and
+FlatAdam epoch of the conv weight and of the four BatchNorm tensors, so an in-place change of ``running_var`` is seen by the next
+forward.  A module in training mode raises NotImplementedError (batch statistics are not built), even under ``torch.no_grad()``
+(``arch_util.refuse_inference_only``).
 
 ValueError for a clip that is not ``[b, 7, 3, h, w]`` fp32 and for h or w that is not a multiple of 16 (the reference's
 ``torch.cat`` fails there); NotImplementedError when a graph would be needed; ``_lib.SrHipError`` for CPU tensors.
@@ -30,15 +31,16 @@ ValueError for a clip that is not ``[b, 7, 3, h, w]`` fp32 and for h or w that i
 import torch
 from torch import nn
 
-from .. import _lib, hip_ops
+from .. import hip_ops
 from ..utils.registry import ARCH_REGISTRY
-from .arch_util import Conv3x3Params
+from .arch_util import Conv3x3Params, fold_batchnorm, refuse_inference_only  # noqa: F401  (fold_batchnorm: its old home)
 from .hip_generator import HipGenerator
 
 _CHANNELS = ((8, 32), (32, 64), (64, 32), (32, 16), (16, 2))
 _LEVELS = 4
 _MEAN, _STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 _OFFICIAL_ORDER = (3, 0, 1, 2, 4, 5, 6)
+_BN = 'folded into the 7x7 convs from'   # what refuse_inference_only says of the BatchNorm layers
 
 
 class BasicModule(nn.Module):
@@ -64,31 +66,6 @@ class BasicModule(nn.Module):
         raise RuntimeError('BasicModule is a parameter container; SPyNetTOF launches the HIP kernels')
 
 
-def fold_batchnorm(weight, bn_weight, bn_bias, running_mean, running_var, eps, bias=None):
-    """(w', b') of eval-mode BatchNorm behind a conv of any rank, in float64 on the host, rounded once to fp32 (CPU tensors):
-    ``w' = w * s``, ``b' = (b - mean) * s + beta``, ``s = gamma / sqrt(var + eps)``; ``bias`` None is a bias-free conv."""
-    scale = bn_weight.detach().cpu().double() / torch.sqrt(running_var.detach().cpu().double() + float(eps))
-    w = weight.detach().cpu().double() * scale.view(-1, *([1] * (weight.dim() - 1)))
-    if bias is None:
-        b = bn_bias.detach().cpu().double() - running_mean.detach().cpu().double() * scale
-    else:
-        b = (bias.detach().cpu().double() - running_mean.detach().cpu().double()) * scale + bn_bias.detach().cpu().double()
-    return w.float(), b.float()
-
-
-def _refuse_graph(net, tensors):
-    name = type(net).__name__
-    if net.training:
-        raise NotImplementedError(f'{name} runs in eval mode only: its BatchNorm layers are folded into the 7x7 convs from their '
-                                  'running statistics and batch statistics are not built; call .eval()')
-    if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in net.parameters())):
-        raise NotImplementedError(f'{name} runs inference only: there is no backward; run under torch.no_grad() (or clear '
-                                  'requires_grad on the input and the parameters)')
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.SrHipError(f'{name}.forward runs only on a HIP device (no CPU fallback): move the module and inputs with '
-                              '.to("cuda")')
-
-
 class SPyNetTOF(HipGenerator):
     """The four-level flow estimator of TOFlow.  ``load_path``: a checkpoint whose ``'params'`` entry holds the state_dict; None
     keeps the default initialisation.  Normalisation is the caller's, as in the reference."""
@@ -103,18 +80,9 @@ class SPyNetTOF(HipGenerator):
         """The 7x7 weight image of ``conv`` with eval-mode ``bn`` folded in (hip_ops.PackedConv7x7), rebuilt when the conv
         weight or a BatchNorm parameter or buffer changed."""
         tensors = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        sig = tuple((t.data_ptr(), t._version) for t in tensors) + (float(bn.eps), self._pack_gen)
-        key = (id(conv), 'bn')
-        hit = self._packs.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        if any(t.dtype != torch.float32 for t in tensors):
-            raise _lib.SrHipError('SPyNetTOF parameters must be fp32')
-        w, b = fold_batchnorm(*tensors, bn.eps)
         dev = conv.weight.device
-        pc = hip_ops.PackedConv7x7(w.to(dev), b.to(dev))
-        self._packs[key] = (sig, pc)
-        return pc
+        return self.derived((id(conv), 'bn'), tensors, float(bn.eps),
+                            lambda: hip_ops.PackedConv7x7(*(t.to(dev) for t in fold_batchnorm(*tensors, bn.eps))))
 
     def flows(self, level_input):
         """The pyramid: ``level_input(level, flow_prev)`` -> (the level's CB8 input block, up).  Returns the finest flow as a
@@ -135,7 +103,7 @@ class SPyNetTOF(HipGenerator):
             raise ValueError(f'SPyNetTOF: expected fp32 [N, 3, H, W] frames, got {ref.dtype} {tuple(ref.shape)}')
         if ref.size(2) % 16 or ref.size(3) % 16 or ref.numel() == 0:
             raise ValueError(f'SPyNetTOF: h and w must be positive multiples of 16, got {ref.size(2)}x{ref.size(3)}')
-        _refuse_graph(self, (ref, supp))
+        refuse_inference_only('SPyNetTOF', self.training, (ref, supp), self.parameters(), _BN)
         with torch.no_grad():
             n = ref.size(0)
             pyramid = [torch.cat([ref, supp], 0).contiguous()]
@@ -162,21 +130,10 @@ class TOFlow(HipGenerator):
         self.conv_2 = Conv3x3Params(64, 64, ksize=9)
         self.conv_3 = Conv3x3Params(64, 64, ksize=1)
         self.conv_4 = Conv3x3Params(64, 3, ksize=1)
-        self._norm = None
-
-    def _drop_device_caches(self):
-        self._norm = None
 
     def invalidate_packed(self):
         super().invalidate_packed()
         self.spynet.invalidate_packed()
-
-    def _norm_host(self):
-        """(mean, std) as host floats, read back once per value of the buffers."""
-        sig = (self.mean.data_ptr(), self.mean._version, self.std.data_ptr(), self.std._version)
-        if self._norm is None or self._norm[0] != sig:
-            self._norm = (sig, self.mean.flatten().tolist(), self.std.flatten().tolist())
-        return self._norm[1], self._norm[2]
 
     def run_forward(self, lrs, keep=None):
         """The whole forward on a contiguous fp32 device clip.  ``keep`` (a dict) receives ``flows``, the six flows of each clip
@@ -207,6 +164,6 @@ class TOFlow(HipGenerator):
             raise ValueError(f'TOFlow: expected an fp32 [b, 7, 3, h, w] clip, got {lrs.dtype} {tuple(lrs.shape)}')
         if lrs.size(3) % 16 or lrs.size(4) % 16:
             raise ValueError(f'TOFlow: h and w must be multiples of 16 (four pyramid levels), got {lrs.size(3)}x{lrs.size(4)}')
-        _refuse_graph(self, (lrs,))
+        refuse_inference_only('TOFlow', self.training, (lrs,), self.parameters(), _BN)
         with torch.no_grad():
             return self.run_forward(lrs.contiguous(), keep)

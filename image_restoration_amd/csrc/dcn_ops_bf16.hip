@@ -245,7 +245,7 @@ int deform_launch(const DeformParams& p, int groups, const sr_dcn_bf16_desc* d, 
   const bool prof = sr::prof_on();
   if (prof) {
     const double px = (double)d->n * d->h * d->w;
-    prof_rec(stream, 124, d->cin, d->cout, d->n, d->h, d->w, 2.0 * 9 * d->cin * d->cout * px,
+    sr::prof_rec(stream, 124, d->cin, d->cout, d->n, d->h, d->w, 2.0 * 9 * d->cin * d->cout * px,
              px * (2.0 * (d->cin + d->cout) + 4.0 * 27 * d->deformable_groups));
   }
   hipLaunchKernelGGL(kern, dim3(p.tiles_x * p.tiles_y * d->n, groups), dim3(256), lds, stream, p);

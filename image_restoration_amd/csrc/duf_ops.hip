@@ -24,19 +24,6 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-void prof_rec(hipStream_t stream, int id, int cin, int cout, int n, int h, int w, double flops, double bytes) {
-  sr_launch_record r = {};
-  r.kernel_id = id;
-  r.cin = cin;
-  r.cout = cout;
-  r.n = n;
-  r.h = h;
-  r.w = w;
-  r.flops = flops;
-  r.bytes = bytes;
-  sr::prof_begin(stream, r);
-}
-
 constexpr int kTH = 8, kTW = 32;  // output tile
 
 struct DParams {
@@ -269,7 +256,7 @@ int pack_common(const char* who, const float* weight, const float* bias, int cou
   SR_CHECK_ARG(sr::aligned16(packed), "%s: packed must be 16-byte aligned", who);
   const long long wf = image_weight_floats(cout, cin, kt, taps, gc), total = wf + (long long)((cout + gc - 1) / gc) * gc;
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 195, cin, cout, 1, kt, taps, 0.0, 4.0 * (total + (double)taps * kt * cin * cout));
+  if (prof) sr::prof_rec(stream, 195, cin, cout, 1, kt, taps, 0.0, 4.0 * (total + (double)taps * kt * cin * cout));
   hipLaunchKernelGGL(duf_conv_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, weight, bias, packed, cout, cin,
                      (cin + 7) / 8, kt, taps, gc, wf, total);
   if (prof) sr::prof_end(stream);
@@ -333,7 +320,7 @@ int launch_conv(const char* who, K kernel, int lds, const DParams& p, int id, co
   const bool prof = sr::prof_on();
   if (prof) {
     const double px = (double)d->b * p.Tout * d->h * d->w;
-    prof_rec(stream, id, d->cin, d->cout, d->b * p.Tout, d->h, d->w, 2.0 * taps * d->kt * d->cin * d->cout * px,
+    sr::prof_rec(stream, id, d->cin, d->cout, d->b * p.Tout, d->h, d->w, 2.0 * taps * d->kt * d->cin * d->cout * px,
              4.0 * px * (p.cinb * 8.0 * d->kt * groups + d->cout));
   }
   hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, p);
@@ -462,7 +449,7 @@ extern "C" int sr_duf_filter_f32(const float* logits, long long logits_img_strid
   SR_CHECK_ARG(logits_img_stride >= hw * 8 * lb && (!res || res_img_stride >= hw * 8 * rb) && centre_img_stride >= hw * 3,
                "sr_duf_filter_f32: an image stride is smaller than the image");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 197, 25 * s2, 3 * s2, n, h, w, (double)n * hw * s2 * (4.0 * 25 + 6.0 * 25), 4.0 * n * hw * (25.0 * s2 + 6.0 * s2 + 3.0));
+  if (prof) sr::prof_rec(stream, 197, 25 * s2, 3 * s2, n, h, w, (double)n * hw * s2 * (4.0 * 25 + 6.0 * 25), 4.0 * n * hw * (25.0 * s2 + 6.0 * s2 + 3.0));
   hipLaunchKernelGGL(duf_filter_f32_kernel, dim3((unsigned)((hw * s2 + 255) / 256), 1, (unsigned)n), dim3(256), 0, stream, logits,
                      logits_img_stride, res, res_img_stride, centre, centre_img_stride, out, s, h, w, softmax, shuffle);
   if (prof) sr::prof_end(stream);

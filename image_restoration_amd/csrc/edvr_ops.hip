@@ -197,19 +197,6 @@ constexpr int conv3x3s2_lds_bytes() {
   return 2 * (((((2 * 4 * PT + 1) * 65 * 32) + 1023) / 1024) * 1024 + 9 * COT * 1024);
 }
 
-void prof_rec(hipStream_t stream, int id, int cin, int cout, int n, int h, int w, double flops, double bytes) {
-  sr_launch_record r = {};
-  r.kernel_id = id;
-  r.cin = cin;
-  r.cout = cout;
-  r.n = n;
-  r.h = h;
-  r.w = w;
-  r.flops = flops;
-  r.bytes = bytes;
-  sr::prof_begin(stream, r);
-}
-
 template <int COT, int PT>
 int conv3x3s2_launch(const ConvS2Params& p, int n, int groups, const sr_conv3x3s2_desc* d, hipStream_t stream) {
   constexpr int lds = conv3x3s2_lds_bytes<COT, PT>();
@@ -218,7 +205,7 @@ int conv3x3s2_launch(const ConvS2Params& p, int n, int groups, const sr_conv3x3s
   const bool prof = sr::prof_on();
   if (prof) {
     const double po = (double)n * p.Ho * p.Wo, pi = (double)n * p.H * p.W;
-    prof_rec(stream, 114, d->cin_pad, d->cout, n, p.H, p.W, 2.0 * 9 * d->cin_pad * d->cout * po, 4.0 * (pi * d->cin_pad + po * d->cout));
+    sr::prof_rec(stream, 114, d->cin_pad, d->cout, n, p.H, p.W, 2.0 * 9 * d->cin_pad * d->cout * po, 4.0 * (pi * d->cin_pad + po * d->cout));
   }
   hipLaunchKernelGGL(kern, dim3(p.tiles_x * p.tiles_y * n, groups), dim3(256), lds, stream, p);
   if (prof) sr::prof_end(stream);
@@ -529,7 +516,7 @@ extern "C" int sr_cb8_zero_insert2_f32(const float* dy, int64_t dy_ns, float* ou
   const long long total = (long long)n * cb * h * w * 2;
   SR_CHECK_ARG(grid_ok(total), "sr_cb8_zero_insert2_f32: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 115, cb * 8, cb * 8, n, h, w, 0.0, 4.0 * n * cb * 8 * ((double)h * w + (double)((h + 1) / 2) * ((w + 1) / 2)));
+  if (prof) sr::prof_rec(stream, 115, cb * 8, cb * 8, n, h, w, 0.0, 4.0 * n * cb * 8 * ((double)h * w + (double)((h + 1) / 2) * ((w + 1) / 2)));
   hipLaunchKernelGGL(cb8_zero_insert2_kernel, EDVR_GRID(total), dy, (long long)dy_ns, out, (long long)out_ns, cb, h, w, total);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("cb8_zero_insert2 launch");
@@ -545,7 +532,7 @@ extern "C" int sr_pool3x3s2_fwd_f32(const float* x, int64_t x_ns, float* out_max
   const long long total = (long long)n * cb * ho * wo * 2;
   SR_CHECK_ARG(grid_ok(total), "sr_pool3x3s2_fwd_f32: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 116, cb * 8, cb * 16, n, h, w, 17.0 * n * cb * 8 * ho * wo, 4.0 * n * cb * 8 * ((double)h * w + 2.0 * ho * wo));
+  if (prof) sr::prof_rec(stream, 116, cb * 8, cb * 16, n, h, w, 17.0 * n * cb * 8 * ho * wo, 4.0 * n * cb * 8 * ((double)h * w + 2.0 * ho * wo));
   hipLaunchKernelGGL(pool3x3s2_fwd_kernel, EDVR_GRID(total), x, (long long)x_ns, out_max, (long long)max_ns, out_avg,
                      (long long)avg_ns, cb, h, w, ho, wo, total);
   if (prof) sr::prof_end(stream);
@@ -562,7 +549,7 @@ extern "C" int sr_pool3x3s2_bwd_f32(const float* x, int64_t x_ns, const float* g
   const long long total = (long long)n * cb * h * w * 2;
   SR_CHECK_ARG(grid_ok(total), "sr_pool3x3s2_bwd_f32: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 117, cb * 16, cb * 8, n, h, w, 12.0 * n * cb * 8 * h * w, 4.0 * n * cb * 8 * (2.0 * h * w + 2.0 * ho * wo));
+  if (prof) sr::prof_rec(stream, 117, cb * 16, cb * 8, n, h, w, 12.0 * n * cb * 8 * h * w, 4.0 * n * cb * 8 * (2.0 * h * w + 2.0 * ho * wo));
   hipLaunchKernelGGL(pool3x3s2_bwd_kernel, EDVR_GRID(total), x, (long long)x_ns, g_max, (long long)gmax_ns, g_avg, (long long)gavg_ns,
                      dx, (long long)dx_ns, cb, h, w, ho, wo, total);
   if (prof) sr::prof_end(stream);
@@ -581,7 +568,7 @@ extern "C" int sr_tsa_corr_fwd_f32(const float* emb, int64_t emb_ns, const float
   const long long hw = (long long)h * w, total = (long long)b * t * hw;
   SR_CHECK_ARG(grid_ok(total), "sr_tsa_corr_fwd_f32: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 118, c, c, b * t, h, w, 3.0 * total * c, 4.0 * total * (3.0 * c + 1) + 4.0 * b * hw * c);
+  if (prof) sr::prof_rec(stream, 118, c, c, b * t, h, w, 3.0 * total * c, 4.0 * total * (3.0 * c + 1) + 4.0 * b * hw * c);
   hipLaunchKernelGGL(tsa_corr_fwd_kernel, EDVR_GRID(total), emb, (long long)emb_ns, emb_ref, (long long)ref_ns, aligned,
                      (long long)al_ns, prob, out, (long long)out_ns, t, c / 8, hw, total);
   if (prof) sr::prof_end(stream);
@@ -602,12 +589,12 @@ extern "C" int sr_tsa_corr_bwd_f32(const float* g, int64_t g_ns, const float* em
   const long long hw = (long long)h * w, total = (long long)b * t * hw, total_ref = (long long)b * (c / 8) * hw * 2;
   SR_CHECK_ARG(grid_ok(total) && grid_ok(total_ref), "sr_tsa_corr_bwd_f32: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 119, c, c, b * t, h, w, 4.0 * total * c, 4.0 * total * (4.0 * c + 2) + 4.0 * b * hw * c);
+  if (prof) sr::prof_rec(stream, 119, c, c, b * t, h, w, 4.0 * total * c, 4.0 * total * (4.0 * c + 2) + 4.0 * b * hw * c);
   hipLaunchKernelGGL(tsa_corr_bwd_kernel, EDVR_GRID(total), g, (long long)g_ns, emb_ref, (long long)ref_ns, aligned, (long long)al_ns,
                      prob, dcorr, d_aligned, (long long)da_ns, d_emb, (long long)de_ns, t, c / 8, hw, total);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("tsa_corr_bwd launch");
-  if (prof) prof_rec(stream, 120, c, c, b, h, w, 2.0 * total * c, 4.0 * (total * (c + 1.0) + (double)b * hw * c));
+  if (prof) sr::prof_rec(stream, 120, c, c, b, h, w, 2.0 * total * c, 4.0 * (total * (c + 1.0) + (double)b * hw * c));
   hipLaunchKernelGGL(tsa_corr_bwd_ref_kernel, EDVR_GRID(total_ref), emb, (long long)emb_ns, (const float*)dcorr, d_emb_ref,
                      (long long)dr_ns, t, c / 8, hw, total_ref);
   if (prof) sr::prof_end(stream);
@@ -623,7 +610,7 @@ extern "C" int sr_tsa_gate_fwd_f32(const float* feat, int64_t feat_ns, const flo
   const long long per_img = (long long)cb * h * w * 2, total = per_img * n;
   SR_CHECK_ARG(grid_ok(total), "sr_tsa_gate_fwd_f32: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 121, cb * 8, cb * 8, n, h, w, 8.0 * total * 4, 4.0 * 4 * total * 4);
+  if (prof) sr::prof_rec(stream, 121, cb * 8, cb * 8, n, h, w, 8.0 * total * 4, 4.0 * 4 * total * 4);
   hipLaunchKernelGGL(tsa_gate_fwd_kernel, EDVR_GRID(total), feat, (long long)feat_ns, attn, (long long)attn_ns, attn_add,
                      (long long)add_ns, out, (long long)out_ns, per_img, total);
   if (prof) sr::prof_end(stream);
@@ -641,7 +628,7 @@ extern "C" int sr_tsa_gate_bwd_f32(const float* g, int64_t g_ns, const float* fe
   const long long per_img = (long long)cb * h * w * 2, total = per_img * n;
   SR_CHECK_ARG(grid_ok(total), "sr_tsa_gate_bwd_f32: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 122, cb * 8, cb * 8, n, h, w, 10.0 * total * 4, 4.0 * 5 * total * 4);
+  if (prof) sr::prof_rec(stream, 122, cb * 8, cb * 8, n, h, w, 10.0 * total * 4, 4.0 * 5 * total * 4);
   hipLaunchKernelGGL(tsa_gate_bwd_kernel, EDVR_GRID(total), g, (long long)g_ns, feat, (long long)feat_ns, attn, (long long)attn_ns,
                      d_feat, (long long)df_ns, d_attn, (long long)da_ns, per_img, total);
   if (prof) sr::prof_end(stream);

@@ -233,7 +233,7 @@ int pw_launch(const PwParams& p, int n, int groups, int cin, int cout, int h, in
   const bool prof = sr::prof_on();
   if (prof) {
     const double px = (double)n * h * w;
-    prof_rec(stream, 125, cin, cout, n, h, w, 2.0 * cin * cout * px, 2.0 * px * (cin + cout));
+    sr::prof_rec(stream, 125, cin, cout, n, h, w, 2.0 * cin * cout * px, 2.0 * px * (cin + cout));
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles * n), groups), dim3(256), lds, stream, p);
   if (prof) sr::prof_end(stream);
@@ -313,7 +313,7 @@ extern "C" int sr_cb16_subsample2_bf16(const void* x, int64_t x_ns, void* out, i
   const long long total = (long long)n * cb * ho * wo * 2;
   SR_CHECK_ARG(grid_ok(total), "sr_cb16_subsample2_bf16: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 126, cb * 16, cb * 16, n, h, w, 0.0, 4.0 * total * 8);
+  if (prof) sr::prof_rec(stream, 126, cb * 16, cb * 16, n, h, w, 0.0, 4.0 * total * 8);
   hipLaunchKernelGGL(cb16_subsample2_kernel, EDVR16_GRID(total), (const __bf16*)x, (long long)x_ns, (__bf16*)out, (long long)out_ns, cb,
                      h, w, ho, wo, total);
   if (prof) sr::prof_end(stream);
@@ -332,7 +332,7 @@ extern "C" int sr_pool3x3s2_fwd_bf16(const void* x, int64_t x_ns, void* out_max,
   const long long total = (long long)n * cb * ho * wo * 2;
   SR_CHECK_ARG(grid_ok(total), "sr_pool3x3s2_fwd_bf16: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 127, cb * 16, cb * 32, n, h, w, 17.0 * n * cb * 16 * ho * wo, 2.0 * n * cb * 16 * ((double)h * w + 2.0 * ho * wo));
+  if (prof) sr::prof_rec(stream, 127, cb * 16, cb * 32, n, h, w, 17.0 * n * cb * 16 * ho * wo, 2.0 * n * cb * 16 * ((double)h * w + 2.0 * ho * wo));
   hipLaunchKernelGGL(pool16_s2_fwd_kernel, EDVR16_GRID(total), (const __bf16*)x, (long long)x_ns, (__bf16*)out_max, (long long)max_ns,
                      (__bf16*)out_avg, (long long)avg_ns, cb, h, w, ho, wo, total);
   if (prof) sr::prof_end(stream);
@@ -352,7 +352,7 @@ extern "C" int sr_tsa_corr_fwd_bf16(const void* emb, int64_t emb_ns, const void*
                "sr_tsa_corr_fwd_bf16: an image stride is smaller than the image or not a multiple of 8");
   SR_CHECK_ARG(grid_ok(total), "sr_tsa_corr_fwd_bf16: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 128, c, c, b * t, h, w, 3.0 * total * c, 2.0 * total * 3.0 * c + 2.0 * b * hw * c + (prob ? 4.0 * total : 0.0));
+  if (prof) sr::prof_rec(stream, 128, c, c, b * t, h, w, 3.0 * total * c, 2.0 * total * 3.0 * c + 2.0 * b * hw * c + (prob ? 4.0 * total : 0.0));
   hipLaunchKernelGGL(tsa16_corr_kernel, EDVR16_GRID(total), (const __bf16*)emb, (long long)emb_ns, (const __bf16*)emb_ref,
                      (long long)ref_ns, (const __bf16*)aligned, (long long)al_ns, prob, (__bf16*)out, (long long)out_ns, t, c / 16, hw,
                      total);
@@ -371,7 +371,7 @@ extern "C" int sr_tsa_gate_fwd_bf16(const void* feat, int64_t feat_ns, const voi
                "sr_tsa_gate_fwd_bf16: an image stride is smaller than the image or not a multiple of 8");
   SR_CHECK_ARG(grid_ok(total), "sr_tsa_gate_fwd_bf16: grid too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 129, cb * 16, cb * 16, n, h, w, 8.0 * total * 8, 2.0 * total * 8 * 4);
+  if (prof) sr::prof_rec(stream, 129, cb * 16, cb * 16, n, h, w, 8.0 * total * 8, 2.0 * total * 8 * 4);
   hipLaunchKernelGGL(tsa16_gate_kernel, EDVR16_GRID(total), (const __bf16*)feat, (long long)feat_ns, (const __bf16*)attn,
                      (long long)attn_ns, (const __bf16*)attn_add, (long long)add_ns, (__bf16*)out, (long long)out_ns, per_img, total);
   if (prof) sr::prof_end(stream);

@@ -1,6 +1,6 @@
 // The backward of SpyNet's building blocks on gfx950 (include/sr_hip_flow_bwd.h).
 //
-// Data gradient: the forward's implicit-GEMM body (flow_device.h, conv7x7_body) with the mask epilogue compiled in, on a weight image
+// Data gradient: the forward's implicit-GEMM body (flow_device.h, conv_body) with the mask epilogue compiled in, on a weight image
 // that holds W flipped and transposed — a 7x7 convolution of dy.
 //
 // Weight gradient: D[cout][cin] += dy[cout][pixel] * x[pixel][cin] on v_mfma_f32_32x32x2_f32, the pixel pair as K.  All 49 taps of
@@ -23,19 +23,6 @@ using namespace flowdev;
 
 namespace {
 
-void prof_rec(hipStream_t stream, int id, int cin, int cout, int n, int h, int w, double flops, double bytes) {
-  sr_launch_record r = {};
-  r.kernel_id = id;
-  r.cin = cin;
-  r.cout = cout;
-  r.n = n;
-  r.h = h;
-  r.w = w;
-  r.flops = flops;
-  r.bytes = bytes;
-  sr::prof_begin(stream, r);
-}
-
 bool served(int cout, int cin) {
   return (cin == 8 && cout == 32) || (cin == 32 && cout == 64) || (cin == 64 && cout == 32) || (cin == 32 && cout == 16) ||
          (cin == 16 && cout == 2);
@@ -46,10 +33,10 @@ bool served(int cout, int cin) {
 template <int COT, int PT>
 __global__ __launch_bounds__(256, 2) void conv7x7_dgrad_f32_kernel(const C7MaskParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  conv7x7_body<COT, PT, true>(p, smem);
+  conv_body<COT, PT, true>(p, smem);
 }
 
-// The image of conv7x7_body for the transposed convolution: [dx group][dy block][tap row][tap column][COT][32 dx channels][8 dy
+// The image of conv_body for the transposed convolution: [dx group][dy block][tap row][tap column][COT][32 dx channels][8 dy
 // channels] of W[dy channel][dx channel][6 - tap row][6 - tap column], then one zero per padded dx channel.
 __global__ __launch_bounds__(256) void conv7x7_dgrad_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int cout, int cin,
                                                                  int COT, long long wfloats, long long total) {
@@ -422,7 +409,7 @@ extern "C" int sr_conv7x7_dgrad_pack_f32(const float* weight, int cout, int cin,
   SR_CHECK_ARG(sr::aligned16(packed), "sr_conv7x7_dgrad_pack_f32: packed must be 16-byte aligned");
   const long long wf = dgrad_weight_floats(cout, cin), total = wf + dgrad_zero_floats(cin);
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 171, cin, cout, 1, 7, 7, 0.0, 4.0 * (total + 49.0 * cin * cout));
+  if (prof) sr::prof_rec(stream, 171, cin, cout, 1, 7, 7, 0.0, 4.0 * (total + 49.0 * cin * cout));
   hipLaunchKernelGGL(conv7x7_dgrad_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, weight, packed, cout, cin,
                      dgrad_cot(cin), wf, total);
   if (prof) sr::prof_end(stream);
@@ -466,13 +453,13 @@ extern "C" int sr_conv7x7_dgrad_f32(const sr_conv7x7_dgrad_desc* d, void* stream
   p.tiles_y = sr::cdiv(d->h, inst == 1 ? 8 : 16);
   SR_CHECK_ARG((long long)p.tiles_x * p.tiles_y * d->n < (1ll << 31), "sr_conv7x7_dgrad_f32: grid too large");
   const void* kern = inst == 0 ? (const void*)conv7x7_dgrad_f32_kernel<1, 4> : (const void*)conv7x7_dgrad_f32_kernel<2, 2>;
-  const int lds = inst == 0 ? conv7x7_lds_bytes<1, 4>() : conv7x7_lds_bytes<2, 2>();
+  const int lds = inst == 0 ? conv_lds_bytes<1, 4>() : conv_lds_bytes<2, 2>();
   if (int rc = sr::ensure_dynamic_lds(kern, lds)) return rc;
   const dim3 grid((unsigned)(p.tiles_x * p.tiles_y * d->n), 1);
   const bool prof = sr::prof_on();
   if (prof) {
     const double px = (double)d->n * (double)hw;
-    prof_rec(stream, 169 + inst, d->cout, d->cin, d->n, d->h, d->w, 2.0 * 49.0 * d->cin * d->cout * px,
+    sr::prof_rec(stream, 169 + inst, d->cout, d->cin, d->n, d->h, d->w, 2.0 * 49.0 * d->cin * d->cout * px,
              4.0 * px * (dyb * 8.0 + d->cin * (d->mask ? 2 : 1)));
   }
   if (inst == 0)
@@ -529,12 +516,12 @@ extern "C" int sr_conv7x7_wgrad_f32(const sr_conv7x7_wgrad_desc* d, void* stream
   if (int rc = sr::ensure_dynamic_lds((const void*)conv7x7_wgrad_f32_kernel, kWgLds)) return rc;
   const bool prof = sr::prof_on();
   const double px = (double)d->n * (double)hw;
-  if (prof) prof_rec(stream, 172, d->cin, d->cout, d->n, d->h, d->w, 2.0 * 49.0 * d->cin * d->cout * px, 4.0 * px * (7.0 * d->cin + 7.0 * dyb * 8.0) + (double)need);
+  if (prof) sr::prof_rec(stream, 172, d->cin, d->cout, d->n, d->h, d->w, 2.0 * 49.0 * d->cin * d->cout * px, 4.0 * px * (7.0 * d->cin + 7.0 * dyb * 8.0) + (double)need);
   hipLaunchKernelGGL(conv7x7_wgrad_f32_kernel, dim3((unsigned)q.NP, (unsigned)(q.CT * q.IT * 7)), dim3(256), kWgLds, stream, p);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("sr_conv7x7_wgrad_f32 launch");
   const int wblocks = q.CT * q.IT * 49 * 4, bblocks = d->dbias ? sr::cdiv(d->cout, 256) : 0;
-  if (prof) prof_rec(stream, 173, d->cin, d->cout, d->n, d->h, d->w, (double)(q.wfloats + q.bfloats), (double)need + 8.0 * 49.0 * d->cin * d->cout);
+  if (prof) sr::prof_rec(stream, 173, d->cin, d->cout, d->n, d->h, d->w, (double)(q.wfloats + q.bfloats), (double)need + 8.0 * 49.0 * d->cin * d->cout);
   hipLaunchKernelGGL(conv7x7_wgrad_reduce_kernel, dim3((unsigned)(wblocks + bblocks)), dim3(256), 0, stream, (const float*)p.slab,
                      (const float*)p.bslab, d->dweight, d->dbias, q.NP, q.CT, q.IT, d->cout, d->cin, d->scale, d->accumulate, wblocks);
   if (prof) sr::prof_end(stream);
@@ -554,12 +541,12 @@ extern "C" int sr_spynet_level_input_bwd_f32(const float* supp, const float* up,
   SR_CHECK_ARG(((uintptr_t)d_up & 7u) == 0, "sr_spynet_level_input_bwd_f32: d_up must be 8-byte aligned");
   SR_CHECK_ARG(g_prev != g_res && g_prev != g_in && g_prev != up, "sr_spynet_level_input_bwd_f32: g_prev must not be an input");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 174, 8, 2, N, H, W, 50.0 * N * H * W, 4.0 * N * H * W * (12.0 + 24.0 + 2.0));
+  if (prof) sr::prof_rec(stream, 174, 8, 2, N, H, W, 50.0 * N * H * W, 4.0 * N * H * W * (12.0 + 24.0 + 2.0));
   hipLaunchKernelGGL(spynet_level_dup_kernel, dim3((unsigned)sr::cdiv(H * W, 256), 1, (unsigned)N), dim3(256), 0, stream, supp, up, g_in,
                      g_res, d_up, H, W);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("sr_spynet_level_input_bwd_f32 d_up launch");
-  if (prof) prof_rec(stream, 175, 2, 2, N, H / 2, W / 2, 4.0 * 9.0 * N * H * W, 4.0 * N * H * W * (2.0 + 2.0));
+  if (prof) sr::prof_rec(stream, 175, 2, 2, N, H / 2, W / 2, 4.0 * 9.0 * N * H * W, 4.0 * N * H * W * (2.0 + 2.0));
   hipLaunchKernelGGL(spynet_level_upT_kernel, dim3((unsigned)sr::cdiv((H / 2) * (W / 2), 256), 1, (unsigned)N), dim3(256), 0, stream,
                      (const float*)d_up, g_prev, H, W);
   if (prof) sr::prof_end(stream);
@@ -575,7 +562,7 @@ extern "C" int sr_resize_bilinear_adjoint_f32(const float* dy, float* dx, int pl
   SR_CHECK_ARG((long long)Hs * Ws < (1ll << 31) && (long long)Hd * Wd < (1ll << 31), "sr_resize_bilinear_adjoint_f32: image too large");
   SR_CHECK_ARG(dy != dx, "sr_resize_bilinear_adjoint_f32: dx must not be dy");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 176, 1, 1, planes, Hs, Ws, 3.0 * planes * Hd * Wd * 4.0, 4.0 * planes * ((double)Hs * Ws + (double)Hd * Wd));
+  if (prof) sr::prof_rec(stream, 176, 1, 1, planes, Hs, Ws, 3.0 * planes * Hd * Wd * 4.0, 4.0 * planes * ((double)Hs * Ws + (double)Hd * Wd));
   hipLaunchKernelGGL(resize_bilinear_adjoint_kernel, dim3((unsigned)sr::cdiv(Ws, 64), (unsigned)sr::cdiv(Hs, 4), (unsigned)planes), dim3(256),
                      0, stream, dy, dx, Hs, Ws, Hd, Wd);
   if (prof) sr::prof_end(stream);

@@ -25,25 +25,13 @@ using namespace flowdev;  // the conv body, the warp rule and the level coordina
 
 namespace {
 
-void prof_rec(hipStream_t stream, int id, int cin, int cout, int n, int h, int w, double flops, double bytes) {
-  sr_launch_record r = {};
-  r.kernel_id = id;
-  r.cin = cin;
-  r.cout = cout;
-  r.n = n;
-  r.h = h;
-  r.w = w;
-  r.flops = flops;
-  r.bytes = bytes;
-  sr::prof_begin(stream, r);
-}
-
 // ------------------------------------------------------------------------------------------------------------ conv 7x7
-// The body described above is conv7x7_body of flow_device.h, shared with the data gradient (flow_bwd_ops.hip); MASK = false here.
+// The body described above is conv_body of flow_device.h (KS = 7 from C7Params), shared with the data gradient
+// (flow_bwd_ops.hip) and TOFlow's 9x9 (tof_ops.hip); MASK = false here.
 template <int COT, int PT>
 __global__ __launch_bounds__(256, 2) void conv7x7_f32_kernel(const C7Params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  conv7x7_body<COT, PT, false>(p, smem);
+  conv_body<COT, PT, false>(p, smem);
 }
 
 // Few output channels (the last conv of a level: 16 -> 2) on v_mfma_f32_4x4x1_16b_f32, after conv_fewcout_f32_kernel: the 32x32
@@ -315,51 +303,10 @@ __global__ __launch_bounds__(256) void flow_warp_bwd_dflow_kernel(const float* _
 __global__ __launch_bounds__(256) void spynet_level_input_kernel(const float* __restrict__ ref, const float* __restrict__ supp,
                                                                  const float* __restrict__ flow_prev, float* __restrict__ out,
                                                                  float* __restrict__ up_out, int H, int W) {
-  const int HW = H * W;
-  const int pix = blockIdx.x * 256 + threadIdx.x;
-  if (pix >= HW) return;
-  const int n = blockIdx.z;
-  const int py = pix / W, px = pix - py * W;
-  float ux = 0.f, uy = 0.f;
-  if (flow_prev) {
-    const int Hp = H / 2, Wp = W / 2;
-    int ya, yb, xa, xb;
-    double fy, fx;
-    up_coord(py, H, Hp, ya, yb, fy);
-    up_coord(px, W, Wp, xa, xb, fx);
-    const float* f = flow_prev + (long long)n * Hp * Wp * 8;
-    const float2 v00 = *(const float2*)(f + ((long long)ya * Wp + xa) * 8), v01 = *(const float2*)(f + ((long long)ya * Wp + xb) * 8);
-    const float2 v10 = *(const float2*)(f + ((long long)yb * Wp + xa) * 8), v11 = *(const float2*)(f + ((long long)yb * Wp + xb) * 8);
-    ux = (float)(2.0 * ((1.0 - fy) * ((1.0 - fx) * v00.x + fx * v01.x) + fy * ((1.0 - fx) * v10.x + fx * v11.x)));
-    uy = (float)(2.0 * ((1.0 - fy) * ((1.0 - fx) * v00.y + fx * v01.y) + fy * ((1.0 - fx) * v10.y + fx * v11.y)));
-  }
-  int x0, y0;
-  float fx, fy;
-  bool gx_on, gy_on;
-  warp_coord(ux, uy, px, py, H, W, 1, x0, y0, fx, fy, gx_on, gy_on);
-  const Corners k = corners(x0, y0, H, W);
-  float o[8];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const long long plane = ((long long)n * 3 + c) * HW;
-    o[c] = ref[plane + pix];
-    const float* s = supp + plane;
-    o[3 + c] = blend(k.ok[0] ? s[k.off[0]] : 0.f, k.ok[1] ? s[k.off[1]] : 0.f, k.ok[2] ? s[k.off[2]] : 0.f,
-                     k.ok[3] ? s[k.off[3]] : 0.f, fx, fy);
-  }
-  o[6] = ux;
-  o[7] = uy;
-  float* dst = out + ((long long)n * HW + pix) * 8;
-  *(f32x4*)dst = f32x4{o[0], o[1], o[2], o[3]};
-  *(f32x4*)(dst + 4) = f32x4{o[4], o[5], o[6], o[7]};
-  float* du = up_out + ((long long)n * HW + pix) * 8;
-  *(f32x4*)du = f32x4{ux, uy, 0.f, 0.f};
-  *(f32x4*)(du + 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+  const long long img = (long long)blockIdx.z * 3 * (H * W);
+  level_input_body<1>(ref + img, supp + img, flow_prev, out, up_out, H, W);  // border padding
 }
 
-struct Norm3 {
-  float mean[3], stdv[3];
-};
 __global__ __launch_bounds__(256) void spynet_preprocess_kernel(const float* x, float* out, long long hw, const Norm3 nm) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= hw) return;
@@ -416,7 +363,7 @@ extern "C" int sr_conv7x7_pack_f32(const float* weight, const float* bias, int c
   SR_CHECK_ARG(sr::aligned16(packed), "sr_conv7x7_pack_f32: packed must be 16-byte aligned");
   const long long wf = conv7x7_weight_floats(cout, cin, inst), total = wf + conv7x7_bias_floats(cout, inst);
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 151, cin, cout, 1, 7, 7, 0.0, 4.0 * (total + 49.0 * cin * cout));
+  if (prof) sr::prof_rec(stream, 151, cin, cout, 1, 7, 7, 0.0, 4.0 * (total + 49.0 * cin * cout));
   hipLaunchKernelGGL(conv7x7_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, weight, bias, packed, cout, cin,
                      inst, wf, total);
   if (prof) sr::prof_end(stream);
@@ -463,13 +410,13 @@ extern "C" int sr_conv7x7_f32(const sr_conv7x7_desc* d, void* stream_) {
   SR_CHECK_ARG((long long)p.tiles_x * p.tiles_y * d->n < (1ll << 31), "sr_conv7x7_f32: grid too large");
   const void* kern = inst == 0 ? (const void*)conv7x7_f32_kernel<1, 4> : inst == 1 ? (const void*)conv7x7_f32_kernel<2, 2>
                                                                                      : (const void*)conv7x7_fewcout_f32_kernel;
-  const int lds = inst == 0 ? conv7x7_lds_bytes<1, 4>() : inst == 1 ? conv7x7_lds_bytes<2, 2>() : kFewLds;
+  const int lds = inst == 0 ? conv_lds_bytes<1, 4>() : inst == 1 ? conv_lds_bytes<2, 2>() : kFewLds;
   if (int rc = sr::ensure_dynamic_lds(kern, lds)) return rc;
   const dim3 grid((unsigned)(p.tiles_x * p.tiles_y * d->n), 1);
   const bool prof = sr::prof_on();
   if (prof) {
     const double px = (double)d->n * (double)hw;
-    prof_rec(stream, 148 + inst, d->cin, d->cout, d->n, d->h, d->w, 2.0 * 49.0 * d->cin * d->cout * px,
+    sr::prof_rec(stream, 148 + inst, d->cin, d->cout, d->n, d->h, d->w, 2.0 * 49.0 * d->cin * d->cout * px,
              4.0 * px * (d->cin + coutb * 8.0 * (d->res1 ? 2 : 1)));
   }
   if (inst == 0)
@@ -491,7 +438,7 @@ extern "C" int sr_flow_warp_f32(const float* x, const float* flow, float* out, i
   SR_CHECK_ARG(layout == SR_FLOW_NCHW || sr::aligned16(out), "sr_flow_warp_f32: a CB8 tensor must be 16-byte aligned");
   const dim3 grid((unsigned)sr::cdiv(H * W, 256), (unsigned)((C + 7) / 8), (unsigned)N);
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 152, C, C, N, H, W, 8.0 * N * C * H * W, 4.0 * N * H * W * (5.0 * C + 2.0));
+  if (prof) sr::prof_rec(stream, 152, C, C, N, H, W, 8.0 * N * C * H * W, 4.0 * N * H * W * (5.0 * C + 2.0));
   if (layout == SR_FLOW_CB8)
     hipLaunchKernelGGL(flow_warp_kernel<true>, grid, dim3(256), 0, stream, x, flow, out, C, H, W, padding);
   else
@@ -510,7 +457,7 @@ extern "C" int sr_flow_warp_bwd_f32(const float* x, const float* flow, const flo
   const bool prof = sr::prof_on();
   if (dx) {
     const dim3 grid((unsigned)sr::cdiv(H * W, 256), (unsigned)((C + 7) / 8), (unsigned)N);
-    if (prof) prof_rec(stream, 153, C, C, N, H, W, 8.0 * N * C * H * W, 4.0 * N * H * W * (5.0 * C + 2.0));
+    if (prof) sr::prof_rec(stream, 153, C, C, N, H, W, 8.0 * N * C * H * W, 4.0 * N * H * W * (5.0 * C + 2.0));
     if (layout == SR_FLOW_CB8)
       hipLaunchKernelGGL(flow_warp_bwd_dx_kernel<true>, grid, dim3(256), 0, stream, flow, g, dx, C, H, W, padding);
     else
@@ -520,7 +467,7 @@ extern "C" int sr_flow_warp_bwd_f32(const float* x, const float* flow, const flo
   }
   if (dflow) {
     const dim3 grid((unsigned)sr::cdiv(H * W, 256), 1, (unsigned)N);
-    if (prof) prof_rec(stream, 154, C, 2, N, H, W, 14.0 * N * C * H * W, 4.0 * N * H * W * (5.0 * C + 4.0));
+    if (prof) sr::prof_rec(stream, 154, C, 2, N, H, W, 14.0 * N * C * H * W, 4.0 * N * H * W * (5.0 * C + 4.0));
     if (layout == SR_FLOW_CB8)
       hipLaunchKernelGGL(flow_warp_bwd_dflow_kernel<true>, grid, dim3(256), 0, stream, x, flow, g, dflow, C, H, W, padding);
     else
@@ -542,7 +489,7 @@ extern "C" int sr_spynet_level_input_f32(const float* ref, const float* supp, co
   SR_CHECK_ARG(sr::aligned16(out) && sr::aligned16(up_out) && sr::aligned16(flow_prev),
                "sr_spynet_level_input_f32: CB8 tensors must be 16-byte aligned");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 155, 8, 8, N, H, W, 40.0 * N * H * W, 4.0 * N * H * W * (3.0 + 12.0 + 2.0 + 16.0));
+  if (prof) sr::prof_rec(stream, 155, 8, 8, N, H, W, 40.0 * N * H * W, 4.0 * N * H * W * (3.0 + 12.0 + 2.0 + 16.0));
   hipLaunchKernelGGL(spynet_level_input_kernel, dim3((unsigned)sr::cdiv(H * W, 256), 1, (unsigned)N), dim3(256), 0, stream, ref, supp,
                      flow_prev, out, up_out, H, W);
   if (prof) sr::prof_end(stream);
@@ -564,7 +511,7 @@ extern "C" int sr_spynet_preprocess_f32(const float* x, float* out, int N, int H
   const long long hw = (long long)H * W;
   SR_CHECK_ARG(hw < (1ll << 31), "sr_spynet_preprocess_f32: image too large");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 156, 3, 3, N, H, W, 6.0 * N * hw, 24.0 * N * hw);
+  if (prof) sr::prof_rec(stream, 156, 3, 3, N, H, W, 6.0 * N * hw, 24.0 * N * hw);
   hipLaunchKernelGGL(spynet_preprocess_kernel, dim3((unsigned)((hw + 255) / 256), 3, (unsigned)N), dim3(256), 0, stream, x, out, hw, nm);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("sr_spynet_preprocess_f32 launch");
@@ -579,7 +526,7 @@ extern "C" int sr_avgpool2x2_f32(const float* x, float* out, int planes, int H, 
   SR_CHECK_ARG((long long)H * W < (1ll << 31), "sr_avgpool2x2_f32: image too large");
   SR_CHECK_ARG(((uintptr_t)x & 7u) == 0, "sr_avgpool2x2_f32: x must be 8-byte aligned");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 157, 1, 1, planes, H / 2, W / 2, 1.0 * planes * H * W, 5.0 * planes * H * W);
+  if (prof) sr::prof_rec(stream, 157, 1, 1, planes, H / 2, W / 2, 1.0 * planes * H * W, 5.0 * planes * H * W);
   hipLaunchKernelGGL(avgpool2x2_kernel, dim3((unsigned)sr::cdiv((H / 2) * (W / 2), 256), 1, (unsigned)planes), dim3(256), 0, stream, x,
                      out, H, W);
   if (prof) sr::prof_end(stream);

@@ -277,19 +277,6 @@ constexpr int modconv_lds_bytes() {
 
 __host__ __device__ __forceinline__ int group_couts(int cout) { return (((cout + 31) / 32 * 32) % 64 == 0) ? 64 : 32; }
 
-void prof_rec(hipStream_t stream, int id, int cin, int cout, int n, int h, int w, double flops, double bytes) {
-  sr_launch_record r = {};
-  r.kernel_id = id;
-  r.cin = cin;
-  r.cout = cout;
-  r.n = n;
-  r.h = h;
-  r.w = w;
-  r.flops = flops;
-  r.bytes = bytes;
-  sr::prof_begin(stream, r);
-}
-
 template <int COT, int PT, int UP>
 int modconv_launch(const ModParams& p, int n, int groups, const sr_gfpgan_modconv_desc* d, hipStream_t stream) {
   constexpr int lds = modconv_lds_bytes<COT, PT, UP>();
@@ -301,7 +288,7 @@ int modconv_launch(const ModParams& p, int n, int groups, const sr_gfpgan_modcon
     const int cin = b->cin_real > 0 ? b->cin_real : b->cin_pad;
     const double px = (double)n * p.H * p.W;
     const double opx = UP ? (double)n * (2 * p.H + 1) * (2 * p.W + 1) : px;
-    prof_rec(stream, UP ? 93 : 92, cin, b->cout, n, p.H, p.W, 18.0 * cin * b->cout * px, 4.0 * (px * cin + opx * b->cout));
+    sr::prof_rec(stream, UP ? 93 : 92, cin, b->cout, n, p.H, p.W, 18.0 * cin * b->cout * px, 4.0 * (px * cin + opx * b->cout));
   }
   hipLaunchKernelGGL(kern, dim3(p.tiles_x * p.tiles_y * n, groups * (UP ? 4 : 1)), dim3(256), lds, stream, p);
   if (prof) sr::prof_end(stream);
@@ -586,7 +573,7 @@ extern "C" int sr_gfpgan_blur_up_f32(const float* t, int64_t t_img_stride, float
   p.tail = make_tail(tail, bias, cout, act_slope, alpha);
   const bool prof = sr::prof_on();
   const double opx = 4.0 * n * h * w;
-  if (prof) prof_rec(stream, 94, cout, cout, n, 2 * h, 2 * w, 32.0 * opx * cout, 4.0 * opx * cout * (2 + (tail->sft_scale ? 2 : 0)));
+  if (prof) sr::prof_rec(stream, 94, cout, cout, n, 2 * h, 2 * w, 32.0 * opx * cout, 4.0 * opx * cout * (2 + (tail->sft_scale ? 2 : 0)));
   hipLaunchKernelGGL(gfp_blur_up_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, stream, p);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("gfpgan blur_up launch");
@@ -621,7 +608,7 @@ extern "C" int sr_gfpgan_torgb_f32(const float* x, int64_t x_img_stride, const f
   p.wscale = wscale;
   const long long HW = (long long)h * w_;
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 95, c, 3, n, h, w_, 6.0 * n * HW * c, 4.0 * n * HW * (c * (x_next ? 2 : 1) + 3 + (skip ? 1 : 0)));
+  if (prof) sr::prof_rec(stream, 95, c, 3, n, h, w_, 6.0 * n * HW * c, 4.0 * n * HW * (c * (x_next ? 2 : 1) + 3 + (skip ? 1 : 0)));
   hipLaunchKernelGGL(gfp_torgb_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)n), dim3(256), 0, stream, p);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("gfpgan torgb launch");
@@ -651,7 +638,7 @@ extern "C" int sr_gfpgan_style_f32(const float* latent, int64_t latent_img_strid
     bytes += 4.0 * ((double)l.cin * nsf + (l.q ? (double)l.cout * l.cin : 0.0));
   }
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 91, nsf, n_layers, n, 1, 1, flops, bytes);
+  if (prof) sr::prof_rec(stream, 91, nsf, n_layers, n, 1, 1, flops, bytes);
   hipLaunchKernelGGL(gfp_style_kernel, dim3((unsigned)n_layers, (unsigned)n), dim3(256), 0, stream, p);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("gfpgan style launch");
@@ -662,7 +649,7 @@ extern "C" int sr_gfpgan_norm_style_f32(const float* x, float* y, int n, int nsf
   hipStream_t stream = (hipStream_t)stream_;
   SR_CHECK_ARG(x && y && n > 0 && n < 65536 && nsf > 0 && nsf <= 1024, "sr_gfpgan_norm_style_f32: bad argument");
   const bool prof = sr::prof_on();
-  if (prof) prof_rec(stream, 96, nsf, nsf, n, 1, 1, 3.0 * n * nsf, 8.0 * n * nsf);
+  if (prof) sr::prof_rec(stream, 96, nsf, nsf, n, 1, 1, 3.0 * n * nsf, 8.0 * n * nsf);
   hipLaunchKernelGGL(gfp_norm_kernel, dim3((unsigned)n), dim3(256), 0, stream, x, y, nsf);
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("gfpgan norm_style launch");

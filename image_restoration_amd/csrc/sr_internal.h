@@ -13,6 +13,19 @@ void set_error(const char* fmt, ...);
 bool prof_on();
 void prof_begin(hipStream_t s, const sr_launch_record& r);
 void prof_end(hipStream_t s);
+// prof_begin with the record spelt as arguments (host code; the caller has tested prof_on())
+inline void prof_rec(hipStream_t stream, int id, int cin, int cout, int n, int h, int w, double flops, double bytes) {
+  sr_launch_record r = {};
+  r.kernel_id = id;
+  r.cin = cin;
+  r.cout = cout;
+  r.n = n;
+  r.h = h;
+  r.w = w;
+  r.flops = flops;
+  r.bytes = bytes;
+  prof_begin(stream, r);
+}
 size_t rdb_dgrad_step_floats(int nf, int gc, int s);
 int rdb_pack_dgrad_step(const float* const w[5], int nf, int gc, int s, float scale5, float* out, hipStream_t stream);
 size_t rdb_dgrad_step_elems16(int nf, int gc, int s);

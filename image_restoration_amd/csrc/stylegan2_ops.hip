@@ -213,19 +213,6 @@ bool ufd_plan(int kh, int kw, int up_x, int up_y, int down_x, int down_y, UfdPla
   return q->lds <= kLdsBudget && (q->instance == 0 || q->th == 32);
 }
 
-void prof_rec(hipStream_t stream, int id, int cin, int cout, int n, int h, int w, double flops, double bytes) {
-  sr_launch_record r = {};
-  r.kernel_id = id;
-  r.cin = cin;
-  r.cout = cout;
-  r.n = n;
-  r.h = h;
-  r.w = w;
-  r.flops = flops;
-  r.bytes = bytes;
-  sr::prof_begin(stream, r);
-}
-
 template <int UP, int DOWN, int K>
 int ufd_launch(const UfdParams& p, const UfdPlan& plan, long long blocks, int n, hipStream_t stream) {
   auto kern = upfirdn2d_kernel<UP, DOWN, K>;
@@ -234,7 +221,7 @@ int ufd_launch(const UfdParams& p, const UfdPlan& plan, long long blocks, int n,
   if (prof) {
     const double po = (double)n * p.planes * p.out_h * p.out_w, pi = (double)n * p.planes * p.in_h * p.in_w;
     const double taps = (double)((p.kh + p.up_y - 1) / p.up_y) * ((p.kw + p.up_x - 1) / p.up_x);
-    prof_rec(stream, 131 + plan.instance, p.planes, p.planes, n, p.in_h, p.in_w, 2.0 * taps * po, 4.0 * (pi + po));
+    sr::prof_rec(stream, 131 + plan.instance, p.planes, p.planes, n, p.in_h, p.in_w, 2.0 * taps * po, 4.0 * (pi + po));
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), plan.lds, stream, p);
   if (prof) sr::prof_end(stream);
@@ -416,7 +403,7 @@ extern "C" int sr_fused_bias_act_f32(const float* x, const float* bias, const fl
   SR_CHECK_ARG(blocks > 0, "sr_fused_bias_act_f32: grid too large");
   const bool prof = sr::prof_on();
   const double total = (double)n * c * (double)inner;
-  if (prof) prof_rec(stream, 135, c, c, n, 1, (int)(inner < (1ll << 31) ? inner : 0), 3.0 * total, 4.0 * total * (ref ? 3 : 2));
+  if (prof) sr::prof_rec(stream, 135, c, c, n, 1, (int)(inner < (1ll << 31) ? inner : 0), 3.0 * total, 4.0 * total * (ref ? 3 : 2));
   if (v == 4)
     hipLaunchKernelGGL((fused_bias_act_kernel<4, false>), dim3((unsigned)blocks), dim3(256), 0, stream, x, bias, ref, out, (float*)nullptr, c,
                        (long long)inner, chunks, slope, scale);
@@ -457,7 +444,7 @@ extern "C" int sr_fused_bias_act_bwd_f32(const float* g, const float* out, float
   float* partial = (float*)workspace;
   const bool prof = sr::prof_on();
   const double total = (double)n * c * (double)inner;
-  if (prof) prof_rec(stream, 136, c, c, n, 1, (int)(inner < (1ll << 31) ? inner : 0), 3.0 * total, 4.0 * total * 3);
+  if (prof) sr::prof_rec(stream, 136, c, c, n, 1, (int)(inner < (1ll << 31) ? inner : 0), 3.0 * total, 4.0 * total * 3);
 #define SR_ACT_BWD(V, RED)                                                                                                          \
   hipLaunchKernelGGL((fused_bias_act_kernel<V, RED>), dim3((unsigned)blocks), dim3(256), 0, stream, g, (const float*)nullptr, out, gx, \
                      partial, c, (long long)inner, chunks, slope, scale)
@@ -470,7 +457,7 @@ extern "C" int sr_fused_bias_act_bwd_f32(const float* g, const float* out, float
   if (prof) sr::prof_end(stream);
   SR_CHECK_LAUNCH("fused_bias_act_bwd launch");
   if (!gbias) return SR_OK;
-  if (prof) prof_rec(stream, 137, c, c, n, 1, (int)chunks, (double)blocks, 4.0 * ((double)blocks + c));
+  if (prof) sr::prof_rec(stream, 137, c, c, n, 1, (int)chunks, (double)blocks, 4.0 * ((double)blocks + c));
   hipLaunchKernelGGL(fused_bias_act_finish_kernel, dim3((unsigned)sr::cdiv(c, 4)), dim3(256), 0, stream, (const float*)partial, gbias, n, c,
                      chunks);
   if (prof) sr::prof_end(stream);

@@ -1523,29 +1523,53 @@ def conv7x7_instance(cout, cin):
     return inst
 
 
-class PackedConv7x7:
-    """MFMA operand image of one 7x7 conv of SpyNet: mode 0 the forward image (weights, then bias) — sr_conv7x7_pack_f32;
-    mode 1 the data-gradient image (the weights flipped and transposed, no bias) — sr_conv7x7_dgrad_pack_f32."""
+class _PackedConvTaps:
+    """What PackedConv7x7 and PackedConv9x9 share: the device, mode, shape and bias checks, ``cout`` / ``cin`` / ``mode`` and the
+    one image ``w`` (weights in operand order, then the bias).  A subclass states ``ksize``, the ``modes`` it serves, its size
+    query (``_packed_floats``, which refuses a (cin, cout) pair that is not served) and its pack launch (``_pack``)."""
+    ksize, modes = None, ()
 
     def __init__(self, weight, bias=None, mode=0):
-        _need_cuda(weight, 'PackedConv7x7')
-        _arg(mode in (0, 1), f'PackedConv7x7: mode {mode} is not supported; supported: 0 (forward), 1 (data gradient)')
-        _arg(mode == 0 or bias is None, 'PackedConv7x7: the data-gradient image has no bias')
-        self.mode = mode
-        _arg(weight.dim() == 4 and tuple(weight.shape[2:]) == (7, 7) and weight.dtype == torch.float32,
-             f'PackedConv7x7: needs an fp32 [cout, cin, 7, 7] weight, got {weight.dtype} {tuple(weight.shape)}')
-        _arg(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (weight.size(0),)), 'PackedConv7x7: bias does not fit')
+        name, k = type(self).__name__, self.ksize
+        _need_cuda(weight, name)
+        _arg(mode in range(len(self.modes)),
+             f'{name}: mode {mode} is not supported; supported: ' + ', '.join(f'{i} ({m})' for i, m in enumerate(self.modes)))
+        _arg(mode == 0 or bias is None, f'{name}: the data-gradient image has no bias')
+        _arg(weight.dim() == 4 and tuple(weight.shape[2:]) == (k, k) and weight.dtype == torch.float32,
+             f'{name}: needs an fp32 [cout, cin, {k}, {k}] weight, got {weight.dtype} {tuple(weight.shape)}')
+        _arg(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (weight.size(0),)), f'{name}: bias does not fit')
         weight = weight.detach().contiguous()
         bias = None if bias is None else bias.detach().contiguous()
+        self.mode = mode
         self.cout, self.cin = weight.shape[:2]
+        self.w = torch.empty(self._packed_floats(_lib.load()), dtype=torch.float32, device=weight.device)
+        self._pack(weight.device, weight.data_ptr(), _p(bias))
+
+
+class PackedConv7x7(_PackedConvTaps):
+    """MFMA operand image of one 7x7 conv of SpyNet: mode 0 the forward image (weights, then bias) — sr_conv7x7_pack_f32;
+    mode 1 the data-gradient image (the weights flipped and transposed, no bias) — sr_conv7x7_dgrad_pack_f32."""
+    ksize, modes = 7, ('forward', 'data gradient')
+
+    def _packed_floats(self, lib):
         self.instance = conv7x7_instance(self.cout, self.cin)     # refuses a pair that is not served
-        if mode == 1:
-            self.instance = _lib.load().sr_conv7x7_dgrad_instance(self.cout, self.cin)
-            self.w = torch.empty(_lib.load().sr_conv7x7_dgrad_packed_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
-            _launch_arg('sr_conv7x7_dgrad_pack_f32', weight.device, weight.data_ptr(), self.cout, self.cin, self.w.data_ptr())
-            return
-        self.w = torch.empty(_lib.load().sr_conv7x7_packed_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
-        _launch_arg('sr_conv7x7_pack_f32', weight.device, weight.data_ptr(), _p(bias), self.cout, self.cin, self.w.data_ptr())
+        if self.mode == 0:
+            return lib.sr_conv7x7_packed_floats(self.cout, self.cin)
+        self.instance = lib.sr_conv7x7_dgrad_instance(self.cout, self.cin)
+        return lib.sr_conv7x7_dgrad_packed_floats(self.cout, self.cin)
+
+    def _pack(self, dev, weight, bias):
+        if self.mode == 0:
+            _launch_arg('sr_conv7x7_pack_f32', dev, weight, bias, self.cout, self.cin, self.w.data_ptr())
+        else:
+            _launch_arg('sr_conv7x7_dgrad_pack_f32', dev, weight, self.cout, self.cin, self.w.data_ptr())
+
+
+def _conv_taps_desc(d, src, pc, out, relu):
+    """The fields a struct sr_conv7x7_desc and a struct sr_tof_conv9x9_desc have in common."""
+    d.in_, d.in_img_stride, d.cin, d.cout, d.n, d.h, d.w = src.ptr, src.img_stride, pc.cin, pc.cout, src.n, src.h, src.w
+    d.packed, d.out, d.out_img_stride, d.relu = pc.w.data_ptr(), out.ptr, out.img_stride, int(bool(relu))
+    return d
 
 
 def conv7x7(src, pc, out=None, *, relu=False, res1=None):
@@ -1557,9 +1581,7 @@ def conv7x7(src, pc, out=None, *, relu=False, res1=None):
     cob = (pc.cout + 7) // 8
     _arg((out.n, out.h, out.w) == (src.n, src.h, src.w) and out.cbn >= cob, 'conv7x7: output window does not fit')
     _arg(res1 is None or ((res1.n, res1.h, res1.w) == (src.n, src.h, src.w) and res1.cbn >= cob), 'conv7x7: res1 does not fit')
-    d = _lib.Conv7x7Desc()
-    d.in_, d.in_img_stride, d.cin, d.cout, d.n, d.h, d.w = src.ptr, src.img_stride, pc.cin, pc.cout, src.n, src.h, src.w
-    d.packed, d.out, d.out_img_stride, d.relu = pc.w.data_ptr(), out.ptr, out.img_stride, int(bool(relu))
+    d = _conv_taps_desc(_lib.Conv7x7Desc(), src, pc, out, relu)
     if res1 is not None:
         d.res1, d.res1_img_stride = res1.ptr, res1.img_stride
     _launch_arg('sr_conv7x7_f32', src.device, C.byref(d))
@@ -1988,24 +2010,18 @@ def vsr_trunk_bwd(cfg, dblob, src, out, stack, dout, din, targets, accumulate=Fa
 CONV9X9_SHAPES = ((21, 64), (64, 64))   # (cin, cout) of TOFlow's conv_1 and conv_2
 
 
-class PackedConv9x9:
+class PackedConv9x9(_PackedConvTaps):
     """MFMA operand image of one 9x9 conv of TOFlow (weights in operand order, then the bias) — sr_tof_conv9x9_pack_f32.
     ``mode`` exists for HipGenerator.packed: only 0 (forward) is served."""
+    ksize, modes = 9, ('forward',)
 
-    def __init__(self, weight, bias=None, mode=0):
-        _need_cuda(weight, 'PackedConv9x9')
-        _arg(mode == 0, f'PackedConv9x9: mode {mode} is not supported; supported: 0 (forward)')
-        _arg(weight.dim() == 4 and tuple(weight.shape[2:]) == (9, 9) and weight.dtype == torch.float32,
-             f'PackedConv9x9: needs an fp32 [cout, cin, 9, 9] weight, got {weight.dtype} {tuple(weight.shape)}')
-        _arg(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (weight.size(0),)), 'PackedConv9x9: bias does not fit')
-        weight = weight.detach().contiguous()
-        bias = None if bias is None else bias.detach().contiguous()
-        self.mode = 0
-        self.cout, self.cin = weight.shape[:2]
-        nfloats = _lib.load().sr_tof_conv9x9_packed_floats(self.cout, self.cin)
+    def _packed_floats(self, lib):
+        nfloats = lib.sr_tof_conv9x9_packed_floats(self.cout, self.cin)
         _arg(nfloats > 0, f'conv9x9: (cin, cout) = ({self.cin}, {self.cout}) is not supported; supported: {CONV9X9_SHAPES}')
-        self.w = torch.empty(nfloats, dtype=torch.float32, device=weight.device)
-        _launch_arg('sr_tof_conv9x9_pack_f32', weight.device, weight.data_ptr(), _p(bias), self.cout, self.cin, self.w.data_ptr())
+        return nfloats
+
+    def _pack(self, dev, weight, bias):
+        _launch_arg('sr_tof_conv9x9_pack_f32', dev, weight, bias, self.cout, self.cin, self.w.data_ptr())
 
 
 def conv9x9(src, pc, out=None, *, relu=False):
@@ -2015,10 +2031,7 @@ def conv9x9(src, pc, out=None, *, relu=False):
     if out is None:
         out = CB8.empty(src.n, pc.cout, src.h, src.w, src.device)
     _arg((out.n, out.h, out.w) == (src.n, src.h, src.w) and out.cbn >= pc.cout // 8, 'conv9x9: output window does not fit')
-    d = _lib.TofConv9x9Desc()
-    d.in_, d.in_img_stride, d.cin, d.cout, d.n, d.h, d.w = src.ptr, src.img_stride, pc.cin, pc.cout, src.n, src.h, src.w
-    d.packed, d.out, d.out_img_stride, d.relu = pc.w.data_ptr(), out.ptr, out.img_stride, int(bool(relu))
-    _launch_arg('sr_tof_conv9x9_f32', src.device, C.byref(d))
+    _launch_arg('sr_tof_conv9x9_f32', src.device, C.byref(_conv_taps_desc(_lib.TofConv9x9Desc(), src, pc, out, relu)))
     return out
 
 

@@ -1,6 +1,6 @@
 """archs/hip_generator.py on the host (no GPU: the weight images and the weight-gradient launches are stubs): the per-network
-weight-image cache of HipGenerator.packed, the shared forward's refusals, the parameter order the FlatAdam arena relies on, and
-GradRouter's routing of parameter gradients."""
+weight-image cache of HipGenerator.packed and the cache of derived tensors under it (HipGenerator.derived), the shared forward's
+refusals, the parameter order the FlatAdam arena relies on, and GradRouter's routing of parameter gradients."""
 from types import SimpleNamespace
 
 import pytest
@@ -8,6 +8,7 @@ import torch
 
 import image_restoration_amd as ira
 from image_restoration_amd import _lib, hip_ops
+from image_restoration_amd.archs.arch_util import bn_prologue
 from image_restoration_amd.archs.hip_generator import GradRouter, HipGenerator
 
 NETS = {
@@ -109,6 +110,107 @@ def test_packed_refuses_other_dtypes_by_the_class_name(built, kind):
     with pytest.raises(_lib.SrHipError, match=f'{kind} parameters must be fp32'):
         net.packed(_first_conv(net))
     assert not built
+
+
+def _derived_setup():
+    """A bare HipGenerator that owns three CPU tensors, and a ``get()`` that asks for what is derived from them; ``calls``
+    counts the builds."""
+    net = HipGenerator()
+    net.a = torch.nn.Parameter(torch.ones(3))
+    net.register_buffer('b', torch.zeros(2))
+    net.register_buffer('c', torch.full((1,), 2.0))
+    calls = []
+
+    def build():
+        calls.append(1)
+        return SimpleNamespace(total=float(net.a.detach().sum() + net.b.sum() + net.c.sum()))
+
+    return net, calls, lambda extra=1e-5: net.derived('sum', (net.a, net.b, net.c), extra, build)
+
+
+def test_derived_hits_on_an_unchanged_signature():
+    net, calls, get = _derived_setup()
+    first = get()
+    assert first.total == 5.0 and get() is first and get() is first and len(calls) == 1
+    assert set(net._packs) == {'sum'}
+    assert get(1e-3) is not first and len(calls) == 2          # ``extra`` is part of the signature
+    other = net.derived('other', (net.a,), None, lambda: object())
+    assert net.derived('other', (net.a,), None, lambda: object()) is other and set(net._packs) == {'sum', 'other'}
+
+
+@pytest.mark.parametrize('name', ['a', 'b', 'c'])
+def test_derived_rebuilds_after_an_in_place_edit_of_any_tensor(name):
+    net, calls, get = _derived_setup()
+    first = get()
+    with torch.no_grad():
+        getattr(net, name).add_(1)
+    second = get()
+    assert second is not first and second.total == first.total + getattr(net, name).numel() and len(calls) == 2
+    assert get() is second and len(calls) == 2
+    t = getattr(net, name)
+    t.data = t.data.clone()                                    # new storage, same values
+    assert get() is not second and len(calls) == 3
+
+
+def test_derived_rebuilds_after_invalidate_packed():
+    net, calls, get = _derived_setup()
+    first = get()
+    net.invalidate_packed()
+    second = get()
+    assert second is not first and len(calls) == 2 and get() is second and len(calls) == 2
+
+
+@pytest.mark.parametrize('name', ['a', 'b', 'c'])
+def test_derived_rebuilds_after_a_write_behind_the_version_counter(name):
+    """FlatAdam writes through raw pointers and bumps the tensor's ``_sr_epoch`` cell: storage and ``_version`` stay."""
+    net, calls, get = _derived_setup()
+    t = getattr(net, name)
+    cell = [0]
+    t._sr_epoch = cell
+    first = get()
+    assert get() is first and len(calls) == 1                  # epoch 0 is what a tensor without a cell counts as
+    before = (t.data_ptr(), t._version)
+    t.data.add_(1)                                             # .data: no version bump
+    cell[0] += 1
+    assert (t.data_ptr(), t._version) == before
+    second = get()
+    assert second is not first and second.total == first.total + t.numel() and len(calls) == 2
+    assert get() is second and len(calls) == 2
+
+
+def test_derived_is_empty_after_apply():
+    net, calls, get = _derived_setup()
+    get()
+    net.derived('other', (net.a,), None, lambda: object())
+    net.double().float()
+    assert net._packs == {}
+    get()
+    assert len(calls) == 2 and set(net._packs) == {'sum'}
+    with pytest.raises(_lib.SrHipError, match='HipGenerator parameters must be fp32'):
+        net.double().derived('sum', (net.a,), None, lambda: calls.append(1))
+    assert len(calls) == 2 and net._packs == {}
+
+
+def test_the_networks_derived_tensors_see_a_write_behind_the_version_counter():
+    """The BatchNorm prologue of DUF and the host (mean, std) of SpyNet and TOFlow are written on ``derived``."""
+    duf = ira.build_network(dict(type='DUF', scale=2, num_layer=16)).eval()
+    bn = duf.bn3d2
+    scale, shift = duf.prologue(bn)
+    assert duf.prologue(bn)[0] is scale and torch.equal(scale, bn_prologue(bn)[0])
+    cell = [0]
+    bn.running_var._sr_epoch = cell
+    assert duf.prologue(bn)[0] is scale
+    bn.running_var.data.mul_(4)
+    cell[0] += 1
+    assert torch.equal(duf.prologue(bn)[0], bn_prologue(bn)[0]) and not torch.equal(duf.prologue(bn)[0], scale)
+    for kind in ('SpyNet', 'TOFlow'):
+        net = ira.build_network(dict(type=kind)).eval()
+        assert type(net)._norm_host is HipGenerator._norm_host and not hasattr(net, '_norm')
+        mean, std = net._norm_host()
+        assert net._norm_host()[0] is mean and mean == net.mean.flatten().tolist() and std == net.std.flatten().tolist()
+        with torch.no_grad():
+            net.std.mul_(2)
+        assert net._norm_host()[1] == [2 * s for s in std] and net._norm_host()[0] is not mean
 
 
 def test_parameter_order_of_the_conv_only_networks():
