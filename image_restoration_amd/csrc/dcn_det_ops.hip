@@ -1,6 +1,6 @@
 // The deterministic input gradient of the modulated deformable convolution on gfx950, fp32 on CB8 (include/sr_hip_dcn_det.h): the dx
 // of dcn_ops.hip's dcn_bwd_data_kernel with the sum taken in 64-bit integers, so that it does not depend on the order in which the
-// adds arrive.  doffset and dmask come from that kernel itself, launched without dx.
+// adds arrive (fixed_sum.h).  doffset and dmask come from that kernel itself, launched without dx.
 //
 // Three kernels per call.  The scale kernel takes, per image, the unsigned maxima of the sign-cleared bit patterns of dcol and of the
 // mask (one wave reduction, then one integer atomic per wave: order-free).  The scatter kernel has one lane per element of dcol — a
@@ -13,6 +13,8 @@
 #include <algorithm>
 
 #include "../../include/sr_hip_dcn_det.h"
+#include "dcn_device.h"
+#include "fixed_sum.h"
 #include "sr_internal.h"
 
 namespace {
@@ -28,13 +30,8 @@ struct DcnDetParams {
   int H, W, cin_blocks, bpg, dg, logit, L;
 };
 
-constexpr unsigned kInfBits = 0x7f800000u;
-
-// ilogb(M) + 1 from the bits of M (finite, not zero; a denormal has its exponent from its leading bit)
-__device__ __forceinline__ int exp_of(unsigned mbits) {
-  const int ex = (int)(mbits >> 23);
-  return (ex ? ex - 127 : (31 - __clz((int)mbits)) - 149) + 1;
-}
+using fixsum::exp_of;
+using fixsum::kInfBits;
 
 // What the image's two scale words say: 0 = dx is zero, 1 = dx is NaN, 2 = sum with the shift k
 __device__ __forceinline__ int scale_state(unsigned md, unsigned mm, int logit, int L, int& k) {
@@ -45,48 +42,13 @@ __device__ __forceinline__ int scale_state(unsigned md, unsigned mm, int logit, 
   return 2;
 }
 
-// The sampling position of dcn_ops.hip (bilinear_at there, word for word: the cell, the fractions and the `inside` test of the
-// forward), without the weights, which this file forms in float64.
-struct Cell {
-  int hl, wl;
-  float lh, lw;
-  bool v1, v2, v3, v4;
-};
-
-__device__ __forceinline__ Cell cell_at(float h_im, float w_im, int H, int W) {
-  Cell b;
-  const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-  if (!inside) h_im = w_im = 0.f;  // also NaN and huge offsets: nothing below is used
-  const float fh = floorf(h_im), fw = floorf(w_im);
-  b.hl = (int)fh;
-  b.wl = (int)fw;
-  b.lh = h_im - fh;
-  b.lw = w_im - fw;
-  const bool t = b.hl >= 0, bo = b.hl + 1 <= H - 1, l = b.wl >= 0, r = b.wl + 1 <= W - 1;
-  b.v1 = inside && t && l;
-  b.v2 = inside && t && r;
-  b.v3 = inside && bo && l;
-  b.v4 = inside && bo && r;
-  return b;
-}
-
-__device__ __forceinline__ float channel_at(const float* t, long long HW, long long pix, int c) {
-  return t[((long long)(c >> 3) * HW + pix) * 8 + (c & 7)];
-}
-
-__device__ __forceinline__ float mask_value(float m, int logit) { return logit ? 1.f / (1.f + expf(-m)) : m; }  // dcn_ops.hip's
-
 // grid (blocks, n), 256 threads: a grid-stride walk over the image's dcol (contiguous, 16 bytes a lane), then over its mask blocks
 __global__ __launch_bounds__(256) void deform_det_scale_kernel(const DcnDetParams p) {
   const int n = blockIdx.y;
   const long long HW = (long long)p.H * p.W;
   const long long quads = HW * 2 * 9 * p.cin_blocks;
-  const uint4* src = (const uint4*)(p.dcol + (long long)n * quads * 4);
-  unsigned md = 0, mm = 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < quads; i += (long long)gridDim.x * 256) {
-    const uint4 v = src[i];
-    md = max(max(md, v.x & 0x7fffffffu), max(v.y & 0x7fffffffu, max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
-  }
+  const unsigned md = fixsum::walk_max((const uint4*)(p.dcol + (long long)n * quads * 4), quads);
+  unsigned mm = 0;
   const int mch = 9 * p.dg;  // the pad channels of the last mask block are not the mask's
   const long long melems = (long long)((mch + 7) / 8) * HW * 8;
   const unsigned* mp = (const unsigned*)(p.msk + (long long)n * p.msk_ns);
@@ -97,15 +59,9 @@ __global__ __launch_bounds__(256) void deform_det_scale_kernel(const DcnDetParam
       if (!p.logit || v > kInfBits) mm = max(mm, v);
     }
   }
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    md = max(md, (unsigned)__shfl_xor((int)md, s));
-    mm = max(mm, (unsigned)__shfl_xor((int)mm, s));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (md) atomicMax(p.scale + 2 * n, md);
-    if (mm) atomicMax(p.scale + 2 * n + 1, mm);
-  }
+  const unsigned wd = fixsum::wave_max(md), wm = fixsum::wave_max(mm);
+  fixsum::publish_max(p.scale + 2 * n, wd);
+  fixsum::publish_max(p.scale + 2 * n + 1, wm);
 }
 
 // grid (ceil(HW / 32), 9 * cin_blocks, n), 256 threads: thread = 8 * (pixel of the workgroup) + channel of the block;
@@ -122,21 +78,20 @@ __global__ __launch_bounds__(256) void deform_det_scatter_kernel(const DcnDetPar
   const int y = pix / p.W, x = pix - y * p.W;
   const float* off_n = p.off + (long long)n * p.off_ns;
   const int oc = 18 * g + 2 * tap;
-  const float oh = channel_at(off_n, HW, pix, oc), ow = channel_at(off_n, HW, pix, oc + 1);
-  const float m = mask_value(channel_at(p.msk + (long long)n * p.msk_ns, HW, pix, 9 * g + tap), p.logit);
-  const int ti = tap / 3, tj = tap - 3 * ti;
-  const Cell b = cell_at((float)(y - 1 + ti) + oh, (float)(x - 1 + tj) + ow, p.H, p.W);
+  const float oh = dcndev::channel_at(off_n, HW, pix, oc), ow = dcndev::channel_at(off_n, HW, pix, oc + 1);
+  const float m = dcndev::mask_value(dcndev::channel_at(p.msk + (long long)n * p.msk_ns, HW, pix, 9 * g + tap), p.logit);
+  const dcndev::Bilinear b = dcndev::tap_position(y, x, tap, oh, ow, p.H, p.W);  // the forward's position, bit for bit
   const float d = p.dcol[(((long long)n * 9 * p.cin_blocks + tb) * HW + pix) * 8 + e];
   const double dm = (double)d * (double)m;  // exact
-  const double lh = b.lh, lw = b.lw, hh = 1.0 - lh, hw = 1.0 - lw;
+  const double lh = b.lh, lw = b.lw, hh = 1.0 - lh, hw = 1.0 - lw;  // not b.hh / b.hw, which are rounded to fp32
   const double w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
   // the corner's element; formed only from a valid corner's (hl, wl)
   unsigned long long* ap = (unsigned long long*)p.acc + ((long long)n * p.cin_blocks + cb) * HW * 8 + e;
   const long long corner = ((long long)b.hl * p.W + b.wl) * 8, down = (long long)p.W * 8;
-  if (b.v1 && w1 != 0.0) atomicAdd(ap + corner, (unsigned long long)llrint(ldexp(dm * w1, k)));  // |t| <= 2^(61 - L)
-  if (b.v2 && w2 != 0.0) atomicAdd(ap + corner + 8, (unsigned long long)llrint(ldexp(dm * w2, k)));
-  if (b.v3 && w3 != 0.0) atomicAdd(ap + corner + down, (unsigned long long)llrint(ldexp(dm * w3, k)));
-  if (b.v4 && w4 != 0.0) atomicAdd(ap + corner + down + 8, (unsigned long long)llrint(ldexp(dm * w4, k)));
+  if (b.v1 && w1 != 0.0) fixsum::add_term(ap + corner, dm * w1, k);  // |t| <= 2^(61 - L)
+  if (b.v2 && w2 != 0.0) fixsum::add_term(ap + corner + 8, dm * w2, k);
+  if (b.v3 && w3 != 0.0) fixsum::add_term(ap + corner + down, dm * w3, k);
+  if (b.v4 && w4 != 0.0) fixsum::add_term(ap + corner + down + 8, dm * w4, k);
 }
 
 // grid (ceil(cin * HW / 256), n), 256 threads: one element of dx a lane
@@ -149,25 +104,24 @@ __global__ __launch_bounds__(256) void deform_det_finish_kernel(const DcnDetPara
   const int state = scale_state(p.scale[2 * n], p.scale[2 * n + 1], p.logit, p.L, k);
   float v = 0.f;
   if (state == 1) v = __builtin_nanf("");
-  if (state == 2) v = (float)ldexp((double)p.acc[(long long)n * img + i], -k);
+  if (state == 2) v = (float)fixsum::scaled_back(p.acc[(long long)n * img + i], k);
   p.dx[(long long)n * p.dx_ns + i] = v;
 }
 
-// accumulator bytes and scale bytes, each rounded up to 256; false for a bad shape
-bool det_sizes(int n, int cin, int h, int w, size_t* acc_bytes, size_t* scale_bytes) {
+// the carve of the workspace; false for a bad shape
+bool det_sizes(int n, int cin, int h, int w, fixsum::Carve* c) {
   if (n <= 0 || n > 65535 || cin <= 0 || cin % 8 || 9 * (cin / 8) > 65535 || h <= 0 || w <= 0) return false;
   const long long hw = (long long)h * w;  // < 2^62
   if (hw >= (1ll << 32) || 9ll * cin * hw * 4 >= (1ll << 32)) return false;  // the atomic entry point's "image too large"
-  *acc_bytes = sr::align_up((size_t)8 * (size_t)n * (size_t)cin * (size_t)hw, 256);  // < 8 * 2^16 * 2^27
-  *scale_bytes = sr::align_up((size_t)8 * (size_t)n, 256);
+  *c = fixsum::carve((size_t)8 * (size_t)n * (size_t)cin * (size_t)hw, (size_t)8 * (size_t)n);  // < 8 * 2^16 * 2^27
   return true;
 }
 
 }  // namespace
 
 extern "C" size_t sr_dcn_bwd_data_det_workspace_bytes(int n, int cin, int h, int w) {
-  size_t a = 0, s = 0;
-  return det_sizes(n, cin, h, w, &a, &s) ? a + s : 0;
+  fixsum::Carve c;
+  return det_sizes(n, cin, h, w, &c) ? c.total() : 0;
 }
 
 extern "C" int sr_dcn_bwd_data_det_f32(const sr_dcn_bwd_det_desc* dd, void* stream_) {
@@ -185,26 +139,20 @@ extern "C" int sr_dcn_bwd_data_det_f32(const sr_dcn_bwd_det_desc* dd, void* stre
   SR_CHECK_ARG(((uintptr_t)b->dx | (uintptr_t)b->doffset | (uintptr_t)b->dmask) % 16 == 0, "%s: pointers must be 16-byte aligned", who);
   if (!b->dx && !b->doffset) return SR_OK;
   const long long hw = (long long)d->h * d->w;
-  size_t acc_bytes = 0, scale_bytes = 0;
   if (b->dx) {
-    SR_CHECK_ARG(det_sizes(d->n, d->cin, d->h, d->w, &acc_bytes, &scale_bytes), "%s: bad shape n=%d cin=%d h=%d w=%d", who, d->n, d->cin,
-                 d->h, d->w);
+    fixsum::Carve c;
+    SR_CHECK_ARG(det_sizes(d->n, d->cin, d->h, d->w, &c), "%s: bad shape n=%d cin=%d h=%d w=%d", who, d->n, d->cin, d->h, d->w);
     SR_CHECK_ARG(b->dx_img_stride % 4 == 0, "%s: the image stride of dx must be a multiple of 4 floats", who);
     SR_CHECK_ARG(d->n == 1 || b->dx_img_stride >= (long long)d->cin * hw, "%s: the image stride of dx is smaller than the image", who);
     SR_CHECK_ARG((const float*)b->dx != d->x && (const float*)b->dx != b->dcol, "%s: dx must not be a source", who);
-    SR_CHECK_ARG(((uintptr_t)dd->workspace & 255u) == 0, "%s: the workspace must be 256-byte aligned", who);
-    if (!dd->workspace || dd->workspace_bytes < acc_bytes + scale_bytes) {
-      sr::set_error("%s: workspace of %zu bytes, %zu needed (sr_dcn_bwd_data_det_workspace_bytes)", who,
-                    dd->workspace ? dd->workspace_bytes : (size_t)0, acc_bytes + scale_bytes);
-      return SR_ENOSPACE;
-    }
+    if (int rc = fixsum::check_and_clear(who, "sr_dcn_bwd_data_det_workspace_bytes", dd->workspace, dd->workspace_bytes, c, stream)) return rc;
     DcnDetParams p = {};
     p.dcol = b->dcol;
     p.off = d->offset;
     p.msk = d->mask;
     p.dx = b->dx;
     p.acc = (long long*)dd->workspace;
-    p.scale = (unsigned*)((char*)dd->workspace + acc_bytes);
+    p.scale = (unsigned*)((char*)dd->workspace + c.acc_bytes);
     p.off_ns = d->offset_img_stride;
     p.msk_ns = d->mask_img_stride;
     p.dx_ns = b->dx_img_stride;
@@ -214,39 +162,22 @@ extern "C" int sr_dcn_bwd_data_det_f32(const sr_dcn_bwd_det_desc* dd, void* stre
     p.bpg = d->cin / d->deformable_groups / 8;
     p.dg = d->deformable_groups;
     p.logit = d->mask_is_logit;
-    p.L = 0;  // ceil(log2(9 * h * w))
-    while ((1ll << p.L) < 9 * hw) ++p.L;
-    if (hipMemsetAsync(dd->workspace, 0, acc_bytes + scale_bytes, stream) != hipSuccess) {
-      sr::set_error("%s: clearing the workspace: %s", who, hipGetErrorString(hipGetLastError()));
-      return SR_ELAUNCH;
-    }
+    p.L = fixsum::level_of(9 * hw);
     const bool prof = sr::prof_on();
     const double px = (double)d->n * (double)hw, ch = d->cin;
-    auto record = [&](int id, double flops, double bytes) {
-      sr_launch_record r = {};
-      r.kernel_id = id;
-      r.cin = d->cin;
-      r.cout = d->cout;
-      r.n = d->n;
-      r.h = d->h;
-      r.w = d->w;
-      r.flops = flops;
-      r.bytes = bytes;
-      sr::prof_begin(stream, r);
-    };
     const long long quads = hw * 2 * 9 * p.cin_blocks;
     const unsigned blocks = (unsigned)std::min<long long>((quads + 255) / 256, 1024);
-    if (prof) record(184, px * (9.0 * ch + 9.0 * p.dg), 4.0 * px * (9.0 * ch + 9.0 * p.dg));
+    if (prof) sr::prof_rec(stream, 184, d->cin, d->cout, d->n, d->h, d->w, px * (9.0 * ch + 9.0 * p.dg), 4.0 * px * (9.0 * ch + 9.0 * p.dg));
     hipLaunchKernelGGL(deform_det_scale_kernel, dim3(blocks, (unsigned)d->n), dim3(256), 0, stream, p);
     if (prof) sr::prof_end(stream);
     SR_CHECK_LAUNCH("sr_dcn_bwd_data_det_f32 scale launch");
     // per element of dcol: itself, two offsets and a mask value, nine float64 operations, four 8-byte read-modify-writes
-    if (prof) record(185, px * 9.0 * ch * 12.0, px * 9.0 * ch * (4.0 + 12.0 + 64.0));
+    if (prof) sr::prof_rec(stream, 185, d->cin, d->cout, d->n, d->h, d->w, px * 9.0 * ch * 12.0, px * 9.0 * ch * (4.0 + 12.0 + 64.0));
     hipLaunchKernelGGL(deform_det_scatter_kernel, dim3((unsigned)((hw + 31) / 32), (unsigned)(9 * p.cin_blocks), (unsigned)d->n), dim3(256), 0,
                        stream, p);
     if (prof) sr::prof_end(stream);
     SR_CHECK_LAUNCH("sr_dcn_bwd_data_det_f32 scatter launch");
-    if (prof) record(186, px * ch * 2.0, px * ch * 12.0);
+    if (prof) sr::prof_rec(stream, 186, d->cin, d->cout, d->n, d->h, d->w, px * ch * 2.0, px * ch * 12.0);
     hipLaunchKernelGGL(deform_det_finish_kernel, dim3((unsigned)(((long long)d->cin * hw + 255) / 256), (unsigned)d->n), dim3(256), 0, stream,
                        p);
     if (prof) sr::prof_end(stream);

@@ -14,6 +14,7 @@
 // dcol = Wt * dy, and one kernel for doffset / dmask (gather, fixed order) and dx (atomicAdd scatter).
 #include <algorithm>
 
+#include "dcn_device.h"
 #include "sr_internal.h"
 #include "../../include/sr_hip_dcn.h"
 
@@ -37,38 +38,10 @@ struct DcnParams {
   float slope;
 };
 
-// One sampling position (dmcn_im2col_bilinear and the `inside` test of its caller, deform_conv_cuda_kernel.cu:466-497, 618):
-// the top-left corner, the four weights and which corners lie in the image.  Outside, no corner is valid.
-struct Bilinear {
-  int hl, wl;
-  float lh, lw, hh, hw;
-  bool v1, v2, v3, v4;
-};
-
-__device__ __forceinline__ Bilinear bilinear_at(float h_im, float w_im, int H, int W) {
-  Bilinear b;
-  const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-  if (!inside) h_im = w_im = 0.f;  // also NaN and huge offsets: nothing below is used
-  const float fh = floorf(h_im), fw = floorf(w_im);
-  b.hl = (int)fh;
-  b.wl = (int)fw;
-  b.lh = h_im - fh;
-  b.lw = w_im - fw;
-  b.hh = 1.f - b.lh;
-  b.hw = 1.f - b.lw;
-  const bool t = b.hl >= 0, bo = b.hl + 1 <= H - 1, l = b.wl >= 0, r = b.wl + 1 <= W - 1;
-  b.v1 = inside && t && l;
-  b.v2 = inside && t && r;
-  b.v3 = inside && bo && l;
-  b.v4 = inside && bo && r;
-  return b;
-}
-
-__device__ __forceinline__ float channel_at(const float* t, long long HW, long long pix, int c) {
-  return t[((long long)(c >> 3) * HW + pix) * 8 + (c & 7)];
-}
-
-__device__ __forceinline__ float mask_value(float m, int logit) { return logit ? 1.f / (1.f + expf(-m)) : m; }
+using dcndev::Bilinear;
+using dcndev::channel_at;
+using dcndev::mask_value;
+using dcndev::tap_position;
 
 // Four channels (16 bytes at `xc`, the block's plane offset by the half) of the bilinear value, unmasked.
 __device__ __forceinline__ f32x4 sample4(const float* xc, int W, const Bilinear& b) {
@@ -145,9 +118,7 @@ __global__ __launch_bounds__(256) void dcn_fwd_f32_kernel(const DcnParams p) {
         const int oc = 18 * g + 2 * tap;
         const float oh = channel_at(off_n, HW, pix, oc), ow = channel_at(off_n, HW, pix, oc + 1);
         const float m = mask_value(channel_at(msk_n, HW, pix, 9 * g + tap), p.logit);
-        const int ti = tap / 3, tj = tap - 3 * ti;
-        const float h_im = (float)(y - 1 + ti) + oh, w_im = (float)(x - 1 + tj) + ow;
-        const Bilinear b = bilinear_at(h_im, w_im, p.H, p.W);
+        const Bilinear b = tap_position(y, x, tap, oh, ow, p.H, p.W);
         v = sample4(xc + half * 4, p.W, b) * m;
       }
       *(f32x4*)(cols + ((tap * TH + row) * 32 + col) * 32 + ((half ^ ((col >> 3) & 1)) * 16)) = v;
@@ -246,8 +217,7 @@ __global__ __launch_bounds__(256) void dcn_cols_kernel(const DcnParams p, float*
   const int oc = 18 * g + 2 * tap;
   const float oh = channel_at(off_n, HW, pix, oc), ow = channel_at(off_n, HW, pix, oc + 1);
   const float m = mask_value(channel_at(msk_n, HW, pix, 9 * g + tap), p.logit);
-  const int ti = tap / 3, tj = tap - 3 * ti;
-  const Bilinear b = bilinear_at((float)(y - 1 + ti) + oh, (float)(x - 1 + tj) + ow, p.H, p.W);
+  const Bilinear b = tap_position(y, x, tap, oh, ow, p.H, p.W);
   const f32x4 v = sample4(p.x + n * p.x_ns + (long long)cb * HW * 8 + half * 4, p.W, b) * m;
   *(f32x4*)(cols + ((n * 9 * p.cin_blocks + (long long)tap * p.cin_blocks + cb) * HW + pix) * 8 + half * 4) = v;
 }
@@ -284,8 +254,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const DcnBwdParams q,
   const int oc = 18 * g + 2 * tap, mc = 9 * g + tap;
   const float oh = channel_at(off_n, HW, pix, oc), ow = channel_at(off_n, HW, pix, oc + 1);
   const float m = mask_value(channel_at(msk_n, HW, pix, mc), p.logit);
-  const int ti = tap / 3, tj = tap - 3 * ti;
-  const Bilinear b = bilinear_at((float)(y - 1 + ti) + oh, (float)(x - 1 + tj) + ow, p.H, p.W);
+  const Bilinear b = tap_position(y, x, tap, oh, ow, p.H, p.W);
   const float w1 = b.hh * b.hw, w2 = b.hh * b.lw, w3 = b.lh * b.hw, w4 = b.lh * b.lw;
   const long long corner = ((long long)b.hl * p.W + b.wl) * 8, down = (long long)p.W * 8;
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};

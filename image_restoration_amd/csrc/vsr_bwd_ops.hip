@@ -2,88 +2,22 @@
 // the trunk call that keeps its activations (the driver of vsr_ops.hip, through vsr_trunk.h) and the trunk's backward as one C call
 // over the existing 3x3 kernels.
 //
-// The step-input adjoint is one kernel for both gradients.  A lane is (pixel, channel e of a block), the channel fastest, and
-// walks the fb blocks: per block it reads one g element, for dflow the four corners of prev (gather, float64 accumulator), for
-// dprev it issues four float atomics.  A wave instruction therefore covers 8 pixels x 8 channels: eight 32-byte runs per corner,
-// contiguous for neighbouring pixels that sample neighbouring cells (a locally constant flow), so the atomics of a wave land in
-// whole lines instead of 64 different ones.  The eight lanes of a pixel add their dflow sums through three xor shuffles; lanes past
-// the image stay in the kernel for them and do nothing else.  No LDS.
+// The step-input adjoint is one kernel for both gradients: the body of vsr_prop_bwd.h with a float atomic per dprev term.
+#include <limits.h>
 #include <math.h>
 
 #include <vector>
 
 #include "../../include/sr_hip_ridnet.h"
 #include "../../include/sr_hip_vsr_bwd.h"
-#include "flow_device.h"
 #include "sr_internal.h"
+#include "vsr_prop_bwd.h"
 #include "vsr_trunk.h"
 
 namespace {
 
 // ----------------------------------------------------------------------------------- adjoint of the propagation step input
-struct PropBwdParams {
-  const float* g;
-  const float* prev;
-  const float* flow;
-  float* dprev;
-  float* dflow;
-  long long g_ns, prev_ns, flow_ns, dprev_ns, dflow_ns;
-  int H, W, fb;
-};
-
-// grid (ceil(HW / 32), n), 256 threads: thread = 8 * (pixel of the workgroup) + channel of the block
-__global__ __launch_bounds__(256) void vsr_prop_input_bwd_kernel(const PropBwdParams p) {
-  const int HW = p.H * p.W;
-  const int e = threadIdx.x & 7;
-  const int pix = blockIdx.x * 32 + (threadIdx.x >> 3);
-  const int n = blockIdx.y;
-  const bool live = pix < HW;
-  int x0 = 0, y0 = 0;
-  float fx = 0.f, fy = 0.f;
-  bool gx_on = false, gy_on = false, ok = false;
-  if (live) {
-    const int py = pix / p.W, px = pix - py * p.W;
-    const float* fl = p.flow + (long long)n * p.flow_ns + pix;
-    ok = flowdev::warp_coord(fl[0], fl[HW], px, py, p.H, p.W, /*border=*/0, x0, y0, fx, fy, gx_on, gy_on);
-  }
-  double sx = 0.0, sy = 0.0;
-  if (ok) {
-    const flowdev::Corners k = flowdev::corners(x0, y0, p.H, p.W);
-    const double ax = fx, ay = fy;
-    const double wq[4] = {(1.0 - ay) * (1.0 - ax), (1.0 - ay) * ax, ay * (1.0 - ax), ay * ax};
-    const float* gp = p.g + (long long)n * p.g_ns + (long long)pix * 8 + e;
-    const float* src = p.prev + (long long)n * p.prev_ns + e;
-    float* dp = p.dprev ? p.dprev + (long long)n * p.dprev_ns + e : nullptr;
-    for (int cb = 0; cb < p.fb; ++cb) {
-      const long long blk = (long long)cb * HW * 8;
-      const float gv = gp[blk];
-      if (p.dflow) {
-        const double v00 = k.ok[0] ? src[blk + (long long)k.off[0] * 8] : 0.f, v01 = k.ok[1] ? src[blk + (long long)k.off[1] * 8] : 0.f;
-        const double v10 = k.ok[2] ? src[blk + (long long)k.off[2] * 8] : 0.f, v11 = k.ok[3] ? src[blk + (long long)k.off[3] * 8] : 0.f;
-        const double gd = gv;
-        sx += gd * ((1.0 - ay) * (v01 - v00) + ay * (v11 - v10));
-        sy += gd * ((1.0 - ax) * (v10 - v00) + ax * (v11 - v01));
-      }
-      if (dp) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (k.ok[q] && wq[q] != 0.0) atomicAdd(dp + blk + (long long)k.off[q] * 8, (float)((double)gv * wq[q]));  // rounded once
-      }
-    }
-  }
-  if (p.dflow) {  // uniform: every lane of the workgroup takes part in the shuffles
-#pragma unroll
-    for (int m = 1; m < 8; m <<= 1) {
-      sx += __shfl_xor(sx, m);
-      sy += __shfl_xor(sy, m);
-    }
-    if (live && e == 0) {
-      float* d = p.dflow + (long long)n * p.dflow_ns + pix;
-      d[0] = ok && gx_on ? (float)sx : 0.f;
-      d[HW] = ok && gy_on ? (float)sy : 0.f;
-    }
-  }
-}
+__global__ __launch_bounds__(256) void vsr_prop_input_bwd_kernel(const vsrprop::Params p) { vsrprop::input_bwd_body<false>(p); }
 
 // --------------------------------------------------------------------------------------------------- the trunk's backward
 // Channel counts and offsets of the data-gradient images, in state_dict order
@@ -132,49 +66,16 @@ bool make_dgrad_plan(const sr_vsr_trunk_cfg* c, DgradPlan* P) {
 extern "C" int sr_vsr_prop_input_bwd_f32(const sr_vsr_prop_bwd_desc* d, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const char* who = "sr_vsr_prop_input_bwd_f32";
-  SR_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  SR_CHECK_ARG(d->g && d->prev && d->flow, "%s: null g / prev / flow", who);
-  SR_CHECK_ARG(d->dprev || d->dflow, "%s: dprev and dflow are both NULL: nothing to compute", who);
-  SR_CHECK_ARG(d->n > 0 && d->n <= 65535 && d->h > 0 && d->w > 0 && d->fb > 0 && d->fb < 65535, "%s: bad shape n=%d h=%d w=%d fb=%d", who,
-               d->n, d->h, d->w, d->fb);
-  const long long hw = (long long)d->h * d->w, win = hw * 8 * d->fb;
-  SR_CHECK_ARG(hw < (1ll << 28), "%s: image too large for 32-bit plane offsets", who);
-  SR_CHECK_ARG(sr::aligned16(d->g) && sr::aligned16(d->prev) && sr::aligned16(d->dprev), "%s: CB8 windows must be 16-byte aligned", who);
-  SR_CHECK_ARG(((uintptr_t)d->flow & 3u) == 0 && ((uintptr_t)d->dflow & 3u) == 0, "%s: flow / dflow must be 4-byte aligned", who);
-  SR_CHECK_ARG(d->g_img_stride % 4 == 0 && d->prev_img_stride % 4 == 0 && (!d->dprev || d->dprev_img_stride % 4 == 0),
-               "%s: image strides of CB8 windows must be multiples of 4 floats", who);
-  SR_CHECK_ARG(d->n == 1 || (d->g_img_stride >= win && d->prev_img_stride >= win && d->flow_img_stride >= 2 * hw &&
-                             (!d->dprev || d->dprev_img_stride >= win) && (!d->dflow || d->dflow_img_stride >= 2 * hw)),
-               "%s: an image stride is smaller than the image", who);
-  SR_CHECK_ARG(d->dprev != d->g && d->dprev != d->prev && d->dflow != d->flow, "%s: a destination must not be a source", who);
-  PropBwdParams p = {};
-  p.g = d->g;
-  p.prev = d->prev;
-  p.flow = d->flow;
-  p.dprev = d->dprev;
-  p.dflow = d->dflow;
-  p.g_ns = d->g_img_stride;
-  p.prev_ns = d->prev_img_stride;
-  p.flow_ns = d->flow_img_stride;
-  p.dprev_ns = d->dprev_img_stride;
-  p.dflow_ns = d->dflow_img_stride;
-  p.H = d->h;
-  p.W = d->w;
-  p.fb = d->fb;
+  vsrprop::Params p = {};
+  if (int rc = vsrprop::check_and_fill(who, d, LLONG_MAX, &p)) return rc;
+  const long long hw = (long long)d->h * d->w;
   const dim3 grid((unsigned)((hw + 31) / 32), (unsigned)d->n);
   const bool prof = sr::prof_on();
   if (prof) {
-    sr_launch_record r = {};
-    r.kernel_id = 178;
-    r.cin = r.cout = 8 * d->fb;
-    r.n = d->n;
-    r.h = d->h;
-    r.w = d->w;
     const double px = (double)d->n * (double)hw, ch = 8.0 * d->fb;
     // per pixel and channel: g once; dflow: four corner reads and 14 float64 operations; dprev: four read-modify-writes
-    r.flops = px * ch * ((d->dflow ? 14.0 : 0.0) + (d->dprev ? 8.0 : 0.0));
-    r.bytes = px * (ch * (4.0 + (d->dflow ? 16.0 : 0.0) + (d->dprev ? 32.0 : 0.0)) + 8.0 + (d->dflow ? 8.0 : 0.0));
-    sr::prof_begin(stream, r);
+    sr::prof_rec(stream, 178, 8 * d->fb, 8 * d->fb, d->n, d->h, d->w, px * ch * ((d->dflow ? 14.0 : 0.0) + (d->dprev ? 8.0 : 0.0)),
+                 px * (ch * (4.0 + (d->dflow ? 16.0 : 0.0) + (d->dprev ? 32.0 : 0.0)) + 8.0 + (d->dflow ? 8.0 : 0.0)));
   }
   hipLaunchKernelGGL(vsr_prop_input_bwd_kernel, grid, dim3(256), 0, stream, p);
   if (prof) sr::prof_end(stream);

@@ -958,6 +958,27 @@ def dcn_wgrad(cols, dy, cout, cin, want_bias=True):
     return dw, db
 
 
+def _dcn_bwd_desc(d, dcol, x, offset, mask, dg, mask_is_logit, dx, doffset, dmask):
+    """The fields of a struct sr_dcn_bwd_desc; ``dx`` and ``doffset`` / ``dmask`` may be None.  The callers check that they fit."""
+    _dcn_desc(d.fwd, x, offset, mask, dg, mask_is_logit, 1)
+    d.dcol = dcol.ptr
+    if dx is not None:
+        d.dx, d.dx_img_stride = dx.ptr, dx.img_stride
+    if doffset is not None:
+        d.doffset, d.doffset_img_stride, d.dmask, d.dmask_img_stride = doffset.ptr, doffset.img_stride, dmask.ptr, dmask.img_stride
+    return d
+
+
+def _det_workspace(who, dd, device, nbytes, workspace):
+    """The workspace fields of a deterministic descriptor: ``workspace`` (uint8, at least ``nbytes`` on ``device``), or the
+    grow-only scratch when None."""
+    if workspace is None:
+        workspace = scratch(device, nbytes, who)
+    _arg(workspace.dtype == torch.uint8 and workspace.numel() >= nbytes and workspace.device == device,
+         f'{who}: the workspace is too small')
+    dd.workspace, dd.workspace_bytes = workspace.data_ptr(), nbytes
+
+
 def dcn_bwd_data(dcol, x, offset, mask, dg, *, mask_is_logit=False, want_dx=True, dx=None, doffset=None, dmask=None):
     """dx (atomicAdd scatter into a zeroed CB8 tensor, or ADDED into the CB8 window ``dx`` when given; returned, or None) and,
     into the CB8 windows ``doffset`` / ``dmask`` (given together or not at all), the offset and mask (or logit) gradients — one
@@ -966,14 +987,8 @@ def dcn_bwd_data(dcol, x, offset, mask, dg, *, mask_is_logit=False, want_dx=True
     if dx is None and want_dx:
         dx = CB8.zeros(x.n, x.channels, x.h, x.w, x.device)
     assert dx is None or (dx.n, dx.cbn, dx.h, dx.w) == (x.n, x.cbn, x.h, x.w)
-    d = _lib.DcnBwdDesc()
-    _dcn_desc(d.fwd, x, offset, mask, dg, mask_is_logit, 1)
-    d.dcol = dcol.ptr
-    if dx is not None:
-        d.dx, d.dx_img_stride = dx.ptr, dx.img_stride
-    if doffset is not None:
-        assert doffset.channels >= 18 * dg and dmask.channels >= 9 * dg
-        d.doffset, d.doffset_img_stride, d.dmask, d.dmask_img_stride = doffset.ptr, doffset.img_stride, dmask.ptr, dmask.img_stride
+    assert doffset is None or (doffset.channels >= 18 * dg and dmask.channels >= 9 * dg)
+    d = _dcn_bwd_desc(_lib.DcnBwdDesc(), dcol, x, offset, mask, dg, mask_is_logit, dx, doffset, dmask)
     launch('sr_dcn_bwd_data_f32', x.device, C.byref(d))
     return dx
 
@@ -996,21 +1011,12 @@ def dcn_bwd_data_det(dcol, x, offset, mask, dg, *, mask_is_logit=False, want_dx=
         dx = CB8.empty(x.n, x.channels, x.h, x.w, x.device)
     _arg(dx is None or (isinstance(dx, CB8) and (dx.n, dx.cbn, dx.h, dx.w) == (x.n, x.cbn, x.h, x.w)), f'{who}: dx does not fit')
     dd = _lib.DcnBwdDetDesc()
-    d = dd.d
-    _dcn_desc(d.fwd, x, offset, mask, dg, mask_is_logit, 1)
-    d.dcol = dcol.ptr
+    _dcn_bwd_desc(dd.d, dcol, x, offset, mask, dg, mask_is_logit, dx, doffset, dmask)
     if dx is not None:
-        d.dx, d.dx_img_stride = dx.ptr, dx.img_stride
         nbytes = dcn_bwd_data_det_workspace_bytes(x.n, x.channels, x.h, x.w)
         _arg(nbytes > 0, f'{who}: bad shape n={x.n} cin={x.channels} h={x.h} w={x.w}')
-        if workspace is None:
-            workspace = scratch(x.device, nbytes, who)
-        _arg(workspace.dtype == torch.uint8 and workspace.numel() >= nbytes and workspace.device == x.device,
-             f'{who}: the workspace is too small')
-        dd.workspace, dd.workspace_bytes = workspace.data_ptr(), nbytes
-    if doffset is not None:
-        _arg(doffset.channels >= 18 * dg and dmask.channels >= 9 * dg, f'{who}: doffset / dmask do not fit')
-        d.doffset, d.doffset_img_stride, d.dmask, d.dmask_img_stride = doffset.ptr, doffset.img_stride, dmask.ptr, dmask.img_stride
+        _det_workspace(who, dd, x.device, nbytes, workspace)
+    _arg(doffset is None or (doffset.channels >= 18 * dg and dmask.channels >= 9 * dg), f'{who}: doffset / dmask do not fit')
     _launch_arg('sr_dcn_bwd_data_det_f32', x.device, C.byref(dd))
     return dx
 
@@ -1868,18 +1874,13 @@ def vsr_trunk_bf16(cfg, blob, src, out):
 # ---- the recurrent backward of BasicVSR: the step-input adjoint, the trunk call that keeps its activations and the trunk's
 # backward (include/sr_hip_vsr_bwd.h) ----
 
-def vsr_prop_input_bwd(g, prev, flow, dprev=None, dflow=None):
-    """The adjoint of vsr_prop_input with respect to ``prev`` and ``flow`` — one sr_vsr_prop_input_bwd_f32 launch.  ``g``: CB8
-    window, the gradient of warp_out; ``prev``: the CB8 window that was warped; ``flow``: the fp32 [N, 2, H, W] view the forward
-    read.  ``dprev``: CB8 window the gradient is ADDED into with float atomics (never zeroed here), or None; ``dflow``: fp32
-    [N, 2, H, W] view with dense images the flow gradient is stored into (a float64 gather, bit-reproducible), or None."""
-    who = 'vsr_prop_input_bwd'
+def _vsr_prop_bwd_desc(who, d, g, prev, flow, dprev, dflow):
+    """Checks the operands of the step-input adjoint and fills a struct sr_vsr_prop_bwd_desc from them."""
     _arg(isinstance(g, CB8) and isinstance(prev, CB8) and (prev.n, prev.h, prev.w, prev.cbn) == (g.n, g.h, g.w, g.cbn),
          f'{who}: g and prev must be CB8 windows of one shape')
     n, h, w = g.n, g.h, g.w
     _need_cuda(flow, who)
     _arg(dprev is not None or dflow is not None, f'{who}: nothing to compute')
-    d = _lib.VsrPropBwdDesc()
     for name, t in (('flow', flow), ('dflow', dflow)):
         if t is None:
             continue
@@ -1892,6 +1893,15 @@ def vsr_prop_input_bwd(g, prev, flow, dprev=None, dflow=None):
         d.dprev, d.dprev_img_stride = dprev.ptr, dprev.img_stride
     d.g, d.g_img_stride, d.prev, d.prev_img_stride = g.ptr, g.img_stride, prev.ptr, prev.img_stride
     d.n, d.h, d.w, d.fb = n, h, w, g.cbn
+    return d
+
+
+def vsr_prop_input_bwd(g, prev, flow, dprev=None, dflow=None):
+    """The adjoint of vsr_prop_input with respect to ``prev`` and ``flow`` — one sr_vsr_prop_input_bwd_f32 launch.  ``g``: CB8
+    window, the gradient of warp_out; ``prev``: the CB8 window that was warped; ``flow``: the fp32 [N, 2, H, W] view the forward
+    read.  ``dprev``: CB8 window the gradient is ADDED into with float atomics (never zeroed here), or None; ``dflow``: fp32
+    [N, 2, H, W] view with dense images the flow gradient is stored into (a float64 gather, bit-reproducible), or None."""
+    d = _vsr_prop_bwd_desc('vsr_prop_input_bwd', _lib.VsrPropBwdDesc(), g, prev, flow, dprev, dflow)
     _launch_arg('sr_vsr_prop_input_bwd_f32', g.device, C.byref(d))
     return dprev, dflow
 
@@ -1907,31 +1917,10 @@ def vsr_prop_input_bwd_det(g, prev, flow, dprev=None, dflow=None, workspace=None
     when None) and added into ``dprev`` with one rounding; ``dflow`` is vsr_prop_input_bwd's bit for bit.  Three launches with
     ``dprev``, one without."""
     who = 'vsr_prop_input_bwd_det'
-    _arg(isinstance(g, CB8) and isinstance(prev, CB8) and (prev.n, prev.h, prev.w, prev.cbn) == (g.n, g.h, g.w, g.cbn),
-         f'{who}: g and prev must be CB8 windows of one shape')
-    n, h, w = g.n, g.h, g.w
-    _need_cuda(flow, who)
-    _arg(dprev is not None or dflow is not None, f'{who}: nothing to compute')
     dd = _lib.VsrPropBwdDetDesc()
-    d = dd.d
-    for name, t in (('flow', flow), ('dflow', dflow)):
-        if t is None:
-            continue
-        _arg(t.dtype == torch.float32 and tuple(t.shape) == (n, 2, h, w) and t[0].is_contiguous() and t.device == g.device,
-             f'{who}: {name} must be an fp32 [{n}, 2, {h}, {w}] view with dense images, got {t.dtype} {tuple(t.shape)}')
-        setattr(d, name, t.data_ptr())
-        setattr(d, name + '_img_stride', t.stride(0))
+    _vsr_prop_bwd_desc(who, dd.d, g, prev, flow, dprev, dflow)
     if dprev is not None:
-        _arg(isinstance(dprev, CB8) and (dprev.n, dprev.h, dprev.w, dprev.cbn) == (n, h, w, g.cbn), f'{who}: dprev does not fit')
-        d.dprev, d.dprev_img_stride = dprev.ptr, dprev.img_stride
-        nbytes = vsr_prop_input_bwd_det_workspace_bytes(n, h, w, g.cbn)
-        if workspace is None:
-            workspace = scratch(g.device, nbytes, who)
-        _arg(workspace.dtype == torch.uint8 and workspace.numel() >= nbytes and workspace.device == g.device,
-             f'{who}: the workspace is too small')
-        dd.workspace, dd.workspace_bytes = workspace.data_ptr(), nbytes
-    d.g, d.g_img_stride, d.prev, d.prev_img_stride = g.ptr, g.img_stride, prev.ptr, prev.img_stride
-    d.n, d.h, d.w, d.fb = n, h, w, g.cbn
+        _det_workspace(who, dd, g.device, vsr_prop_input_bwd_det_workspace_bytes(g.n, g.h, g.w, g.cbn), workspace)
     _launch_arg('sr_vsr_prop_input_bwd_det_f32', g.device, C.byref(dd))
     return dprev, dflow
 

@@ -10,28 +10,19 @@ rint(ldexp(term, k)), is summed in int64 per element, and dx = float32(ldexp(flo
 
 The mask VALUE m is an input of the model (fp32): for a logit mask it is the device's own fp32 sigmoid, which numpy cannot restate
 bit for bit, so the GPU test reads it back from the forward's column kernel; the logits themselves only say whether one is NaN."""
+import os
+import sys
+
 import numpy as np
 
-U = 2.0 ** -24
-INF_BITS = 0x7f800000
-
-
-def max_bits(a):
-    """The unsigned maximum of the bit patterns of |a| (fp32 array); 0 for an empty one."""
-    return int((np.ascontiguousarray(a, np.float32).view(np.uint32) & np.uint32(0x7fffffff)).max(initial=0))
-
-
-def exp_of(bits):
-    """ilogb(M) + 1 for a finite non-zero M given by its bits, denormals included."""
-    return int(np.frexp(float(np.array(bits, np.uint32).view(np.float32)))[1])   # M = f * 2^e, f in [0.5, 1)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fixed_sum_model as FS  # noqa: E402
+from fixed_sum_model import INF_BITS, U, exp_of, max_bits  # noqa: E402,F401
 
 
 def level_of(h, w):
     """L = ceil(log2(9 h w))."""
-    L = 0
-    while (1 << L) < 9 * h * w:
-        L += 1
-    return L
+    return FS.level_of(9 * h * w)
 
 
 def scale_state(md, mm, logit, h, w):
@@ -128,25 +119,21 @@ def det_dx(dcol, offset, m, dg, logit, logits=None):
                     sel = c['inside'][i, g, tap] & (yy >= 0) & (yy <= h - 1) & (xx >= 0) & (xx <= w - 1) & (wt != 0)
                     if not sel.any():
                         continue
-                    scaled = np.rint(np.ldexp(dm[:, sel] * wt[sel][None], k))
+                    scaled = FS.quantise(dm[:, sel] * wt[sel][None], k)
                     maxabs = max(maxabs, float(np.abs(scaled).max()))
                     np.add.at(av, (slice(None), yy[sel], xx[sel]), scaled.astype(np.int64))
                     np.add.at(cv, (slice(None), yy[sel], xx[sel]), 1)
         assert maxabs <= 2.0 ** (61 - L)
         rec.update(acc=acc, count=count, maxabs=maxabs)
         with np.errstate(over='ignore'):
-            out[i] = np.ldexp(acc.astype(np.float64), -k).astype(np.float32)
+            out[i] = FS.scaled_back(acc, k).astype(np.float32)
     return out, info
 
 
 def det_bound(exact, count, absterms, ks):
     """The header's bound per element: 2^-24 |exact| + d 2^-(k + 1) + 2^-50 sum |terms|; ``ks``: k per image (None for an image
     whose dx is zero or NaN)."""
-    bound = U * np.abs(exact) + 2.0 ** -50 * absterms
-    for i, k in enumerate(ks):
-        if k is not None:
-            bound[i] += count[i] * 2.0 ** -(k + 1)
-    return bound
+    return FS.bound(exact, count, absterms, ks)
 
 
 # ------------------------------------------------------------------------------------------------------------ the cases

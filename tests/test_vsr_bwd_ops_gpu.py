@@ -219,6 +219,40 @@ def test_prop_input_bwd_matches_float64(cuda, lib, shape, fb, n):
     print(f'{h}x{w} fb={fb} n={n}: worst error / bound ' + ', '.join(f'{k} {v:.2f}' for k, v in worst.items()))
 
 
+@pytest.mark.parametrize('fb', [1, 9])
+@pytest.mark.parametrize('shape', [(1, 1), (5, 7), (33, 40)], ids=lambda s: f'{s[0]}x{s[1]}')
+def test_prop_input_bwd_dprev_is_exact_on_whole_pixel_flows(cuda, shape, fb):
+    """The float-atomic dprev bit for bit, where it cannot depend on the order of the adds: on a zero flow and on a uniform
+    whole-pixel flow the fractions are exactly 0, so three corner weights are 0.0 (skipped) and the fourth is 1, and a translation
+    maps distinct pixels to distinct elements.  Every element of dprev then receives at most one add, of a term that is g itself:
+    dprev = before + term in one fp32 addition.  (The reference's `count` also counts zero-weight corners and is not used here.)"""
+    (h, w), n = shape, 3
+    rng = np.random.default_rng(1000 * h + 10 * fb + 3)
+    c = 8 * fb
+    prev, g, before = (rng.standard_normal((n, c, h, w)).astype(np.float32).astype(np.float64) for _ in range(3))
+    prev_wide = torch.full((n, fb + 2, h, w, 8), NAN, device=cuda)
+    prev_wide[:, 1:1 + fb] = _to_cb8(prev, cuda)
+    g_wide = torch.full((n, fb + 3, h, w, 8), NAN, device=cuda)
+    g_wide[:, 2:2 + fb] = _to_cb8(g, cuda)
+    for name, (fx, fy) in (('zero', (0.0, 0.0)), ('shifted', (2.0, -1.0))):
+        flow = np.empty((n, 2, h, w), np.float32)
+        flow[:, 0], flow[:, 1] = fx, fy
+        term = _prop_reference(prev, flow, g)[0]
+        assert np.array_equal(term.astype(np.float32).astype(np.float64), term), name      # exact in fp32: one term, weight 1
+        assert np.abs(term).max() > 0, name                                                # part of the image stays inside
+        if name == 'shifted' and h * w > 1:
+            assert int((term == 0).all(1).sum()) > 0, name                                 # and part of it gets nothing
+        want = before.astype(np.float32) + term.astype(np.float32)                         # one fp32 addition
+        flows = torch.full((n, 2, 2, h, w), NAN, device=cuda)
+        flows[:, 1] = torch.from_numpy(flow).to(cuda)
+        dprev_wide = torch.full((n, fb + 2, h, w, 8), 777.0, device=cuda)
+        dprev_wide[:, 1:1 + fb] = _to_cb8(before, cuda)
+        dflows = torch.full((n, 3, 2, h, w), NAN, device=cuda)
+        H.vsr_prop_input_bwd(H.CB8(g_wide, 2, fb), H.CB8(prev_wide, 1, fb), flows[:, 1], H.CB8(dprev_wide, 1, fb), dflows[:, 2])
+        assert bool((dprev_wide[:, 0] == 777.0).all()) and bool((dprev_wide[:, 1 + fb] == 777.0).all()), name
+        assert _same(dprev_wide[:, 1:1 + fb], _to_cb8(want, cuda)), name
+
+
 # ------------------------------------------------------------------------------------------------------ trunk, kept
 def _trunk_case(num_feat, num_block, segs, n, h, w, dev, seed=3):
     """(cfg, device parameters in state_dict order, numpy state dict, source window inside a wider NaN tensor, its blocks)."""

@@ -12,24 +12,16 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fixed_sum_model as FS  # noqa: E402
 import flow_restate as FR  # noqa: E402
+from fixed_sum_model import INF_BITS, U  # noqa: E402,F401
 
-U = 2.0 ** -24
-INF_BITS = 0x7f800000
-
-
-def scale_bits(g_img):
-    """The unsigned maximum of the bit patterns of |g| over one image (fp32 array)."""
-    return int((np.ascontiguousarray(g_img, np.float32).view(np.uint32) & np.uint32(0x7fffffff)).max())
+scale_bits = FS.max_bits    # of |g| over one image
 
 
 def shift_of(mbits, h, w):
     """(k, e, L) for a finite non-zero M given by its bits."""
-    m = float(np.array(mbits, np.uint32).view(np.float32))
-    e = int(np.frexp(m)[1])                      # m = f * 2^e with f in [0.5, 1): ilogb(m) + 1, denormals included
-    L = 2
-    while (1 << L) < 4 * h * w:
-        L += 1
+    e, L = FS.exp_of(mbits), FS.level_of(4 * h * w)
     return 61 - e - L, e, L
 
 
@@ -72,24 +64,20 @@ def det_dprev(before, g, flow):
             ys, xs = yy[sel], xx[sel]
             for ch in range(c):
                 term = (gd[ch] * wt[i])[sel]
-                scaled = np.rint(np.ldexp(term, k))
+                scaled = FS.quantise(term, k)
                 assert np.abs(scaled).max(initial=0.0) <= 2.0 ** (61 - L)
                 np.add.at(acc[ch], (ys, xs), scaled.astype(np.int64))
                 np.add.at(absacc[ch], (ys, xs), np.abs(scaled))
                 np.add.at(count[ch], (ys, xs), 1)
         rec.update(k=k, e=e, L=L, acc=acc, absacc=absacc, count=count)
-        out[i] = (before[i].astype(np.float64) + np.ldexp(acc.astype(np.float64), -k)).astype(np.float32)
+        out[i] = (before[i].astype(np.float64) + FS.scaled_back(acc, k)).astype(np.float32)
     return out, info
 
 
 def det_bound(before, exact, count, absterms, ks):
     """The header's bound per element: 2^-24 |before + exact| + d 2^-(k + 1) + 2^-50 sum |terms|; ``ks``: k per image (None for an
     image that is skipped: the bound is then 0 only where nothing is added)."""
-    bound = U * np.abs(before + exact) + 2.0 ** -50 * absterms
-    for i, k in enumerate(ks):
-        if k is not None:
-            bound[i] += count[i] * 2.0 ** -(k + 1)
-    return bound
+    return FS.bound(before + exact, count, absterms, ks)
 
 
 def case_data(h, w, fb, n):
